@@ -11,11 +11,22 @@ on every frame and ORBmatcher::SearchForInitialization of every frame against it
 checkOrientation).  Keypoints / descriptors / match indices
 come back to host memory inside the timed region (they are the path's outputs).
 
-`value`: frames resident in HBM when the timed region starts (the task's bench contract).  The same run also times
-the stream with the frames starting in page-locked HOST memory (`pcie_inclusive`: H2D of every frame inside the timed
-region, the figure SURVEY.md s8(d) defines) and prints it next to the measured link rate.
+`value`: frames resident in HBM when the timed region starts (the task's bench contract).  A plain run does only what that
+figure needs: it sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is given, and prints
+the line.  Everything else below is measured or checked only with --full.
 
-Self-check against the oracle's per-position digests (tests/golden/stream1080_digests.json), twice: (1) before anything is
+--dump-outputs DIR (after the timed steps): a fixed, seeded sample of 64 frames of the LAST timed step, what Stream.pop() handed
+the caller for them, as DIR/<name>.npy in float32 / float64 -- frames (stream position, counted from the first warm-up frame),
+num_keypoints, keypoints (x, y, size, angle, response, octave, class_id per row, the sampled frames' rows one after another),
+descriptors (32 byte values per row), num_matches (SearchForInitialization's return value), num_prev_keypoints and matches12
+(vnMatches12: one entry per keypoint of the frame's predecessor, the sampled frames' entries one after another).  The warm-up
+starts at a multiple of the stream's period, so the inputs depend on the arguments only and two builds can be compared output
+for output.
+
+--full also times the stream with the frames starting in page-locked HOST memory (`pcie_inclusive`: H2D of every frame inside
+the timed region, the figure SURVEY.md s8(d) defines) and prints it next to the measured link rate.
+
+--full self-checks against the oracle's per-position digests (tests/golden/stream1080_digests.json), twice: (1) before anything is
 timed the WHOLE forwards-and-backwards period of the stream (510 positions: every pool frame, the turn-around, every backward
 pair) goes through the same runner; (2) INSIDE the timed region the batch popped last in every step is copied, and after the
 clock has stopped every frame of those copies is checked at its stream position (`verify.timed_verified`,
@@ -27,7 +38,7 @@ traffic is the barrier and the max-over-ranks of the elapsed time (gloo, CPU ten
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) or, when WORLD_SIZE is unset, by
 bench.py itself: `python bench.py --gpus N` spawns the N ranks as fresh child processes before it touches any GPU.
 
-One JSON line on rank 0 (see the task's bench contract) with extra objects:
+One JSON line on rank 0 (see the task's bench contract) with extra objects (filled by --full, null otherwise):
   roofline       -- dominant kernel (k_fast_tasks): algorithmic bytes per launch / HIP-event duration vs HBM peak,
                     plus its vector-instruction-issue roof (the bound that actually explains its time)
   cpu_baseline   -- the CPU oracle (scalar port, 1 core) on a bounded sample of the same frames
@@ -36,6 +47,7 @@ One JSON line on rank 0 (see the task's bench contract) with extra objects:
 import argparse
 import collections
 import json
+import math
 import os
 
 # Four extraction batches in flight need more than the HIP runtime's default of 4 hardware queues (two streams folded onto one
@@ -82,6 +94,11 @@ def parse_args():
     ap.add_argument('--plumbing-only', action='store_true',
                     help='CPU test aid for the N>1 control plane: rendezvous, barrier, max-over-ranks and the JSON line with NO '
                          'hot-path work and no value (tests/test_multiproc.py); never a measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='also the digest self-checks, the PCIe-inclusive leg, roofline, single-frame latencies, the config-5 / tracking / BoW '
+                         'legs and the CPU baselines (a plain run times the headline stream only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write a seeded 64-frame sample of the last step\'s outputs to DIR/<name>.npy (rank 0)')
     return ap.parse_args()
 
 
@@ -202,13 +219,15 @@ def run_single_stream(args):
         for d in sorted(set(devices)):
             api.device_synchronize(d)
 
-    table = None if (args.no_verify or args.no_match or args.pool != wl.POOL) else load_digest_table(seed)
+    table = None if (not args.full or args.no_verify or args.no_match or args.pool != wl.POOL) else load_digest_table(seed)
     verify = {'verified': None}
     if table:
         verify = verify_period(wl, table, seed, B, lambda nb, cb: run(nb, cb))
     t_end = time.perf_counter() + args.prewarm_seconds
     while time.perf_counter() < t_end:
         run(subs)
+    run(submissions_to_align(pos[0], B, args.pool))
+    dump = OutputSample(step_frames, B, pos[0]) if args.dump_outputs else None
     run(args.warmup * subs)
     samples = []
     every = -(-args.steps // 32)
@@ -216,6 +235,8 @@ def run_single_stream(args):
 
     def sample(p0, res, fst):
         popped[0] += 1
+        if dump is not None and (popped[0] - 1) // subs == args.steps - 1:
+            dump.take((popped[0] - 1) % subs, p0, res, 0 if fst else last_n[0])
         k, last = divmod(popped[0], subs)
         if last == 0 and (k - 1) % every == 0 and table is not None:
             samples.append((p0, tuple(a.copy() for a in res), last_n[0]))
@@ -254,6 +275,8 @@ def run_single_stream(args):
            'roofline': None, 'cpu_baseline': None,
            'note': 'single-stream mode (SURVEY.md s8(e)); the kernels are the per-GPU-stream mode\'s: its line carries roofline and cpu_baseline'}
     st.close()
+    if dump is not None:
+        out['dumped_outputs'] = dump.write(args.dump_outputs)
     print(json.dumps(out), flush=True)
 
 
@@ -268,7 +291,7 @@ def run_rank(args):
     # leaves torch without devices), then the product library.
     import numpy as np
     import torch
-    have_torch_gpu = torch.cuda.is_available()
+    have_torch_gpu = not args.plumbing_only and torch.cuda.is_available()     # (plumbing: no GPU call at all, whatever the box has)
     if have_torch_gpu:
         torch.cuda.set_device(local_rank)
     dist = None
@@ -338,7 +361,7 @@ def run_rank(args):
     sf = wl.StreamFrames(seed, W, H, args.pool)
     frames = sf.frames()
     dev = api.DeviceFrames(frames, local_rank)
-    want_pinned = (not args.no_pcie) or args.host_input == 'pinned'
+    want_pinned = (args.full and not args.no_pcie) or args.host_input == 'pinned'
     pinned = api.PinnedFrames(frames) if want_pinned else None
 
     # native stream runner: `depth` extractor handles, GPU-resident matching, C++ worker thread
@@ -417,7 +440,7 @@ def run_rank(args):
     samples = []                                # copies of batches popped inside the timed region, checked after the clock stops
     MAX_SAMPLES = 32
 
-    def timed(nsteps, nwarm, source):
+    def timed(nsteps, nwarm, source, dump=None):
         run(nwarm * cur['subs'], source)
         del pop_times[:]
         del samples[:]
@@ -426,6 +449,8 @@ def run_rank(args):
 
         def sample(p0, res, first):
             popped[0] += 1
+            if dump is not None and (popped[0] - 1) // cur['subs'] == nsteps - 1:      # the last step: --dump-outputs
+                dump.take((popped[0] - 1) % cur['subs'], p0, res, 0 if first else cur.get('last_n', 0))
             k, last = divmod(popped[0], cur['subs'])
             if last == 0 and (k - 1) % every == 0 and table is not None:
                 samples.append((p0, tuple(a.copy() for a in res), cur.get('last_n', 0)))
@@ -455,7 +480,7 @@ def run_rank(args):
     # timed region; self-check 2 -- the batches popped INSIDE the timed region -- follows it, see check_samples)
     verify = {'verified': None, 'outputs_sha256': None}
     table = None
-    if not args.no_verify and not args.no_match and not args.bow and args.pool == wl.POOL:
+    if args.full and not args.no_verify and not args.no_match and not args.bow and args.pool == wl.POOL:
         table = load_digest_table(seed)
         verify = verify_period(wl, table, seed, B, lambda n, cb: run(n, 'hbm', cb))
     verify['verified_own'] = verify['verified']
@@ -489,7 +514,9 @@ def run_rank(args):
     head_source = {'pinned': 'pinned', 'pageable': 'pageable', None: 'hbm'}[args.host_input]
     if args.prewarm_seconds > 0:
         prewarm(head_source, args.prewarm_seconds)
-    elapsed = timed(args.steps, args.warmup, head_source)
+    run(submissions_to_align(pos[0], B, args.pool), head_source)
+    dump = OutputSample(step_frames, B, pos[0]) if (args.dump_outputs and rank == 0) else None
+    elapsed = timed(args.steps, args.warmup, head_source, dump)
     verify.update(check_samples())
     if verify.get('verified') is not None and verify.get('timed_verified') is not None:
         verify['verified_before_timing'] = verify['verified']
@@ -514,7 +541,7 @@ def run_rank(args):
         Host frames: a batch computes only after its whole upload, so one batch fewer in flight serves the link better (26.2 k
         frames/s with 3, 25.3 k with 4) -- a runner of its own for this leg."""
         nonlocal st, lookahead
-        if args.no_pcie or head_source != 'hbm':
+        if not args.full or args.no_pcie or head_source != 'hbm':
             return None
         pdepth = min(3, max(1, args.depth))
         pB = min(B, wl.BATCH)                     # a batch computes only after its whole upload: 32-frame submissions serve the link better than 64
@@ -559,145 +586,152 @@ def run_rank(args):
     if rank == 0:
         frames_done = world * step_frames * args.steps
         fps = frames_done / elapsed
-        # roofline of the dominant kernel: k_fast_tasks reads every pyramid pixel once (sum of level
-        # sizes) and writes 4 B per surviving candidate; algorithmic bytes per launch = that x B.
-        ex = api.Extractor(wl.NFEAT, wl.SCALE, wl.NLEVELS, wl.INI_TH, wl.MIN_TH, device=local_rank)   # geometry + candidate count only
-        t = ex.tables()
-        px = 0
-        for l in range(wl.NLEVELS):
-            lw = int(np.rint(np.float32(W) * t['isf'][l]))
-            lh = int(np.rint(np.float32(H) * t['isf'][l]))
-            px += lw * lh
-        ex.extract_batch_ptrs(dev.ptrs[:1], H, W, dev.stride, True)
-        ncand = sum(len(ex.candidates(l, 0)) for l in range(wl.NLEVELS))
-        # the call pattern of the reference's Tracking thread: one blocking ORBextractor::operator() per frame
-        # (Frame.cc:133), frame already in HBM; median wall time of 60 calls on distinct frames, outside the timed region
-        single = None
-        if world == 1 and not args.no_latency:
-            kbuf = np.zeros((1, ex.cap), api.KP_DTYPE)
-            dbuf = np.zeros((1, ex.cap, 32), np.uint8)
-            lat = []
-            for i in range(70):
-                t_a = time.perf_counter()
-                ex.extract_batch_ptrs(dev.ptrs[i % args.pool:i % args.pool + 1], H, W, dev.stride, True, kbuf, dbuf)
-                lat.append(time.perf_counter() - t_a)
-            lat = np.array(lat[10:]) * 1e3
-            single = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4),
-                      'call': 'blocking orbfe_extract_batch of ONE resident 1080p frame (extract only), 60 calls'}
-        # ... and what Frame.cc:133 really hands over: a HOST cv::Mat.  One blocking orbfe_extract per frame, host pointer in
-        # -> keypoints / descriptors in host memory out, from (a) pageable and (b) page-locked memory; 60 calls on distinct frames
-        single_host = None
-        if world == 1 and not args.no_latency:
-            single_host = {}
-            kbuf = np.zeros((1, ex.cap), api.KP_DTYPE)
-            dbuf = np.zeros((1, ex.cap, 32), np.uint8)
-            nlat = 64
-            pin_lat = api.PinnedFrames([frames[i % len(frames)] for i in range(nlat)])
-            for name, ptr_of in (('pageable', lambda i: frames[i % len(frames)].ctypes.data), ('page_locked', lambda i: pin_lat.ptrs[i])):
+        step_ms = np.diff(head_pops[subs - 1::subs]) * 1e3 if len(head_pops) >= 3 * subs else None
+        value_p50 = round(world * step_frames / (float(np.percentile(step_ms, 50)) * 1e-3), 2) if step_ms is not None and len(step_ms) > 1 else None
+        single = single_host = roofline = None
+        if args.full:
+            # roofline of the dominant kernel: k_fast_tasks reads every pyramid pixel once (sum of level
+            # sizes) and writes 4 B per surviving candidate; algorithmic bytes per launch = that x B.
+            ex = api.Extractor(wl.NFEAT, wl.SCALE, wl.NLEVELS, wl.INI_TH, wl.MIN_TH, device=local_rank)   # geometry + candidate count only
+            t = ex.tables()
+            px = 0
+            for l in range(wl.NLEVELS):
+                lw = int(np.rint(np.float32(W) * t['isf'][l]))
+                lh = int(np.rint(np.float32(H) * t['isf'][l]))
+                px += lw * lh
+            ex.extract_batch_ptrs(dev.ptrs[:1], H, W, dev.stride, True)
+            ncand = sum(len(ex.candidates(l, 0)) for l in range(wl.NLEVELS))
+            # the call pattern of the reference's Tracking thread: one blocking ORBextractor::operator() per frame
+            # (Frame.cc:133), frame already in HBM; median wall time of 60 calls on distinct frames, outside the timed region
+            single = None
+            if world == 1 and not args.no_latency:
+                kbuf = np.zeros((1, ex.cap), api.KP_DTYPE)
+                dbuf = np.zeros((1, ex.cap, 32), np.uint8)
+                lat = []
+                for i in range(70):
+                    t_a = time.perf_counter()
+                    ex.extract_batch_ptrs(dev.ptrs[i % args.pool:i % args.pool + 1], H, W, dev.stride, True, kbuf, dbuf)
+                    lat.append(time.perf_counter() - t_a)
+                lat = np.array(lat[10:]) * 1e3
+                single = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4),
+                          'call': 'blocking orbfe_extract_batch of ONE resident 1080p frame (extract only), 60 calls'}
+            # ... and what Frame.cc:133 really hands over: a HOST cv::Mat.  One blocking orbfe_extract per frame, host pointer in
+            # -> keypoints / descriptors in host memory out, from (a) pageable and (b) page-locked memory; 60 calls on distinct frames
+            single_host = None
+            if world == 1 and not args.no_latency:
+                single_host = {}
+                kbuf = np.zeros((1, ex.cap), api.KP_DTYPE)
+                dbuf = np.zeros((1, ex.cap, 32), np.uint8)
+                nlat = 64
+                pin_lat = api.PinnedFrames([frames[i % len(frames)] for i in range(nlat)])
+                for name, ptr_of in (('pageable', lambda i: frames[i % len(frames)].ctypes.data), ('page_locked', lambda i: pin_lat.ptrs[i])):
+                    lat = []
+                    for i in range(nlat + 10):
+                        p = ptr_of(i % nlat)
+                        t_a = time.perf_counter()
+                        ex.extract_batch_ptrs([p], H, W, W, False, kbuf, dbuf)
+                        lat.append(time.perf_counter() - t_a)
+                    lat = np.array(lat[10:]) * 1e3
+                    single_host[name] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4)}
+                # (b') the same page-locked call as a C caller issues it: arguments prepared once, the C entry point called directly -- what
+                # include/orbfe/orb_shim.hpp pays; the figures above include os1_amd.api's per-call ctypes / numpy marshalling (about 5 us),
+                # and the library's own clocks split the call into enqueue / GPU wait / output assembly (orbfe_debug_stage_ms)
+                import ctypes as C
+                nout = np.zeros(1, np.int32)
+                arrs = [(C.c_void_p * 1)(pin_lat.ptrs[i]) for i in range(nlat)]
+                cargs = lambda i: (ex.h, 1, arrs[i], 0, H, W, C.c_size_t(W), kbuf.ctypes.data_as(C.c_void_p), dbuf.ctypes.data_as(C.c_void_p),
+                                   int(kbuf.shape[1]), nout.ctypes.data_as(C.c_void_p))
+                prepared = [cargs(i) for i in range(nlat)]
+                lat, stages = [], []
+                for i in range(nlat + 10):
+                    a_ = prepared[i % nlat]
+                    t_a = time.perf_counter()
+                    rc_ = ex.L.orbfe_extract_batch(*a_)
+                    lat.append(time.perf_counter() - t_a)
+                    stages.append(ex.stage_ms())
+                    if rc_:
+                        raise SystemExit('bench: orbfe_extract_batch failed')
+                lat = np.array(lat[10:]) * 1e3
+                stg = np.median(np.array(stages[10:]), 0)
+                single_host['page_locked_prepared_c_call'] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4),
+                                                              'library_stages_ms': {'enqueue': round(float(stg[0]), 4), 'gpu_wait': round(float(stg[1]), 4),
+                                                                                    'output_assembly': round(float(stg[3]), 4), 'total': round(float(stg[4]), 4)}}
+                # (c) the caller's OWN pageable buffer registered once (orbfe_host_register: a capture ring, a long-lived cv::Mat): page-locked route
+                ring = np.stack([frames[i % len(frames)] for i in range(nlat)])
+                reg = api.RegisteredArray(ring)
                 lat = []
                 for i in range(nlat + 10):
-                    p = ptr_of(i % nlat)
+                    p = ring[i % nlat].ctypes.data
                     t_a = time.perf_counter()
                     ex.extract_batch_ptrs([p], H, W, W, False, kbuf, dbuf)
                     lat.append(time.perf_counter() - t_a)
+                reg.close()
                 lat = np.array(lat[10:]) * 1e3
-                single_host[name] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4)}
-            # (b') the same page-locked call as a C caller issues it: arguments prepared once, the C entry point called directly -- what
-            # include/orbfe/orb_shim.hpp pays; the figures above include os1_amd.api's per-call ctypes / numpy marshalling (about 5 us),
-            # and the library's own clocks split the call into enqueue / GPU wait / output assembly (orbfe_debug_stage_ms)
-            import ctypes as C
-            nout = np.zeros(1, np.int32)
-            arrs = [(C.c_void_p * 1)(pin_lat.ptrs[i]) for i in range(nlat)]
-            cargs = lambda i: (ex.h, 1, arrs[i], 0, H, W, C.c_size_t(W), kbuf.ctypes.data_as(C.c_void_p), dbuf.ctypes.data_as(C.c_void_p),
-                               int(kbuf.shape[1]), nout.ctypes.data_as(C.c_void_p))
-            prepared = [cargs(i) for i in range(nlat)]
-            lat, stages = [], []
-            for i in range(nlat + 10):
-                a_ = prepared[i % nlat]
-                t_a = time.perf_counter()
-                rc_ = ex.L.orbfe_extract_batch(*a_)
-                lat.append(time.perf_counter() - t_a)
-                stages.append(ex.stage_ms())
-                if rc_:
-                    raise SystemExit('bench: orbfe_extract_batch failed')
-            lat = np.array(lat[10:]) * 1e3
-            stg = np.median(np.array(stages[10:]), 0)
-            single_host['page_locked_prepared_c_call'] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4),
-                                                          'library_stages_ms': {'enqueue': round(float(stg[0]), 4), 'gpu_wait': round(float(stg[1]), 4),
-                                                                                'output_assembly': round(float(stg[3]), 4), 'total': round(float(stg[4]), 4)}}
-            # (c) the caller's OWN pageable buffer registered once (orbfe_host_register: a capture ring, a long-lived cv::Mat): page-locked route
-            ring = np.stack([frames[i % len(frames)] for i in range(nlat)])
-            reg = api.RegisteredArray(ring)
-            lat = []
-            for i in range(nlat + 10):
-                p = ring[i % nlat].ctypes.data
-                t_a = time.perf_counter()
-                ex.extract_batch_ptrs([p], H, W, W, False, kbuf, dbuf)
-                lat.append(time.perf_counter() - t_a)
-            reg.close()
-            lat = np.array(lat[10:]) * 1e3
-            single_host['registered'] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4)}
-            single_host['call'] = ('blocking orbfe_extract_batch of ONE 1080p frame in HOST memory (the cv::Mat of Frame.cc:133), '
-                                   'keypoints + descriptors returned to host memory, %d calls on distinct frames' % nlat)
-            pin_lat.free()
-        fast_bytes_per_frame = px + 4 * ncand
-        fast_ms_per_launch = kms[1] / max(kbatches, 1)
-        achieved = fast_bytes_per_frame * B / (fast_ms_per_launch * 1e-3) / 1e9 if fast_ms_per_launch > 0 else 0.0
-        prof = load_profile_counters(B)
-        traffic = prof.get('traffic_bytes_per_launch')
-        valu = None
-        if prof.get('valu_insts_per_launch') and fast_ms_per_launch > 0:
-            # the binding roof of this kernel: vector-instruction issue.  Cycles per wave64 instruction are MEASURED, twice:
-            # tools/ubench/valu_rate.hip (profiles/r03_valu_rate.txt) -- 2 cycles for v_fma/add/mul_f32, v_add/sub_u32, and/or/xor,
-            # right shifts and the unpacked 16-bit ops once two waves share a SIMD (the guide's figure), 4 cycles for every packed
-            # 16-bit op, v_alignbyte, v_perm, v_lshlrev_b32, min/max_u32, 24-bit multiplies, DPP / SDWA forms, compares and any
-            # op with a scalar source -- and for the kernel's own mix by the SQ counters (4 * SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU)
-            cpi = prof.get('valu_cycles_per_inst') or 4.0
-            peak = 1024 * 2.4e9 / cpi
-            rate = prof['valu_insts_per_launch'] / (fast_ms_per_launch * 1e-3)
-            valu = {'insts_per_launch': prof['valu_insts_per_launch'], 'insts_per_cell_wave': prof.get('valu_insts_per_cell_wave'),
-                    'cycles_per_inst': cpi, 'cycles_per_inst_source': 'SQ counters of this kernel (' + str(prof.get('source', ''))[:28] + '...) and profiles/r03_valu_rate.txt per opcode',
-                    'issue_peak_per_s': round(peak, 1), 'achieved_per_s': round(rate, 1), 'frac': round(rate / peak, 4),
-                    'frac_if_all_ops_were_2_cycle': round(rate / (1024 * 2.4e9 / 2.0), 4),
-                    'note': 'wave64 VALU instructions (SQ_INSTS_VALU, separate rocprofv3 --pmc pass); peak = 1024 SIMDs x 2.4 GHz / cycles_per_inst'}
-        # ... and the scalar port beside it (round 5): a CU has ONE scalar ALU, visited round-robin by its four SIMDs -- a SIMD's scalar port
-        # takes one SALU instruction per ~4.25 cycles (tools/ubench/salu_rate.hip, profiles/r05_salu_rate.txt) and issues side by side
-        # with the vector port when the two instructions come from different waves (same file, "mix" rows)
-        salu = None
-        if prof.get('salu_insts_per_launch') and fast_ms_per_launch > 0:
-            scpi = prof.get('salu_cycles_per_inst') or 4.25
-            speak = 1024 * 2.4e9 / scpi
-            srate = (prof['salu_insts_per_launch'] + prof.get('smem_insts_per_launch', 0)) / (fast_ms_per_launch * 1e-3)
-            salu = {'insts_per_launch': prof['salu_insts_per_launch'], 'smem_insts_per_launch': prof.get('smem_insts_per_launch'),
-                    'insts_per_cell_wave': prof.get('salu_insts_per_cell_wave'), 'cycles_per_inst': scpi,
-                    'issue_peak_per_s': round(speak, 1), 'achieved_per_s': round(srate, 1), 'frac': round(srate / speak, 4),
-                    'scalar_over_vector_port_time': round((prof['salu_insts_per_launch'] + prof.get('smem_insts_per_launch', 0)) * scpi /
-                                                          (prof['valu_insts_per_launch'] * (prof.get('valu_cycles_per_inst') or 4.0)), 4) if prof.get('valu_insts_per_launch') else None,
-                    'note': 'SQ_INSTS_SALU + SQ_INSTS_SMEM (separate --pmc pass); peak = 1024 SIMDs x 2.4 GHz / 4.25 cycles per scalar instruction per SIMD '
-                            '(measured, profiles/r05_salu_rate.txt); the scalar and the vector port issue side by side (different waves), so the two fractions do not add'}
-        step_ms = np.diff(head_pops[subs - 1::subs]) * 1e3 if len(head_pops) >= 3 * subs else None
-        value_p50 = round(world * step_frames / (float(np.percentile(step_ms, 50)) * 1e-3), 2) if step_ms is not None and len(step_ms) > 1 else None
-        # the WHOLE path against both roofs (not only its dominant kernel): SURVEY.md s8(d)'s algorithmic 30.03 MB per frame x
-        # frames/s against HBM, and the vector instructions of all kernels of a batch (SQ_INSTS_VALU summed over every dispatch of
-        # the committed --pmc pass, profiles/counters.json) / (batch period x issue roof at the pipeline's own measured cycles
-        # per instruction)
-        batch_period_s = elapsed / max(args.steps * subs, 1)
-        pipeline = {'hbm': {'algorithmic_MB_per_frame': 30.03, 'achieved_GBps_per_gpu': round(30.03e6 * fps / world / 1e9, 2),
-                            'frac': round(30.03e6 * fps / world / (HBM_PEAK_GBS * 1e9), 5),
-                            'note': 'SURVEY.md s8(d): pyramid build + FAST + full-level blur + descriptor patches per 1080p frame, resident input'}}
-        if prof.get('pipeline_valu_insts_per_batch'):
-            pcpi = prof.get('pipeline_valu_cycles_per_inst') or 4.0
-            ppeak = 1024 * 2.4e9 / pcpi
-            prate = prof['pipeline_valu_insts_per_batch'] / batch_period_s
-            pipeline['valu'] = {'insts_per_batch': prof['pipeline_valu_insts_per_batch'], 'batch_period_ms': round(batch_period_s * 1e3, 4),
-                                'cycles_per_inst': pcpi, 'issue_peak_per_s': round(ppeak, 1), 'achieved_per_s': round(prate, 1),
-                                'frac': round(prate / ppeak, 4), 'by_kernel': prof.get('pipeline_valu_insts_per_batch_by_kernel'),
-                                'note': 'all kernels of one %d-frame submission (extract + SearchForInitialization), counters from %s' % (B, str(prof.get('source', ''))[:40])}
-        if prof.get('pipeline_salu_insts_per_batch'):
-            scpi = prof.get('salu_cycles_per_inst') or 4.25
-            n_s = prof['pipeline_salu_insts_per_batch'] + prof.get('pipeline_smem_insts_per_batch', 0)
-            pipeline['salu'] = {'insts_per_batch': n_s, 'cycles_per_inst': scpi, 'issue_peak_per_s': round(1024 * 2.4e9 / scpi, 1),
-                                'achieved_per_s': round(n_s / batch_period_s, 1), 'frac': round(n_s / batch_period_s / (1024 * 2.4e9 / scpi), 4)}
+                single_host['registered'] = {'ms_median': round(float(np.median(lat)), 4), 'ms_p90': round(float(np.percentile(lat, 90)), 4)}
+                single_host['call'] = ('blocking orbfe_extract_batch of ONE 1080p frame in HOST memory (the cv::Mat of Frame.cc:133), '
+                                       'keypoints + descriptors returned to host memory, %d calls on distinct frames' % nlat)
+                pin_lat.free()
+            fast_bytes_per_frame = px + 4 * ncand
+            fast_ms_per_launch = kms[1] / max(kbatches, 1)
+            achieved = fast_bytes_per_frame * B / (fast_ms_per_launch * 1e-3) / 1e9 if fast_ms_per_launch > 0 else 0.0
+            prof = load_profile_counters(B)
+            traffic = prof.get('traffic_bytes_per_launch')
+            valu = None
+            if prof.get('valu_insts_per_launch') and fast_ms_per_launch > 0:
+                # the binding roof of this kernel: vector-instruction issue.  Cycles per wave64 instruction are MEASURED, twice:
+                # tools/ubench/valu_rate.hip (profiles/r03_valu_rate.txt) -- 2 cycles for v_fma/add/mul_f32, v_add/sub_u32, and/or/xor,
+                # right shifts and the unpacked 16-bit ops once two waves share a SIMD (the guide's figure), 4 cycles for every packed
+                # 16-bit op, v_alignbyte, v_perm, v_lshlrev_b32, min/max_u32, 24-bit multiplies, DPP / SDWA forms, compares and any
+                # op with a scalar source -- and for the kernel's own mix by the SQ counters (4 * SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU)
+                cpi = prof.get('valu_cycles_per_inst') or 4.0
+                peak = 1024 * 2.4e9 / cpi
+                rate = prof['valu_insts_per_launch'] / (fast_ms_per_launch * 1e-3)
+                valu = {'insts_per_launch': prof['valu_insts_per_launch'], 'insts_per_cell_wave': prof.get('valu_insts_per_cell_wave'),
+                        'cycles_per_inst': cpi, 'cycles_per_inst_source': 'SQ counters of this kernel (' + str(prof.get('source', ''))[:28] + '...) and profiles/r03_valu_rate.txt per opcode',
+                        'issue_peak_per_s': round(peak, 1), 'achieved_per_s': round(rate, 1), 'frac': round(rate / peak, 4),
+                        'frac_if_all_ops_were_2_cycle': round(rate / (1024 * 2.4e9 / 2.0), 4),
+                        'note': 'wave64 VALU instructions (SQ_INSTS_VALU, separate rocprofv3 --pmc pass); peak = 1024 SIMDs x 2.4 GHz / cycles_per_inst'}
+            # ... and the scalar port beside it (round 5): a CU has ONE scalar ALU, visited round-robin by its four SIMDs -- a SIMD's scalar port
+            # takes one SALU instruction per ~4.25 cycles (tools/ubench/salu_rate.hip, profiles/r05_salu_rate.txt) and issues side by side
+            # with the vector port when the two instructions come from different waves (same file, "mix" rows)
+            salu = None
+            if prof.get('salu_insts_per_launch') and fast_ms_per_launch > 0:
+                scpi = prof.get('salu_cycles_per_inst') or 4.25
+                speak = 1024 * 2.4e9 / scpi
+                srate = (prof['salu_insts_per_launch'] + prof.get('smem_insts_per_launch', 0)) / (fast_ms_per_launch * 1e-3)
+                salu = {'insts_per_launch': prof['salu_insts_per_launch'], 'smem_insts_per_launch': prof.get('smem_insts_per_launch'),
+                        'insts_per_cell_wave': prof.get('salu_insts_per_cell_wave'), 'cycles_per_inst': scpi,
+                        'issue_peak_per_s': round(speak, 1), 'achieved_per_s': round(srate, 1), 'frac': round(srate / speak, 4),
+                        'scalar_over_vector_port_time': round((prof['salu_insts_per_launch'] + prof.get('smem_insts_per_launch', 0)) * scpi /
+                                                              (prof['valu_insts_per_launch'] * (prof.get('valu_cycles_per_inst') or 4.0)), 4) if prof.get('valu_insts_per_launch') else None,
+                        'note': 'SQ_INSTS_SALU + SQ_INSTS_SMEM (separate --pmc pass); peak = 1024 SIMDs x 2.4 GHz / 4.25 cycles per scalar instruction per SIMD '
+                                '(measured, profiles/r05_salu_rate.txt); the scalar and the vector port issue side by side (different waves), so the two fractions do not add'}
+            # the WHOLE path against both roofs (not only its dominant kernel): SURVEY.md s8(d)'s algorithmic 30.03 MB per frame x
+            # frames/s against HBM, and the vector instructions of all kernels of a batch (SQ_INSTS_VALU summed over every dispatch of
+            # the committed --pmc pass, profiles/counters.json) / (batch period x issue roof at the pipeline's own measured cycles
+            # per instruction)
+            batch_period_s = elapsed / max(args.steps * subs, 1)
+            pipeline = {'hbm': {'algorithmic_MB_per_frame': 30.03, 'achieved_GBps_per_gpu': round(30.03e6 * fps / world / 1e9, 2),
+                                'frac': round(30.03e6 * fps / world / (HBM_PEAK_GBS * 1e9), 5),
+                                'note': 'SURVEY.md s8(d): pyramid build + FAST + full-level blur + descriptor patches per 1080p frame, resident input'}}
+            if prof.get('pipeline_valu_insts_per_batch'):
+                pcpi = prof.get('pipeline_valu_cycles_per_inst') or 4.0
+                ppeak = 1024 * 2.4e9 / pcpi
+                prate = prof['pipeline_valu_insts_per_batch'] / batch_period_s
+                pipeline['valu'] = {'insts_per_batch': prof['pipeline_valu_insts_per_batch'], 'batch_period_ms': round(batch_period_s * 1e3, 4),
+                                    'cycles_per_inst': pcpi, 'issue_peak_per_s': round(ppeak, 1), 'achieved_per_s': round(prate, 1),
+                                    'frac': round(prate / ppeak, 4), 'by_kernel': prof.get('pipeline_valu_insts_per_batch_by_kernel'),
+                                    'note': 'all kernels of one %d-frame submission (extract + SearchForInitialization), counters from %s' % (B, str(prof.get('source', ''))[:40])}
+            if prof.get('pipeline_salu_insts_per_batch'):
+                scpi = prof.get('salu_cycles_per_inst') or 4.25
+                n_s = prof['pipeline_salu_insts_per_batch'] + prof.get('pipeline_smem_insts_per_batch', 0)
+                pipeline['salu'] = {'insts_per_batch': n_s, 'cycles_per_inst': scpi, 'issue_peak_per_s': round(1024 * 2.4e9 / scpi, 1),
+                                    'achieved_per_s': round(n_s / batch_period_s, 1), 'frac': round(n_s / batch_period_s / (1024 * 2.4e9 / scpi), 4)}
+            roofline = {'kernel': 'k_fast_tasks', 'bound': 'hbm', 'binding_roof': 'valu-issue (see roofline.valu)', 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS,
+                        'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic,
+                        'traffic_source': prof.get('source'),
+                        'algorithmic_bytes_per_launch': fast_bytes_per_frame * B,
+                        'launch_ms': round(fast_ms_per_launch, 4), 'valu': valu, 'salu': salu, 'pipeline': pipeline}
         out = {
             'metric': 'frames/sec extract+match, 1920x1080 @ 2000 ORB feats',
             'value': round(fps, 2), 'value_p50': value_p50,
@@ -737,20 +771,18 @@ def run_rank(args):
             'host_cpu_cores_used_rank0': round(head_cpu / max(elapsed, 1e-9), 2),
             'host_cpu_cores_used_all_ranks': round(cpu_all / max(elapsed, 1e-9), 2),
             'host_worker_ms_per_submission': {'submit': round(wstats[0] / max(wstats[3], 1), 4), 'collect_incl_gpu_wait': round(wstats[1] / max(wstats[3], 1), 4)},
-            'roofline': {'kernel': 'k_fast_tasks', 'bound': 'hbm', 'binding_roof': 'valu-issue (see roofline.valu)', 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS,
-                         'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic,
-                         'traffic_source': prof.get('source'),
-                         'algorithmic_bytes_per_launch': fast_bytes_per_frame * B,
-                         'launch_ms': round(fast_ms_per_launch, 4), 'valu': valu, 'salu': salu, 'pipeline': pipeline},
+            'roofline': roofline,
         }
-        if world == 1 and not args.no_latency:
+        if dump is not None:
+            out['dumped_outputs'] = dump.write(args.dump_outputs)
+        if args.full and world == 1 and not args.no_latency:
             out['config5_search_by_projection'] = config5_leg(api, local_rank, args.cpu_frames > 0)
             out['tracking_step'] = tracking_step_leg(api, local_rank, frames, W, H, wl, args.cpu_frames > 0)
             out['bow'] = bow_leg(api, local_rank, frames, W, H, wl, args.cpu_frames > 0)
-        if world == 1:
+        if args.full and world == 1:
             out['pcie_inclusive'] = pcie_leg()
             out['value_pcie_inclusive'] = (out['pcie_inclusive'] or {}).get('value')
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             out['cpu_baseline'] = cpu_baseline(frames, args.cpu_frames, not args.no_match)
             out['cpu_baseline_all_cores'] = cpu_baseline_all_cores(frames, not args.no_match)
         print(json.dumps(out), flush=True)
@@ -782,6 +814,52 @@ def per_rank_summary(per_rank, aggregate):
         out['slowest_rank'] = {'rank': slow['rank'], 'device': slow['device'], 'numa_node': slow['numa_node']}
         out['aggregate_over_sum_of_rank_rates'] = round(aggregate / sum(vals), 4) if aggregate else None
     return out
+
+
+class OutputSample:
+    """--dump-outputs: a fixed, seeded sample of the frames of the last timed step.  take() is called on every pop of that step
+    (submission `sub` of the step, first stream position p0, the Stream.pop() tuple, the keypoint count of the frame before the
+    batch) and copies the sampled frames only; write() saves them after the clock has stopped."""
+    NFRAMES = 64
+
+    def __init__(self, step_frames, B, base):
+        import numpy as np
+        self.base = base                        # stream position of the first warm-up frame: `frames` counts from there
+        pick = np.sort(np.random.default_rng(0).choice(step_frames, min(self.NFRAMES, step_frames), replace=False))
+        self.by_sub = {}
+        for f in pick.tolist():
+            self.by_sub.setdefault(f // B, []).append(f % B)
+        self.rows = []
+
+    def take(self, sub, p0, res, prev_n):
+        kps, desc, n, m12, nm = res
+        for j in self.by_sub.get(sub, ()):
+            nj, npv = int(n[j]), (prev_n if j == 0 else int(n[j - 1]))
+            self.rows.append((p0 + j - self.base, nj, kps[j, :nj].copy(), desc[j, :nj].copy(), int(nm[j]), m12[j, :npv].copy(), npv))
+
+    def write(self, path):
+        import numpy as np
+        os.makedirs(path, exist_ok=True)
+        rows = sorted(self.rows, key=lambda r: r[0])
+        fields = ('x', 'y', 'size', 'angle', 'response', 'octave', 'class_id')
+        kp = np.concatenate([np.stack([r[2][f].astype(np.float32) for f in fields], 1).reshape(-1, len(fields)) for r in rows])
+        out = {'frames': np.array([r[0] for r in rows], np.float64),
+               'num_keypoints': np.array([r[1] for r in rows], np.float64),
+               'keypoints': kp,
+               'descriptors': np.concatenate([r[3].reshape(-1, 32) for r in rows]).astype(np.float32),
+               'num_matches': np.array([r[4] for r in rows], np.float64),
+               'num_prev_keypoints': np.array([r[6] for r in rows], np.float64),
+               'matches12': np.concatenate([r[5] for r in rows]).astype(np.float32)}
+        for name, a in out.items():
+            np.save(os.path.join(path, name + '.npy'), a)
+        return sorted(out)
+
+
+def submissions_to_align(pos, B, pool):
+    """Submissions of B frames that take the stream from position `pos` to the next multiple of both B and the stream's period: the
+    warm-up and the timed steps then start at the same point of the forwards-and-backwards walk whatever the time-bounded pre-warm
+    (and the self-check) pushed before them, so every run with the same arguments times -- and dumps -- the same frames."""
+    return (-pos % math.lcm(B, max(2 * pool - 2, 1))) // B
 
 
 def load_digest_table(seed):

@@ -1,4 +1,7 @@
 """CPU: the oracle's DBoW2 transform / SearchByBoW restatements against independent pure-Python versions."""
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
@@ -33,26 +36,43 @@ def test_transform_matches_python_restatement(oracle, scoring, weighting):
             assert wof.tolist() == pw and nof.tolist() == pn
 
 
+DBOW2_REF_OUTPUTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dbow2_ref_outputs.npz')
+
+
+def accumulation_cases():
+    """(name, vocabulary image, descriptors, levelsup) of the reference-accumulation check: every scoring / weighting combination."""
+    for scoring in range(6):
+        for weighting in range(4):
+            for i, (image, lu) in enumerate([(synth_vocabulary(3, 10, 3, stop_fraction=0.1), 1), (ragged_vocabulary(4), 2)]):
+                image = with_header(image, scoring, weighting)
+                yield 's%dw%di%d' % (scoring, weighting, i), image, _descs(scoring * 10 + weighting + 100, image, 400), lu
+
+
+def case_digest(image, d, lu):
+    return hashlib.sha256(bytes(image) + np.ascontiguousarray(d).tobytes() + np.int32(lu).tobytes()).hexdigest()
+
+
 def test_restated_accumulation_equals_reference_dbow2(oracle):
     """The oracle's restated BowVector / FeatureVector accumulation against the REFERENCE'S OWN BowVector.cpp +
-    FeatureVector.cpp (oracle/_ref/libdbow2_vec.so, built from /root/reference by oracle/Makefile): every weighting /
-    scoring combination, doubles bit for bit.  Skipped only where the reference-built object is absent."""
-    if not oracle.have_dbow2_ref():
-        pytest.skip('oracle/_ref/libdbow2_vec.so not built (no /root/reference on this box)')
+    FeatureVector.cpp (oracle/_ref/libdbow2_vec.so, built from the reference's sources by oracle/Makefile where they are present):
+    every weighting / scoring combination, doubles bit for bit.  Where the reference-built object is absent, against what it
+    returned for the same inputs (tests/golden/dbow2_ref_outputs.npz <- tools/gen_dbow2_ref_golden.py)."""
+    live = oracle.have_dbow2_ref()
+    rec = None if live else np.load(DBOW2_REF_OUTPUTS)
     try:
-        for scoring in range(6):
-            for weighting in range(4):
-                for image, lu in [(synth_vocabulary(3, 10, 3, stop_fraction=0.1), 1), (ragged_vocabulary(4), 2)]:
-                    image = with_header(image, scoring, weighting)
-                    v = oracle.vocabulary(image)
-                    d = _descs(scoring * 10 + weighting + 100, image, 400)
-                    assert not oracle.use_dbow2_ref(False) and not oracle.bow_accumulator_is_reference()
-                    a = v.transform(d, lu)
-                    assert oracle.use_dbow2_ref(True) and oracle.bow_accumulator_is_reference()
-                    b = v.transform(d, lu)
-                    assert a[0].tolist() == b[0].tolist()
-                    assert a[1].tobytes() == b[1].tobytes()
-                    assert all(x.tolist() == y.tolist() for x, y in zip(a[2], b[2]))
+        for name, image, d, lu in accumulation_cases():
+            v = oracle.vocabulary(image)
+            assert not oracle.use_dbow2_ref(False) and not oracle.bow_accumulator_is_reference()
+            a = v.transform(d, lu)
+            if live:
+                assert oracle.use_dbow2_ref(True) and oracle.bow_accumulator_is_reference()
+                b = v.transform(d, lu)
+            else:
+                assert str(rec[name + '_in']) == case_digest(image, d, lu), name
+                b = (rec[name + '_ids'], rec[name + '_vals'], (rec[name + '_fvn'], rec[name + '_fvo'], rec[name + '_fvf']))
+            assert a[0].tolist() == b[0].tolist()
+            assert a[1].tobytes() == b[1].tobytes()
+            assert all(x.tolist() == y.tolist() for x, y in zip(a[2], b[2]))
     finally:
         oracle.use_dbow2_ref(False)
 

@@ -221,7 +221,7 @@ def _bench(args, extra_env=None):
 
 
 def test_bench_line_is_self_verified(api):
-    res = _bench(['--steps', '2', '--warmup', '1', '--cpu-frames', '0'])
+    res = _bench(['--full', '--steps', '2', '--warmup', '1', '--cpu-frames', '0'])
     assert res['n_gpus'] == 1 and res['verified'] is True and len(res['outputs_sha256']) == 64
     v = res['verify']
     assert v['frames_checked'] >= 510 and v['distinct_period_positions'] == 510 and v['verified_before_timing'] is True
@@ -232,10 +232,38 @@ def test_bench_line_is_self_verified(api):
     assert res['roofline']['frac'] > 0 and res['roofline']['launch_ms'] > 0
 
 
+def test_bench_plain_run_dumps_the_last_steps_outputs(api, tmp_path):
+    """A plain run (no --full) times the headline stream only, and --dump-outputs writes a seeded sample of the last timed step's
+    frames: every dumped frame, rebuilt from the float arrays, has the oracle's digests of its stream position."""
+    res = _bench(['--steps', '2', '--warmup', '1', '--prewarm-seconds', '0', '--dump-outputs', str(tmp_path)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert res[k] is not None, k
+    assert res['steps'] == 2 and res['value'] > 1000 and res['ms_per_step'] > 0
+    assert res['verified'] is None and res['pcie_inclusive'] is None and res['roofline'] is None and 'cpu_baseline' not in res
+    d = {n: np.load(tmp_path / (n + '.npy')) for n in res['dumped_outputs']}
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20 and all(a.dtype in (np.float32, np.float64) for a in d.values())
+    pos = d['frames'].astype(np.int64)
+    assert len(pos) == 64 and (pos >= 2 * 2048).all() and (pos < 3 * 2048).all()    # warm-up step 0, timed steps 1 and 2: the last one
+    table = DIGESTS['streams'][str(wl.stream_seed(0))]
+    fields = ('x', 'y', 'size', 'angle', 'response', 'octave', 'class_id')
+    kp_at = m_at = 0
+    for i, p in enumerate(pos.tolist()):
+        n, npv = int(d['num_keypoints'][i]), int(d['num_prev_keypoints'][i])
+        k = np.zeros(n, api.KP_DTYPE)
+        for j, f in enumerate(fields):
+            k[f] = d['keypoints'][kp_at:kp_at + n, j].astype(k[f].dtype)
+        desc = d['descriptors'][kp_at:kp_at + n].astype(np.uint8)
+        ef, em, _ = wl.expected_digests(table, p)
+        assert wl.frame_digest(k, desc, n) == ef, p
+        assert wl.match_digest(int(d['num_matches'][i]), d['matches12'][m_at:m_at + npv].astype(np.int32), npv) == em, p
+        kp_at, m_at = kp_at + n, m_at + npv
+    assert kp_at == len(d['keypoints']) and m_at == len(d['matches12'])
+
+
 def test_bench_two_ranks_on_one_gpu(api):
     """bench.py --gpus 2 launches its two ranks itself; ORBFE_BENCH_DEVICE=0 puts both on the one GPU of this box.
     Each rank runs its own stream (seeds 100, 101) through the product and checks it against that seed's digests."""
-    res = _bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--no-pcie'], {'ORBFE_BENCH_DEVICE': '0'})
+    res = _bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-pcie'], {'ORBFE_BENCH_DEVICE': '0'})
     assert res['n_gpus'] == 2
     assert res['verified'] is True and res['verify']['ranks_verified'] == 2 and res['verify']['timed_ranks_verified'] == 2
     assert res['value'] > 1000 and res['config']['parallelism'].startswith('independent streams')
@@ -246,7 +274,7 @@ def test_bench_eight_ranks_on_one_gpu(api):
     initialised process), ORBFE_BENCH_DEVICE=0 puts all of them on the one GPU of this box.  Every rank runs its own camera
     stream (seeds 100..107) through the product and checks it against that seed's committed digests
     (tests/golden/stream1080_digests.json); the line reports the host cores all ranks used together."""
-    res = _bench(['--gpus', '8', '--steps', '1', '--warmup', '1', '--no-pcie', '--no-latency', '--cpu-frames', '0', '--prewarm-seconds', '0'],
+    res = _bench(['--full', '--gpus', '8', '--steps', '1', '--warmup', '1', '--no-pcie', '--no-latency', '--cpu-frames', '0', '--prewarm-seconds', '0'],
                  {'ORBFE_BENCH_DEVICE': '0'})
     assert res['n_gpus'] == 8
     assert res['verified'] is True and res['verify']['ranks_verified'] == 8 and res['verify']['timed_ranks_verified'] == 8
@@ -324,7 +352,7 @@ def test_bench_single_stream_mode_on_one_gpu(api):
     """`bench.py --single-stream --gpus 4` with the four device runners on the one GPU of the test box: the same JSON contract, the
     whole period verified before timing and the sampled batches of the timed region (mid-stream batches: their first frame's predecessor
     came over the host) verified after it."""
-    line = _bench(['--single-stream', '--gpus', '4', '--steps', '3', '--warmup', '1', '--prewarm-seconds', '0.2', '--depth', '2'],
+    line = _bench(['--full', '--single-stream', '--gpus', '4', '--steps', '3', '--warmup', '1', '--prewarm-seconds', '0.2', '--depth', '2'],
                   {'ORBFE_BENCH_DEVICE': '0'})
     assert line['n_gpus'] == 4 and line['scaling'] == 'strong' and line['unit'] == 'frames/s' and line['value'] > 1000
     assert line['verified'] is True and line['verify']['distinct_period_positions'] == wl.PERIOD
@@ -337,7 +365,7 @@ def test_runner_adapts_to_the_default_four_hardware_queues(api):
     queues (GPU_MAX_HW_QUEUES=4 here, because bench.py exports 8 unless the caller said otherwise) a runner asked for four batches in
     flight measures that only three of its streams run side by side, keeps three in flight, and delivers at least 0.95 of the rate of
     the same runner in a process with eight queues -- every digest green in both."""
-    args = ['--steps', '20', '--warmup', '3', '--no-pcie', '--no-latency', '--cpu-frames', '0']
+    args = ['--full', '--steps', '20', '--warmup', '3', '--no-pcie', '--no-latency', '--cpu-frames', '0']
     ratios = []
     for attempt in range(2):       # (two half-second measurements on a shared box: a second look before a step-time burst fails the suite)
         four = _bench(args, {'GPU_MAX_HW_QUEUES': '4', 'ORBFE_QUIET': '1'})

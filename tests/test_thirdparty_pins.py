@@ -4,7 +4,11 @@ Anaconda python3.9 with scikit-image and an older scipy: implementations of the 
 somebody else.  They are not OpenCV, so they pin the ALGORITHM (the FAST-9 segment test, the score as the largest passing
 threshold, an integer 7x7 convolution with reflect-101 borders), not OpenCV's choice of variant.
 
-The other interpreter runs as a child process on .npy files; skipped where it (or scikit-image) is absent."""
+The other interpreter ran the jobs below as a child process on .npy files.  What it returned is recorded in
+tests/golden/thirdparty_outputs.npz, keyed by a digest of the job script and of its input arrays: the tests replay it and need no
+second interpreter, and a check whose inputs are not the recorded ones fails.  `python tools/gen_thirdparty_golden.py --record`
+reruns the jobs under that interpreter (on a machine with a GPU for the -m gpu check) and rewrites the file."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -14,22 +18,45 @@ import numpy as np
 import pytest
 
 PY39 = '/opt/conda/bin/python3.9'
+RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'thirdparty_outputs.npz')
+RECORD_TO = os.environ.get('ORBFE_THIRDPARTY_RECORD')     # (tools/gen_thirdparty_golden.py --record): run the jobs live, keep outputs here
+
+
+def _job_key(script, arrays):
+    h = hashlib.sha256(textwrap.dedent(script).encode())
+    for k in sorted(arrays):
+        a = np.ascontiguousarray(arrays[k])
+        h.update(('%s %s %s\n' % (k, a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()[:24]
 
 
 def _run39(script, tmp_path, **arrays):
-    if not os.path.exists(PY39):
-        pytest.skip('no %s in this image' % PY39)
+    """The job's output files in tmp_path: replayed from RECORDED, or (recording) computed by PY39 and copied to RECORD_TO/<key>/."""
+    key = _job_key(script, arrays)
+    if not RECORD_TO:
+        g = np.load(RECORDED)
+        names = [k for k in g.files if k.startswith(key + '__')]
+        assert names, 'the inputs of this check are not the recorded ones (tools/gen_thirdparty_golden.py --record)'
+        for k in names:
+            if k != key + '__stdout':
+                np.save(tmp_path / (k[len(key) + 2:] + '.npy'), g[k])
+        print(str(g[key + '__stdout']), '(recorded)')
+        return tmp_path
     for k, a in arrays.items():
         np.save(tmp_path / (k + '.npy'), a)
     src = tmp_path / 'job.py'
     src.write_text(textwrap.dedent(script))
     env = {k: v for k, v in os.environ.items() if not k.startswith('PYTHON')}
     r = subprocess.run([PY39, '-W', 'ignore', str(src)], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
-    if r.returncode != 0:
-        if 'ModuleNotFoundError' in r.stderr or 'ImportError' in r.stderr:
-            pytest.skip('third-party module missing: ' + r.stderr.strip().splitlines()[-1])
-        raise AssertionError(r.stderr[-2000:])
+    assert r.returncode == 0, r.stderr[-2000:]
     print(r.stdout.strip())
+    dst = os.path.join(RECORD_TO, key)
+    os.makedirs(dst, exist_ok=True)
+    for f in os.listdir(tmp_path):
+        if f.endswith('.npy') and f[:-4] not in arrays:
+            np.save(os.path.join(dst, f), np.load(tmp_path / f))
+    np.save(os.path.join(dst, 'stdout.npy'), np.array(r.stdout.strip()))
     return tmp_path
 
 
@@ -136,10 +163,14 @@ def test_brief_pattern_against_scikit_image():
     the ORB authors with its own ORB (`skimage/feature/orb_descriptor_positions.txt`); ours, as compiled into the oracle and
     into the product, must equal it entry for entry."""
     import glob, re
-    found = glob.glob('/opt/conda/lib/python3*/site-packages/skimage/feature/orb_descriptor_positions.txt')
-    if not found:
-        pytest.skip('no scikit-image data files in this image')
-    want = np.loadtxt(found[0]).astype(np.int8)
+    if RECORD_TO:
+        found = glob.glob(os.path.join(os.path.dirname(os.path.dirname(PY39)), 'lib', 'python3*', 'site-packages', 'skimage', 'feature',
+                                       'orb_descriptor_positions.txt'))
+        assert found, 'no scikit-image data files in this image'
+        want = np.loadtxt(found[0]).astype(np.int8)
+        np.save(os.path.join(RECORD_TO, 'orb_descriptor_positions.npy'), want)
+    else:
+        want = np.load(RECORDED)['orb_descriptor_positions']
     assert want.shape == (256, 4)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for f in ('oracle/brief_pattern.inc', 'os1_amd/csrc/brief_pattern.inc'):

@@ -8,7 +8,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/prof_$tag
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python3 $root/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python3 $root/bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --steps 4 --warmup 1 --passes 2 --cpu-frames 0 --no-pcie --no-latency --prewarm-seconds 0 > $out/stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_$c -- python3 $root/bench.py --steps 2 --warmup 1 --passes 1 --cpu-frames 0 --no-pcie --no-verify --no-latency --prewarm-seconds 0 > $out/pmc_$c.log 2>&1

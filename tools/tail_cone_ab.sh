@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 export ORBFE_LIB=$PWD/os1_amd/liborbfe_exp.so
 run() {
-  env "$@" python bench.py --steps 20 --warmup 3 --no-pcie --no-latency --cpu-frames 0 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 20 --warmup 3 --no-pcie --no-latency --cpu-frames 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-52s value %.0f  p50 %s  verified %s' % ('$*', d['value'], d.get('value_p50'), d['verified']))"
