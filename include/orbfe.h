@@ -196,6 +196,10 @@ void orbfe_sfi_chain_destroy(orbfe_sfi_chain* c);
  * its count 0) and its last frame is not handed on.  For callers that deal the batches of ONE stream to several devices and match the
  * boundary pairs themselves (orbfe_stream_multi_*). */
 int orbfe_sfi_chain_set_isolated(orbfe_sfi_chain* c, int isolated);
+/* The next batch submitted with this chain has no predecessor in the chain (its first frame reports no match); its last frame is handed
+ * on as usual.  For callers whose stream went on without the chain (a batch extracted unmatched, another geometry or route): they
+ * match that first frame themselves. */
+int orbfe_sfi_chain_restart(orbfe_sfi_chain* c);
 int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chain, int nframes, const uint8_t* const* gray,
                                        int in_device_memory, int rows, int cols, size_t stride_bytes, const float bounds[4],
                                        int window_size, float nnratio, int check_orientation);
@@ -256,6 +260,14 @@ int orbfe_debug_sincos_host_check(uint32_t lo_bits, uint32_t hi_bits, uint32_t s
  * orbfe_search_for_initialization frame by frame.
  * ------------------------------------------------------------------------------------------- */
 typedef struct orbfe_stream orbfe_stream;
+/* PREDECESSOR CONTRACT (orbfe_stream_* and orbfe_stream_multi_*).  Frame 0 of a batch is matched against the last frame pushed before
+ * it, whatever that frame's size, whichever route (GPU or host quadtree) either batch took, and whether or not matching was on for that
+ * batch.  Three exceptions, where frame 0 reports nmatches 0 and a matches12 row of -1 only: (a) the runner's first batch; (b) every
+ * batch pushed while isolated batches are on; (c) the first batch after isolated batches are switched off.  Within a batch, frame i is
+ * matched against frame i - 1.  A batch pushed while matching is off reports nmatches 0 and matches12 -1 for every frame.
+ * A held result (orbfe_stream_pop_hold) stays valid and unchanged until it is released; while any ticket is held, orbfe_stream_pop,
+ * the _set_* calls, orbfe_stream_set_queue_slots and a push that would grow orbfe_stream_capacity return ORBFE_ERR_INVALID, and so
+ * does a release of a ticket that is not held. */
 /* batch = frames per push; depth = extraction batches in flight (1..8).
  * HARDWARE QUEUES: each batch in flight has its own HIP stream and the HIP runtime folds a process's streams onto GPU_MAX_HW_QUEUES
  * hardware queues (4 unless the ENVIRONMENT variable said otherwise before the process's first HIP call: the runtime reads it once,
@@ -278,7 +290,7 @@ int orbfe_stream_set_isolated_batches(orbfe_stream* s, int isolated);
 int orbfe_stream_batches_in_flight(const orbfe_stream* s);
 /* orbfe_stream_pop without the "valid until the next pop" rule: the result stays valid until orbfe_stream_release(s, *ticket).  Any
  * number of results may be held; each keeps one of the runner's result slots (orbfe_stream_queue_slots) busy, and a push waits while no
- * slot is free.  Do not mix with orbfe_stream_pop on the same runner. */
+ * slot is free.  Do not mix with orbfe_stream_pop on the same runner (orbfe_stream_pop is refused while a result is held). */
 int orbfe_stream_pop_hold(orbfe_stream* s, const OrbfeKeyPoint** kps, const uint8_t** desc, const int** n_kps, const int32_t** matches12,
                           const int** nmatches, int* ticket);
 int orbfe_stream_release(orbfe_stream* s, int ticket);
@@ -293,7 +305,7 @@ int orbfe_stream_set_vocabulary(orbfe_stream* s, orbfe_vocabulary* v, int levels
 int orbfe_stream_bow_raw(orbfe_stream* s, int frame, const uint32_t** leaf_node, const uint32_t** level_node, int* n);
 /* Per-frame output capacity (keypoints) of the arrays returned by orbfe_stream_pop = their row stride.  It grows when a
  * push brings frames of a geometry that can return more keypoints (orbfe_extractor_max_keypoints_for_size); such a push
- * is only accepted while no batch is in flight. */
+ * is only accepted while no batch is in flight or held. */
 int orbfe_stream_capacity(const orbfe_stream* s);
 /* Result slots of the runner = batches that can be pushed ahead of the pops before orbfe_stream_push blocks, plus 2
  * (one is in the caller's hands after a pop, one is being filled).  Default depth+4; a caller whose own thread may be
@@ -669,6 +681,9 @@ int orbfe_debug_features_in_area(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, 
  * is matched by the host-array search on the batch's own device.  Results are identical to one orbfe_stream fed the same frames.
  * A device may appear several times in device_ids (more batches in flight on it).  With in_device_memory != 0 the frames of a
  * push must live on the device that push goes to: orbfe_stream_multi_device_of_next_push.
+ * The predecessor contract above orbfe_stream_create holds (there are no isolated batches here).  The runner has one row stride for
+ * every batch, orbfe_stream_multi_capacity, the same for every device's runner: a push of frames that need more keypoint slots is only
+ * accepted while nothing is in flight (it lets go of the batch the caller holds, as _set_* do) and grows every device's runner at once.
  * Everything else as orbfe_stream_*: pointers returned by _pop stay valid until the next _pop; _set_* only while nothing is in flight;
  * push from one thread, pop from one thread; never push more than `depth` + 2 batches PER DEVICE ahead of the pops (a device's runner
  * has depth + 4 result slots and finished batches wait in them for their turn).

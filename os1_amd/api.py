@@ -158,6 +158,8 @@ def load_library():
     L.orbfe_stream_queue_slots.argtypes = [vp]
     L.orbfe_stream_push.argtypes = [vp, vp, ci, ci, ci, C.c_size_t]
     L.orbfe_stream_pop.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.orbfe_stream_pop_hold.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ci)]
+    L.orbfe_stream_release.argtypes = [vp, ci]
     L.orbfe_stream_set_isolated_batches.argtypes = [vp, ci]
     L.orbfe_stream_batches_in_flight.argtypes = [vp]
     L.orbfe_stream_multi_create.argtypes = [ci, cf, ci, ci, ci, C.POINTER(ci), ci, ci, ci, C.POINTER(vp)]
@@ -1016,6 +1018,18 @@ def h2d_rate_gbs(device, host_ptr, nbytes, reps=8):
     return g.value
 
 
+def _result_views(B, cap, ptrs, copy):
+    """(kps[B,cap], desc[B,cap,32], n[B], matches12[B,cap], nmatches[B]) over a runner's result pointers."""
+    def view(ptr, dtype, shape):
+        n = int(np.prod(shape))
+        buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr.value)
+        a = np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
+        return a.copy() if copy else a
+    pk, pd, pn, pm, pnm = ptrs
+    return (view(pk, KP_DTYPE, (B, cap)), view(pd, np.uint8, (B, cap, 32)), view(pn, np.int32, (B,)),
+            view(pm, np.int32, (B, cap)), view(pnm, np.int32, (B,)))
+
+
 class Stream:
     """Native stream runner (orbfe_stream_*): push batches of frames, pop (keypoints, descriptors, matches
     against the predecessor frame) in order.  Orchestration (async extraction, matching thread) is C++."""
@@ -1077,15 +1091,18 @@ class Stream:
         """-> (kps[B,cap], desc[B,cap,32], n[B], matches12[B,cap], nmatches[B]) as views valid until the next pop."""
         pk, pd, pn, pm, pnm = (C.c_void_p() for _ in range(5))
         _check(self.L.orbfe_stream_pop(self.h, C.byref(pk), C.byref(pd), C.byref(pn), C.byref(pm), C.byref(pnm)))
-        B, cap = self.batch, self.cap
+        return _result_views(self.batch, self.cap, (pk, pd, pn, pm, pnm), copy)
 
-        def view(ptr, dtype, shape):
-            n = int(np.prod(shape))
-            buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr.value)
-            a = np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
-            return a.copy() if copy else a
-        return (view(pk, KP_DTYPE, (B, cap)), view(pd, np.uint8, (B, cap, 32)), view(pn, np.int32, (B,)),
-                view(pm, np.int32, (B, cap)), view(pnm, np.int32, (B,)))
+    def pop_hold(self, copy=False):
+        """-> (ticket, (kps, desc, n, matches12, nmatches)): pop() whose views stay valid until release(ticket) (orbfe_stream_pop_hold)."""
+        pk, pd, pn, pm, pnm = (C.c_void_p() for _ in range(5))
+        t = C.c_int(-1)
+        _check(self.L.orbfe_stream_pop_hold(self.h, C.byref(pk), C.byref(pd), C.byref(pn), C.byref(pm), C.byref(pnm), C.byref(t)))
+        return t.value, _result_views(self.batch, self.cap, (pk, pd, pn, pm, pnm), copy)
+
+    def release(self, ticket):
+        """Give a held result's slot back to the runner (orbfe_stream_release)."""
+        _check(self.L.orbfe_stream_release(self.h, int(ticket)))
 
     def batches_in_flight(self):
         """Batches the runner keeps on the GPU at a time: `depth`, or fewer when the process has fewer hardware queues than that."""
@@ -1153,12 +1170,4 @@ class MultiStream:
         """-> (kps[B,cap], desc[B,cap,32], n[B], matches12[B,cap], nmatches[B]) as views valid until the next pop."""
         pk, pd, pn, pm, pnm = (C.c_void_p() for _ in range(5))
         _check(self.L.orbfe_stream_multi_pop(self.h, C.byref(pk), C.byref(pd), C.byref(pn), C.byref(pm), C.byref(pnm)))
-        B, cap = self.batch, self.cap
-
-        def view(ptr, dtype, shape):
-            n = int(np.prod(shape))
-            buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr.value)
-            a = np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
-            return a.copy() if copy else a
-        return (view(pk, KP_DTYPE, (B, cap)), view(pd, np.uint8, (B, cap, 32)), view(pn, np.int32, (B,)),
-                view(pm, np.int32, (B, cap)), view(pnm, np.int32, (B,)))
+        return _result_views(self.batch, self.cap, (pk, pd, pn, pm, pnm), copy)

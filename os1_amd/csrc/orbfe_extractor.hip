@@ -131,6 +131,7 @@ struct orbfe_sfi_chain {
   hipEvent_t ready[2] = {};
   long long seq = 0;           // batches submitted so far
   bool isolated = false;       // orbfe_sfi_chain_set_isolated: no batch has a predecessor (frame 0 of every batch reports no match)
+  bool restart = false;        // orbfe_sfi_chain_restart: the next batch's frame 0 has no predecessor in the chain
   // host-quadtree route (geometries outside the GPU quadtree's limits): the predecessor frame lives on the host and the
   // searches go through an ordinary matcher handle
   orbfe_matcher* hostMatcher = nullptr;
@@ -872,7 +873,9 @@ struct orbfe_extractor {
       const int prev = (int)((ch.seq + 1) & 1), cur = (int)(ch.seq & 1);   // buffer written by the previous / this batch
       SP.carrySel = ch.sel[prev].p; SP.carryAngle = ch.angle[prev].p; SP.carryDesc = ch.desc[prev].p;
       const bool iso = ch.isolated;   // every batch stands alone: no carry in, no carry out
-      SP.carryCount = ch.count.p + ((ch.seq == 0 || iso) ? 2 : prev);
+      // (after a restart the carry is not read, but the batch still waits for the one before: it overwrites the buffer that one reads)
+      SP.carryCount = ch.count.p + ((ch.seq == 0 || iso || ch.restart) ? 2 : prev);
+      ch.restart = false;
       SP.minX = ms->bounds[0]; SP.minY = ms->bounds[2];
       SP.invW = static_cast<float>(64) / static_cast<float>(ms->bounds[1] - ms->bounds[0]);   // Frame.cc:98
       SP.invH = static_cast<float>(48) / static_cast<float>(ms->bounds[3] - ms->bounds[2]);   // Frame.cc:99
@@ -1775,8 +1778,17 @@ void orbfe_sfi_chain_destroy(orbfe_sfi_chain* c) { delete c; }
 
 int orbfe_sfi_chain_set_isolated(orbfe_sfi_chain* c, int isolated) {
   if (!c) { set_err("chain is NULL"); return ORBFE_ERR_INVALID; }
+  if (c->isolated != (isolated != 0)) {   // either way the carry is stale: start over (no batch of the chain is in flight)
+    c->seq = 0;
+    c->hostPrevValid = false;
+  }
   c->isolated = isolated != 0;
-  if (c->isolated) c->hostPrevValid = false;
+  return ORBFE_OK;
+}
+
+int orbfe_sfi_chain_restart(orbfe_sfi_chain* c) {
+  if (!c) { set_err("chain is NULL"); return ORBFE_ERR_INVALID; }
+  c->restart = true;
   return ORBFE_OK;
 }
 
@@ -1808,7 +1820,7 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
       const uint8_t* pd;
       int pn;
       if (f == 0) {
-        if (!chain->hostPrevValid || chain->isolated) continue;   // very first frame of the stream (or isolated batches): no predecessor
+        if (!chain->hostPrevValid || chain->isolated || chain->restart) continue;   // very first frame of the stream (or isolated batches): no predecessor
         pk = chain->hostPrevKps.data(); pd = chain->hostPrevDesc.data(); pn = (int)chain->hostPrevKps.size();
       } else {
         pk = h->defKps.data() + (size_t)(f - 1) * cap; pd = h->defDesc.data() + (size_t)(f - 1) * cap * 32; pn = h->defN[f - 1];
@@ -1833,6 +1845,7 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
     chain->hostPrevKps.assign(h->defKps.begin() + (size_t)last * cap, h->defKps.begin() + (size_t)last * cap + ln);
     chain->hostPrevDesc.assign(h->defDesc.begin() + (size_t)last * cap * 32, h->defDesc.begin() + ((size_t)last * cap + ln) * 32);
     chain->hostPrevValid = !chain->isolated;
+    chain->restart = false;
     h->deferredMatched = true;
     return ORBFE_OK;
   }

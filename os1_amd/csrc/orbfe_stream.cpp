@@ -53,6 +53,8 @@ struct Slot {
   int prevN = -1;
   long long seq = 0;
   bool done = false;
+  bool held = false;        // handed out by orbfe_stream_pop_hold and not released yet
+  bool frame0OnHost = false;   // GPU matching path: the chain does not hold frame 0's predecessor, the runner matches it on the host
   int status = ORBFE_OK;
   std::string err;
   // match parameters of the stream at push time (orbfe_stream_set_matching only works on an idle stream, but the
@@ -72,6 +74,8 @@ struct orbfe_stream {
   std::vector<orbfe_extractor*> ext;
   std::vector<orbfe_matcher*> matchers;   // one per match worker (host-side matching path)
   orbfe_sfi_chain* chain = nullptr;       // GPU-resident matching path (default)
+  orbfe_matcher* frame0Matcher = nullptr; // GPU path: frame 0 of a batch whose predecessor the chain does not hold (created when first needed)
+  int chainRows = 0, chainCols = 0;       // geometry of the previous batch if the chain matched it (its last frame is the chain's carry), else 0
   bool gpuMatch = true;
   bool isolated = false;                  // orbfe_stream_set_isolated_batches: frame 0 of a batch has no predecessor
   std::vector<Slot> slots;
@@ -96,6 +100,25 @@ struct orbfe_stream {
   std::condition_variable cv;
   std::deque<int> freeQ, extractQ, matchQ, doneQ;
   int popped = -1;  // slot handed to the caller by the last pop (returned to freeQ on the next pop)
+  int nHeld = 0;     // slots handed out by orbfe_stream_pop_hold and not released
+  bool idle() const { return pushSeq == popSeq && nHeld == 0; }   // (caller holds mu)
+  // keypoint slots per frame: grow every slot to `need` -- only while idle, the row stride changes (caller holds mu)
+  int growCap(int need, int rows, int cols) {
+    if (need <= cap) return ORBFE_OK;
+    if (!idle()) {
+      set_err("frames of %dx%d need %d keypoint slots per frame, the runner holds %d: pop every pushed batch and release every held one "
+              "before changing the frame size", cols, rows, need, cap);
+      return ORBFE_ERR_INVALID;
+    }
+    cap = need;
+    for (Slot& sl : slots) {
+      sl.kps.resize((size_t)batch * need);
+      sl.desc.resize((size_t)batch * need * 32);
+      sl.m12.assign((size_t)batch * need, -1);
+      sl.prevxy.resize((size_t)batch * need * 2);
+    }
+    return ORBFE_OK;
+  }
   bool stop = false;
   std::thread tExtract;
   std::vector<std::thread> tMatch;
@@ -113,6 +136,21 @@ struct orbfe_stream {
   long long nBatches = 0;
   static double nowMs() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  }
+
+  // GPU matching path, frame 0 of a batch whose predecessor (the last frame of the batch before, s.prevKps) the chain does not hold:
+  // the host-array search (the same kernels), row 0 overwritten
+  int matchFrame0(Slot& s) {
+    if (!frame0Matcher) {
+      const int rc = orbfe_matcher_create(device, &frame0Matcher);
+      if (rc != ORBFE_OK) return rc;
+    }
+    float* pxy = s.prevxy.data();   // (row 0: prevN <= cap)
+    for (int j = 0; j < s.prevN; j++) { pxy[2 * j] = s.prevKps[j].x; pxy[2 * j + 1] = s.prevKps[j].y; }
+    int32_t* row = s.m12.data();
+    std::fill(row, row + cap, -1);
+    return orbfe_search_for_initialization(frame0Matcher, s.prevKps.data(), s.prevDesc.data(), s.prevN, s.kps.data(), s.desc.data(), s.n[0],
+                                           s.bounds, pxy, row, s.window, s.nnratio, s.checkOri, &s.nm[0]);
   }
 
   void extractLoop() {
@@ -136,11 +174,19 @@ struct orbfe_stream {
         Slot& s = slots[job];
         orbfe_extractor* h = ext[nextExt];
         const double ta = nowMs();
-        if (gpuMatch && s.window > 0)
+        if (gpuMatch && s.window > 0) {
+          // the chain's carry is frame 0's predecessor only if the chain matched the batch before, on the same geometry (so the same
+          // route: the GPU and the host quadtree route keep a carry each); otherwise frame 0 is matched on the host at collect time
+          s.frame0OnHost = s.rows != chainRows || s.cols != chainCols;
+          if (s.frame0OnHost) (void)orbfe_sfi_chain_restart(chain);
           s.status = orbfe_extract_batch_submit_matched(h, chain, batch, s.frames.data(), s.onDevice, s.rows, s.cols, s.stride,
                                                         s.bounds, s.window, s.nnratio, s.checkOri);
-        else
+          chainRows = s.status == ORBFE_OK ? s.rows : 0;
+          chainCols = s.status == ORBFE_OK ? s.cols : 0;
+        } else {
           s.status = orbfe_extract_batch_submit(h, batch, s.frames.data(), s.onDevice, s.rows, s.cols, s.stride);
+          chainRows = chainCols = 0;
+        }
         {
           std::lock_guard<std::mutex> lk(mu);
           busySubmit += nowMs() - ta;
@@ -178,6 +224,13 @@ struct orbfe_stream {
       if (s.status == ORBFE_OK) {
         s.prevN = isolated ? -1 : lastN;
         if (s.prevN >= 0) { s.prevKps = lastKps; s.prevDesc = lastDesc; }
+        if (s.window <= 0) {   // extraction only: no matches
+          std::fill(s.nm.begin(), s.nm.end(), 0);
+          std::fill(s.m12.begin(), s.m12.end(), -1);
+        } else if (gpuMatch && s.frame0OnHost && s.prevN >= 0) {
+          s.status = matchFrame0(s);
+          if (s.status != ORBFE_OK) s.err = orbfe_last_error();
+        }
         lastN = s.n[batch - 1];
         lastKps.assign(s.kps.begin() + (size_t)(batch - 1) * cap, s.kps.begin() + (size_t)(batch - 1) * cap + lastN);
         lastDesc.assign(s.desc.begin() + (size_t)(batch - 1) * cap * 32, s.desc.begin() + ((size_t)(batch - 1) * cap + lastN) * 32);
@@ -238,6 +291,7 @@ struct orbfe_stream {
           } else {
             pk = s.kps.data() + (size_t)(i - 1) * cap; pd = s.desc.data() + (size_t)(i - 1) * cap * 32; pn = s.n[i - 1];
           }
+          std::fill(s.m12.begin() + (size_t)i * cap + pn, s.m12.begin() + (size_t)(i + 1) * cap, -1);   // (the search writes the first pn)
           float* pxy = s.prevxy.data() + (size_t)i * cap * 2;
           for (int j = 0; j < pn; j++) { pxy[2 * j] = pk[j].x; pxy[2 * j + 1] = pk[j].y; }
           k1.push_back(pk); d1.push_back(pd); n1.push_back(pn);
@@ -368,6 +422,7 @@ void orbfe_stream_destroy(orbfe_stream* s) {
   for (auto& t : s->tMatch) if (t.joinable()) t.join();
   for (auto* e : s->ext) orbfe_extractor_destroy(e);
   for (auto* q : s->matchers) orbfe_matcher_destroy(q);
+  if (s->frame0Matcher) orbfe_matcher_destroy(s->frame0Matcher);
   orbfe_sfi_chain_destroy(s->chain);
   delete s;
 }
@@ -376,7 +431,7 @@ int orbfe_stream_set_matching(orbfe_stream* s, const float bounds[4], int window
                               int check_orientation) {
   if (!s || (window_size > 0 && !bounds)) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
   if (bounds) memcpy(s->bounds, bounds, sizeof s->bounds);
   s->window = window_size;
   s->nnratio = nnratio;
@@ -387,16 +442,17 @@ int orbfe_stream_set_matching(orbfe_stream* s, const float bounds[4], int window
 int orbfe_stream_set_isolated_batches(orbfe_stream* s, int isolated) {
   if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
   s->isolated = isolated != 0;
   s->lastN = -1;
+  s->chainRows = s->chainCols = 0;
   return orbfe_sfi_chain_set_isolated(s->chain, isolated);
 }
 
 int orbfe_stream_set_input_format(orbfe_stream* s, int format, int gray_variant) {
   if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
   for (orbfe_extractor* e : s->ext) {
     const int rc = orbfe_extractor_set_input_format(e, format, gray_variant);
     if (rc) return rc;
@@ -408,7 +464,7 @@ int orbfe_stream_set_input_format(orbfe_stream* s, int format, int gray_variant)
 int orbfe_stream_set_blur_variant(orbfe_stream* s, int variant) {
   if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
   for (orbfe_extractor* e : s->ext) {
     const int rc = orbfe_extractor_set_blur_variant(e, variant);
     if (rc) return rc;
@@ -419,7 +475,7 @@ int orbfe_stream_set_blur_variant(orbfe_stream* s, int variant) {
 int orbfe_stream_set_vocabulary(orbfe_stream* s, orbfe_vocabulary* v, int levelsup) {
   if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
   for (orbfe_extractor* e : s->ext) {
     const int rc = orbfe_extractor_set_vocabulary(e, v, levelsup);
     if (rc) return rc;
@@ -442,12 +498,22 @@ int orbfe_stream_bow_raw(orbfe_stream* s, int frame, const uint32_t** leaf_node,
 }
 
 int orbfe_stream_capacity(const orbfe_stream* s) { return s ? s->cap : 0; }
+
+// (orbfe_stream_multi.cpp, not in the header) keypoint slots per frame that frames of rows x cols need, and growing to them while idle
+int orbfe_stream_capacity_for(const orbfe_stream* s, int rows, int cols) {
+  return s ? std::max(s->cap, orbfe_extractor_max_keypoints_for_size(s->ext[0], rows, cols)) : 0;
+}
+int orbfe_stream_grow_capacity(orbfe_stream* s, int need) {
+  if (!s) { set_err("stream is NULL"); return ORBFE_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(s->mu);
+  return s->growCap(need, 0, 0);
+}
 int orbfe_stream_batches_in_flight(const orbfe_stream* s) { return s ? s->inFlight : 0; }
 
 int orbfe_stream_set_queue_slots(orbfe_stream* s, int nslots) {
   if (!s) { set_err("stream is NULL"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  if (s->popSeq != s->pushSeq) { set_err("orbfe_stream_set_queue_slots: batches in flight"); return ORBFE_ERR_INVALID; }
+  if (!s->idle()) { set_err("orbfe_stream_set_queue_slots: batches in flight or held"); return ORBFE_ERR_INVALID; }
   if (nslots < s->depth + 2 || nslots > 256) { set_err("orbfe_stream_set_queue_slots: need depth+2 <= nslots <= 256"); return ORBFE_ERR_INVALID; }
   s->growSlots(nslots);
   return ORBFE_OK;
@@ -462,17 +528,8 @@ int orbfe_stream_push(orbfe_stream* s, const uint8_t* const* gray, int in_device
   const int need = orbfe_extractor_max_keypoints_for_size(s->ext[0], rows, cols);
   if (need > s->cap) {
     std::lock_guard<std::mutex> lk(s->mu);
-    if (s->popSeq != s->pushSeq) {
-      set_err("frames of %dx%d need %d keypoint slots per frame, the runner holds %d: pop every pushed batch before changing the frame size", cols, rows, need, s->cap);
-      return ORBFE_ERR_INVALID;
-    }
-    s->cap = need;
-    for (Slot& sl : s->slots) {
-      sl.kps.resize((size_t)s->batch * need);
-      sl.desc.resize((size_t)s->batch * need * 32);
-      sl.m12.assign((size_t)s->batch * need, -1);
-      sl.prevxy.resize((size_t)s->batch * need * 2);
-    }
+    const int rc = s->growCap(need, rows, cols);
+    if (rc != ORBFE_OK) return rc;
   }
   int slot;
   {
@@ -503,6 +560,7 @@ int orbfe_stream_pop(orbfe_stream* s, const OrbfeKeyPoint** kps, const uint8_t**
   int slot;
   {
     std::unique_lock<std::mutex> lk(s->mu);
+    if (s->nHeld > 0) { set_err("orbfe_stream_pop: %d result(s) of orbfe_stream_pop_hold not released", s->nHeld); return ORBFE_ERR_INVALID; }
     if (s->popped >= 0) {
       s->freeQ.push_back(s->popped);
       s->popped = -1;
@@ -539,6 +597,11 @@ int orbfe_stream_pop_hold(orbfe_stream* s, const OrbfeKeyPoint** kps, const uint
   int slot;
   {
     std::unique_lock<std::mutex> lk(s->mu);
+    if (s->popped >= 0) {   // (a pop ends the previous pop's result)
+      s->freeQ.push_back(s->popped);
+      s->popped = -1;
+      s->cv.notify_all();
+    }
     if (s->popSeq == s->pushSeq) { set_err("no batch outstanding (every pushed batch has been popped)"); return ORBFE_ERR_INVALID; }
     auto ready = [&]() -> int {
       for (size_t i = 0; i < s->slots.size(); i++)
@@ -548,6 +611,8 @@ int orbfe_stream_pop_hold(orbfe_stream* s, const OrbfeKeyPoint** kps, const uint
     s->cv.wait(lk, [&] { return ready() >= 0; });
     slot = ready();
     s->slots[slot].done = false;
+    s->slots[slot].held = true;
+    s->nHeld++;
     s->popSeq++;
   }
   *ticket = slot;
@@ -565,7 +630,9 @@ int orbfe_stream_release(orbfe_stream* s, int ticket) {
   if (!s || ticket < 0) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   {
     std::lock_guard<std::mutex> lk(s->mu);
-    if (ticket >= (int)s->slots.size()) { set_err("not a ticket of this runner"); return ORBFE_ERR_INVALID; }
+    if (ticket >= (int)s->slots.size() || !s->slots[(size_t)ticket].held) { set_err("not a held ticket of this runner"); return ORBFE_ERR_INVALID; }
+    s->slots[(size_t)ticket].held = false;
+    s->nHeld--;
     s->freeQ.push_back(ticket);
   }
   s->cv.notify_all();

@@ -27,9 +27,12 @@ namespace orbfe {
 void set_err(const char* fmt, ...);
 }
 using orbfe::set_err;
+extern "C" int orbfe_stream_capacity_for(const orbfe_stream* s, int rows, int cols);   // orbfe_stream.cpp
+extern "C" int orbfe_stream_grow_capacity(orbfe_stream* s, int need);
 
 struct orbfe_stream_multi {
   int ndev = 0, batch = 0;
+  int cap = 0;   // keypoint slots per frame of every sub-runner (they grow together, only while the whole runner is idle)
   std::vector<int> devices;
   std::vector<orbfe_stream*> sub;        // one single-device runner per entry of device_ids, batches isolated
   std::vector<orbfe_matcher*> matcher;   // the boundary pairs of a device's batches
@@ -203,6 +206,7 @@ int orbfe_stream_multi_create(int nfeatures, float scaleFactor, int nlevels, int
     for (auto* m : s->matcher) orbfe_matcher_destroy(m);
     return rc;
   }
+  s->cap = orbfe_stream_capacity(s->sub[0]);
   orbfe_stream_multi* p = s.release();
   for (int d = 0; d < n_devices; d++)
     p->finisher.emplace_back([p, d] {
@@ -232,7 +236,7 @@ void orbfe_stream_multi_destroy(orbfe_stream_multi* s) {
 }
 
 int orbfe_stream_multi_devices(const orbfe_stream_multi* s) { return s ? s->ndev : 0; }
-int orbfe_stream_multi_capacity(const orbfe_stream_multi* s) { return s && !s->sub.empty() ? orbfe_stream_capacity(s->sub[0]) : 0; }
+int orbfe_stream_multi_capacity(const orbfe_stream_multi* s) { return s ? s->cap : 0; }
 int orbfe_stream_multi_device_of_next_push(const orbfe_stream_multi* s) {
   if (!s) return -1;
   return s->devices[(size_t)(s->pushSeq % s->ndev)];
@@ -272,11 +276,28 @@ int orbfe_stream_multi_set_blur_variant(orbfe_stream_multi* s, int variant) {
 }
 
 int orbfe_stream_multi_push(orbfe_stream_multi* s, const uint8_t* const* gray, int in_device_memory, int rows, int cols, size_t stride_bytes) {
-  if (!s || !gray) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
-  long long k;
+  if (!s || !gray || rows <= 0 || cols <= 0) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  long long k, popped;
   {
     std::lock_guard<std::mutex> lk(s->mu);
     k = s->pushSeq;
+    popped = s->popSeq;
+  }
+  // one row stride for every batch: a geometry that needs more keypoint slots grows every sub-runner at once, and only while the whole
+  // runner is idle (the batch the caller holds is let go of, as by _set_*)
+  const int need = orbfe_stream_capacity_for(s->sub[0], rows, cols);
+  if (need > s->cap) {
+    if (k != popped) {
+      set_err("frames of %dx%d need %d keypoint slots per frame, the runner holds %d: pop every pushed batch before changing the frame size",
+              cols, rows, need, s->cap);
+      return ORBFE_ERR_INVALID;
+    }
+    release_held_batch(s);
+    for (auto* q : s->sub) {
+      const int rc = orbfe_stream_grow_capacity(q, need);
+      if (rc != ORBFE_OK) return rc;
+    }
+    s->cap = need;
   }
   const int rc = orbfe_stream_push(s->sub[(size_t)(k % s->ndev)], gray, in_device_memory, rows, cols, stride_bytes);
   if (rc != ORBFE_OK) return rc;
