@@ -248,6 +248,11 @@ int orbfe_debug_sincos(orbfe_extractor* h, const float* angle_deg, int n, float*
 int orbfe_debug_quadtree(const int16_t* x, const int16_t* y, const uint8_t* score, int n, int min_x, int max_x,
                          int min_y, int max_y, int n_target, int32_t* out_idx, int cap, int* n_out);
 int orbfe_debug_sincos_host_check(uint32_t lo_bits, uint32_t hi_bits, uint32_t step, long long* mismatches);
+/* The device restatement of glibc logf (the one orbfe_project_local_map uses in PredictScale) evaluated on the GPU of
+ * matcher m for n inputs, and its host build compared against the host libm over the float bit patterns [lo_bits, hi_bits]
+ * step `step` (*mismatches = values whose bits differ). */
+int orbfe_debug_logf(orbfe_matcher* m, const float* x, int n, float* out);
+int orbfe_debug_logf_host_check(uint32_t lo_bits, uint32_t hi_bits, uint32_t step, long long* mismatches);
 
 /* ---------------------------------------------------------------------------------------------
  * Stream runner (throughput path; no counterpart class in the reference, whose Tracking thread drives
@@ -542,6 +547,69 @@ int orbfe_search_projected_frame(orbfe_matcher* m, orbfe_frame* f, int n_src, co
                                  const int32_t* src_level, const uint8_t* src_valid, const uint8_t* src_desc,
                                  const uint8_t* kp_skip, int claim, const float* inv_level_sigma2, int nlevels, double chi2,
                                  int max_dist, int32_t* best_idx, int32_t* best_dist, int* nmatches);
+/* ---------------------------------------------------------------------------------------------
+ * Local map on the device.  Tracking::SearchLocalPoints (src/Tracking.cc:798-825) calls Frame::isInFrustum(pMP, 0.5)
+ * (src/Frame.cc:151-207) for every local MapPoint and then SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th).  An
+ * orbfe_local_map is a table of the MapPoint fields that projection reads, one 64-byte row per MapPoint, in the memory of
+ * the matcher's device: pos[3] (GetWorldPos), normal[3] (GetNormal), the RAW mfMinDistance and mfMaxDistance (PredictScale,
+ * src/MapPoint.cc:370-379, divides the raw mfMaxDistance; GetMin/MaxDistanceInvariance, :358-368, scale them by 0.8f / 1.2f),
+ * then the 32-byte descriptor (GetDescriptor).  The caller keeps the rows current; a search names its MapPoints by row.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct orbfe_local_map orbfe_local_map;
+/* Frame::isInFrustum skips a MapPoint that Tracking::SearchLocalPoints skips: mnLastFrameSeen == mCurrentFrame.mnId
+ * (Tracking.cc:804-805; the MapPoints already matched in this frame). */
+#define ORBFE_MP_SKIP 16u
+/* The camera of the current Frame, as the Frame holds it: mRcw (row-major), mtcw, mOw (passed as it is, nothing is
+ * recomputed), fx, fy, cx, cy, mfLogScaleFactor.  The image bounds mnMinX..mnMaxY are the resident frame's. */
+typedef struct OrbfeCamera {
+  float Rcw[9];
+  float tcw[3];
+  float Ow[3];
+  float fx, fy, cx, cy;
+  float logScaleFactor;
+} OrbfeCamera;
+/* A table of `capacity` rows (zeroed) for searches through matcher m (the table lives on m's device; its uploads are
+ * ordered on m's stream). */
+int orbfe_local_map_create(orbfe_matcher* m, int capacity, orbfe_local_map** out);
+void orbfe_local_map_destroy(orbfe_local_map* map);
+int orbfe_local_map_capacity(const orbfe_local_map* map);
+/* Writes rows[0..n) of the table: entry i of each array goes to row rows[i] (pos, normal: 3 floats per entry; min_raw,
+ * max_raw: 1; desc: 32 bytes).  Any array may be NULL: that field of those rows keeps its value.  Asynchronous: the
+ * values are copied into page-locked staging the library owns and sent on the matcher's stream, ordered before its next
+ * search; the caller's arrays may be reused when the call returns.  A row outside [0, capacity) or a row named twice
+ * fails the call with ORBFE_ERR_INVALID before anything is sent. */
+int orbfe_local_map_set_rows(orbfe_local_map* map, int n, const int32_t* rows, const float* pos, const float* normal,
+                             const float* min_raw, const float* max_raw, const uint8_t* desc);
+/* bool Frame::isInFrustum(MapPoint*, float viewingCosLimit) (src/Frame.cc:151-207) for MapPoint i = table row rows[i],
+ * i < n_mp, on the GPU, as Tracking::SearchLocalPoints calls it (Tracking.cc:800-814): a MapPoint whose flags[i] carry
+ * ORBFE_MP_BAD or ORBFE_MP_SKIP is not projected (in_view 0); other bits of flags are ignored.  Per MapPoint:
+ *   in_view [n_mp]     : the return value (mbTrackInView)
+ *   proj_xy [2*n_mp]   : mTrackProjX, mTrackProjY     level [n_mp] : mnTrackScaleLevel (PredictScale, NOT clamped: a
+ *   view_cos [n_mp]    : mTrackViewCos                 level outside [0, nlevels) is reported as it is)
+ * bit for bit what the reference writes into the MapPoint (float cv::Mat arithmetic, glibc logf); where in_view is 0 the
+ * other three hold 0 (the reference leaves the MapPoint's old values).  *n_in_view = MapPoints in view (nToMatch).  Any
+ * output array may be NULL.  rows and flags are host memory; a row outside [0, capacity) of a MapPoint that is projected
+ * fails the call with ORBFE_ERR_INVALID.  Returns when the outputs are written. */
+int orbfe_project_local_map(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
+                            float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp, uint8_t* in_view,
+                            float* proj_xy, int32_t* level, float* view_cos, int* n_in_view);
+/* The projection of orbfe_project_local_map followed by int ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&
+ * vpLocalMapPoints, const float th) (ORBmatcher.cc:45-132, ORBmatcher(nnratio)) in ONE submission on the matcher's stream:
+ * the projection kernel leaves the queries in device memory and the search reads them there; no per-MapPoint value
+ * crosses PCIe between the two.  flags: ORBFE_MP_BAD / _SKIP as above, ORBFE_MP_CANDIDATO / _OBSERVED as for
+ * orbfe_search_by_projection; ORBFE_MP_IN_VIEW is computed, its input value ignored.  kp_occupied, kp_assigned, nmatches,
+ * scale_factors (F.mvScaleFactors, 1..32 levels) as for orbfe_search_by_projection_frame.  in_view, proj_xy, level, view_cos:
+ * optional outputs (NULL: not returned), as orbfe_project_local_map.  Results are those of orbfe_project_local_map followed
+ * by orbfe_search_by_projection_frame_rows on the same inputs.
+ * LEVEL CONTRACT: a MapPoint in view whose predicted level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID
+ * (as an out-of-range level does in the rows form).  The projection kernel finds it and takes it out of the search before
+ * anything is indexed with that level; the outputs are then unspecified, and the matcher, frame and table stay usable. */
+int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
+                                    float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp,
+                                    const float* scale_factors, int nlevels, const uint8_t* kp_occupied, float th, float nnratio,
+                                    uint8_t* in_view, float* proj_xy, int32_t* level, float* view_cos, int32_t* kp_assigned,
+                                    int* nmatches, int* n_in_view);
+
 /* Rounds the bookkeeping kernel of the last `_frame` search needed -- the most any chunk of 2 048 consecutive queries took
  * (negative: a chunk hit the bound ORBFE_RESOLVE_MAX_ROUNDS, default 48, and a serial pass on the device finished it). */
 int orbfe_debug_resolve_rounds(const orbfe_matcher* m);

@@ -215,6 +215,7 @@ class MatcherContext {
     if (table_.pending) orbfe_matcher_synchronize(m_);
     if (table_.rows) orbfe_device_free(device_, table_.rows);
     if (table_.mirror) orbfe_host_free(table_.mirror);
+    if (lmap_.map) orbfe_local_map_destroy(lmap_.map);
     orbfe_matcher_destroy(m_);
     for (auto& s : scratch_)
       if (s.p) orbfe_host_free(s.p);
@@ -378,6 +379,61 @@ class MatcherContext {
   size_t tableRowsFromDevice() const { return table_.rowsFromDevice; }  // descriptor reads served by the device copy
   size_t tableRows() const { return table_.used; }
 
+  // ---- the local map on the device (SearchLocalPoints below): the 64-byte rows of orbfe_local_map (position, normal, raw
+  // mfMinDistance / mfMaxDistance, descriptor), keyed by the MapPoint's ADDRESS, with a host mirror.  localMapRow compares a
+  // MapPoint's current row with its mirror row BY CONTENT; only rows that differ (a moved MapPoint, a new normal or depth
+  // range, a recomputed descriptor, a new MapPoint, a new object at a recycled address) are sent, all of them in one
+  // orbfe_local_map_set_rows call by localMapCommit -- asynchronous, ordered before the search on the matcher's stream.
+  // Rows of MapPoints that are gone are reclaimed by starting over when the table holds more than 4x the rows one search
+  // uses (at least 16 384).
+  void localMapBegin(size_t nQueries) {
+    LocalMapRows& t = lmap_;
+    if (t.rowOf.size() > std::max<size_t>(16384, 4 * std::max(nQueries, t.lastQueries))) {
+      t.rowOf.clear(); t.used = 0; t.dirty.clear();   // (every row is new again: none is compared with the mirror)
+      std::fill(t.queued.begin(), t.queued.end(), (uint8_t)0);
+    }
+    t.lastQueries = nQueries;
+    if (!t.map) growLocalMap(std::max<size_t>(4096, nQueries + nQueries / 2));
+  }
+  int32_t localMapRow(const void* pMP, const uint8_t row[64]) {
+    LocalMapRows& t = lmap_;
+    auto it = t.rowOf.find(pMP);
+    int32_t r;
+    if (it == t.rowOf.end()) {
+      if (t.used + 1 > t.cap) growLocalMap(t.used + 1 + (t.used + 1) / 2);
+      r = (int32_t)t.used++;
+      t.rowOf.emplace(pMP, r);
+    } else {
+      r = it->second;
+      if (std::memcmp(&t.mirror[(size_t)r * 64], row, 64) == 0) return r;
+    }
+    if (!t.queued[(size_t)r]) { t.queued[(size_t)r] = 1; t.dirty.push_back(r); }
+    std::memcpy(&t.mirror[(size_t)r * 64], row, 64);
+    return r;
+  }
+  void localMapCommit() {
+    LocalMapRows& t = lmap_;
+    if (t.dirty.empty()) return;
+    const size_t n = t.dirty.size();
+    std::vector<float> pos(3 * n), nrm(3 * n), dmin(n), dmax(n);
+    std::vector<uint8_t> desc(32 * n);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* src = &t.mirror[(size_t)t.dirty[i] * 64];
+      std::memcpy(&pos[3 * i], src, 12);
+      std::memcpy(&nrm[3 * i], src + 12, 12);
+      std::memcpy(&dmin[i], src + 24, 4);
+      std::memcpy(&dmax[i], src + 28, 4);
+      std::memcpy(&desc[32 * i], src + 32, 32);
+    }
+    check(orbfe_local_map_set_rows(t.map, (int)n, t.dirty.data(), pos.data(), nrm.data(), dmin.data(), dmax.data(), desc.data()));
+    for (int32_t r : t.dirty) t.queued[(size_t)r] = 0;
+    t.rowsSent += n;
+    t.dirty.clear();
+  }
+  orbfe_local_map* localMap() const { return lmap_.map; }
+  size_t localMapRowsSent() const { return lmap_.rowsSent; }   // rows that went to the device (first sight or new content)
+  size_t localMapRows() const { return lmap_.used; }
+
  private:
   struct Entry { int n = 0; detail::Hash128 keys, desc; float bounds[4] = {0, 0, 0, 0}; orbfe_frame* frame = nullptr; };
   // the extractor route: F.mvKeys are the records some live Extractor of this device returned last (same count, same
@@ -443,6 +499,29 @@ class MatcherContext {
     t.notOnDevice.resize(cap, 0);
   }
   DescTable table_;
+  struct LocalMapRows {
+    orbfe_local_map* map = nullptr;
+    size_t cap = 0, used = 0, lastQueries = 0, rowsSent = 0;
+    std::unordered_map<const void*, int32_t> rowOf;   // MapPoint address -> row
+    std::vector<uint8_t> mirror;                      // [cap][64] what the device rows hold (or will, once `dirty` is sent)
+    std::vector<int32_t> dirty;                       // rows whose new content has not been sent yet (each once)
+    std::vector<uint8_t> queued;                      // [cap] 1: the row is in `dirty`
+  };
+  void growLocalMap(size_t cap) {
+    LocalMapRows& t = lmap_;
+    orbfe_local_map* m = nullptr;
+    check(orbfe_local_map_create(m_, (int)cap, &m));
+    if (t.map) {   // the new table starts empty: every row in use is sent again with the next commit
+      orbfe_local_map_destroy(t.map);
+      for (size_t r = 0; r < t.used; r++)
+        if (!t.queued[r]) { t.queued[r] = 1; t.dirty.push_back((int32_t)r); }
+    }
+    t.map = m;
+    t.cap = cap;
+    t.mirror.resize(cap * 64, 0);
+    t.queued.resize(cap, 0);
+  }
+  LocalMapRows lmap_;
 };
 
 namespace detail {
@@ -680,6 +759,86 @@ inline bool projectIntoKeyFrame(KeyFrameT* pKF, MapPointT* pMP, const float Rcw[
   return true;
 }
 }  // namespace detail
+
+// ---------------------------------------------------------------------------------------------------------------
+// void Tracking::SearchLocalPoints()  (src/Tracking.cc:798-825), from the projection loop onwards: for every local MapPoint
+// that is not skipped (mnLastFrameSeen == F.mnId) and not bad, Frame::isInFrustum(pMP, viewingCosLimit) (src/Frame.cc:151-207),
+// IncreaseVisible() for the ones in view, then SearchByProjection(F, vpLocalMapPoints, th) with ORBmatcher(0.8) -- the
+// projection and the search in one GPU submission (orbfe_search_local_points_frame).  The caller keeps the loop in front of it
+// (Tracking.cc:784-796: MapPoints already matched in F get mnLastFrameSeen = F.mnId and mbTrackInView = false) and chooses th
+// (1, or 5 right after a relocalisation, :820-822).
+// os1 keeps a MapPoint's mWorldPos, mNormalVector and mfMinDistance / mfMaxDistance protected (include/MapPoint.h): the
+// integrator hands them over with `geometry(pMP, pos, normal, minRaw, maxRaw)` (float pos[3], normal[3]; float& minRaw,
+// maxRaw = the RAW fields, not the 0.8f / 1.2f invariance bounds), under the MapPoint's position mutex.  The rows go to the
+// context's device table (changed rows only, MatcherContext::localMapRow).  Written back, as the reference does:
+// mbTrackInView, mTrackProjX / Y, mnTrackScaleLevel, mTrackViewCos of every projected MapPoint (isInFrustum sets
+// mbTrackInView = false first and leaves the other fields alone when it returns false), IncreaseVisible(), F.mvpMapPoints.
+// Returns the number of matches.  F's pose: Rcw, tcw from F.mTcw (UpdatePoseMatrices' views of it), Ow = F.GetCameraCenter().
+template <class FrameT, class MapPointT, class GeometryFn>
+inline int SearchLocalPoints(MatcherContext& ctx, FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoints, float th,
+                             float viewingCosLimit, GeometryFn geometry) {
+  const int n = (int)F.mvKeysUn.size(), nmp = (int)vpLocalMapPoints.size();
+  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
+  uint8_t* flags = ctx.scratch<uint8_t>(1, nmp, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, nmp, true);
+  uint8_t* inView = ctx.scratch<uint8_t>(3, nmp, false);
+  float* xy = ctx.scratch<float>(4, (size_t)nmp * 2, false);
+  int32_t* lvl = ctx.scratch<int32_t>(5, nmp, false);
+  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
+  float* vcos = ctx.scratch<float>(7, nmp, false);
+  OrbfeCamera cam;
+  detail::poseRt(F.mTcw, cam.Rcw, cam.tcw);
+  detail::vec3(F.GetCameraCenter(), cam.Ow);
+  cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy;
+  cam.logScaleFactor = F.mfLogScaleFactor;
+  for (int i = 0; i < n; i++)
+    if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) occ[i] = 1;
+  ctx.localMapBegin((size_t)nmp);
+  for (int i = 0; i < nmp; i++) {
+    MapPointT* p = vpLocalMapPoints[i];
+    if (p->mnLastFrameSeen == F.mnId) { flags[i] = ORBFE_MP_SKIP; continue; }   // Tracking.cc:804-805
+    if (p->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                       // :806-807
+    flags[i] = (uint8_t)((p->plCandidato ? ORBFE_MP_CANDIDATO : 0) | (p->Observations() > 0 ? ORBFE_MP_OBSERVED : 0));
+    float row[16];
+    float& minRaw = row[6];
+    float& maxRaw = row[7];
+    geometry(p, row, row + 3, minRaw, maxRaw);
+    const auto d = p->GetDescriptor();
+    std::memcpy(row + 8, d.data, 32);
+    rows[i] = ctx.localMapRow(p, reinterpret_cast<const uint8_t*>(row));
+  }
+  ctx.localMapCommit();
+  orbfe_frame* rf = ctx.resident(F, 0);
+  orbfe_frame* tmpFrame = nullptr;
+  if (!rf) {   // the context's frame cache is off: a frame for this call only
+    float b[4];
+    detail::frameBounds(F, b);
+    std::vector<uint8_t> tmp;
+    check(orbfe_frame_create(ctx.get(), reinterpret_cast<const OrbfeKeyPoint*>(F.mvKeysUn.data()),
+                             detail::packedDescriptors(F.mDescriptors, n, tmp), n, b, &tmpFrame));
+    rf = tmpFrame;
+  }
+  int nmatches = 0, nInView = 0;
+  const int rc = orbfe_search_local_points_frame(ctx.get(), rf, ctx.localMap(), &cam, viewingCosLimit, rows, flags, nmp,
+                                                 F.mvScaleFactors.data(), (int)F.mvScaleFactors.size(), occ, th, 0.8f, inView, xy,
+                                                 lvl, vcos, assigned, &nmatches, &nInView);
+  if (tmpFrame) orbfe_frame_destroy(tmpFrame);
+  check(rc);
+  for (int i = 0; i < nmp; i++) {
+    if (flags[i] & (ORBFE_MP_SKIP | ORBFE_MP_BAD)) continue;
+    MapPointT* p = vpLocalMapPoints[i];
+    p->mbTrackInView = inView[i] != 0;
+    if (!inView[i]) continue;
+    p->mTrackProjX = xy[2 * i];
+    p->mTrackProjY = xy[2 * i + 1];
+    p->mnTrackScaleLevel = lvl[i];
+    p->mTrackViewCos = vcos[i];
+    p->IncreaseVisible();
+  }
+  for (int i = 0; i < n; i++)
+    if (assigned[i] >= 0) F.mvpMapPoints[i] = vpLocalMapPoints[assigned[i]];
+  return nmatches;
+}
 
 // int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th)   (ORBmatcher.cc:1292-1423)
 template <class Ops = detail::RestatedOps, class FrameT>

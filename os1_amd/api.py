@@ -176,6 +176,16 @@ def load_library():
     L.orbfe_stream_kernel_ms.argtypes = [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci]
     L.orbfe_debug_quadtree.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, C.POINTER(ci)]
     L.orbfe_debug_sincos_host_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_longlong)]
+    L.orbfe_debug_logf.argtypes = [vp, vp, ci, vp]
+    L.orbfe_debug_logf_host_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_longlong)]
+    L.orbfe_local_map_create.argtypes = [vp, ci, C.POINTER(vp)]
+    L.orbfe_local_map_destroy.argtypes = [vp]
+    L.orbfe_local_map_destroy.restype = None
+    L.orbfe_local_map_capacity.argtypes = [vp]
+    L.orbfe_local_map_set_rows.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_project_local_map.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci)]
+    L.orbfe_search_local_points_frame.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, ci, vp, cf, cf, vp, vp, vp, vp, vp,
+                                                  C.POINTER(ci), C.POINTER(ci)]
     _lib = L
     return L
 
@@ -383,6 +393,66 @@ class Extractor:
         return c, s
 
 
+class Camera(C.Structure):
+    """OrbfeCamera: the current Frame's mRcw (row-major), mtcw, mOw, fx, fy, cx, cy and mfLogScaleFactor."""
+    _fields_ = [('Rcw', C.c_float * 9), ('tcw', C.c_float * 3), ('Ow', C.c_float * 3), ('fx', C.c_float), ('fy', C.c_float),
+                ('cx', C.c_float), ('cy', C.c_float), ('logScaleFactor', C.c_float)]
+
+    @classmethod
+    def make(cls, Rcw, tcw, Ow, fx, fy, cx, cy, log_scale_factor):
+        c = cls()
+        c.Rcw[:] = [float(v) for v in np.asarray(Rcw, np.float32).ravel()]
+        c.tcw[:] = [float(v) for v in np.asarray(tcw, np.float32).ravel()]
+        c.Ow[:] = [float(v) for v in np.asarray(Ow, np.float32).ravel()]
+        c.fx, c.fy, c.cx, c.cy = float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy))
+        c.logScaleFactor = float(np.float32(log_scale_factor))
+        return c
+
+
+MP_IN_VIEW, MP_BAD, MP_CANDIDATO, MP_OBSERVED, MP_SKIP = 1, 2, 4, 8, 16
+
+
+class LocalMap:
+    """orbfe_local_map: `capacity` 64-byte MapPoint rows (pos, normal, raw mfMin/MaxDistance, descriptor) on the matcher's
+    device, searched through that matcher."""
+
+    def __init__(self, matcher, capacity):
+        self.L = load_library()
+        self.matcher = matcher
+        h = C.c_void_p()
+        _check(self.L.orbfe_local_map_create(matcher.h, capacity, C.byref(h)))
+        self.h = h
+        self.capacity = capacity
+
+    def set_rows(self, rows, pos=None, normal=None, min_raw=None, max_raw=None, desc=None):
+        """Rows rows[i] := entry i of each given array (None: that field keeps its value).  Asynchronous, ordered before
+        the matcher's next search."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        keep = []
+
+        def arg(a, dt, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt).reshape(shape)
+            keep.append(a)
+            return _p(a)
+        n = len(rows)
+        _check(self.L.orbfe_local_map_set_rows(self.h, n, _p(rows), arg(pos, np.float32, (n, 3)), arg(normal, np.float32, (n, 3)),
+                                               arg(min_raw, np.float32, (n,)), arg(max_raw, np.float32, (n,)),
+                                               arg(desc, np.uint8, (n, 32))))
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.orbfe_local_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Frame:
     """A Frame's features resident on the GPU (orbfe_frame): mvKeysUn, mDescriptors and the grid, built once.  Pass it
     as the `kps` argument of Matcher.search_by_projection / _uv / search_projected (desc and bounds are then ignored)."""
@@ -560,6 +630,48 @@ class Matcher:
                                                             _p(mp_viewcos), _p(mp_flags), C.c_void_p(table.dev), C.c_void_p(table.host.base),
                                                             _p(rows), table.cap, len(mp_level), th, nnratio, _p(assigned), C.byref(n)))
         return n.value, assigned[:len(frame)]
+
+    def project_local_map(self, frame, lmap, cam, rows, flags, cos_limit=0.5):
+        """Frame::isInFrustum(pMP, cos_limit) for MapPoint i = row rows[i] of `lmap` (flags: MP_BAD / MP_SKIP skip it):
+        dict of in_view, proj_xy, level, view_cos arrays and n_in_view."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        n = len(rows)
+        iv = np.zeros(max(n, 1), np.uint8)
+        xy = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        vc = np.zeros(max(n, 1), np.float32)
+        cnt = C.c_int(0)
+        _check(self.L.orbfe_project_local_map(self.h, frame.h, lmap.h, C.byref(cam), cos_limit, _p(rows), _p(flags), n, _p(iv),
+                                              _p(xy), _p(lv), _p(vc), C.byref(cnt)))
+        return dict(in_view=iv[:n], proj_xy=xy[:n], level=lv[:n], view_cos=vc[:n], n_in_view=cnt.value)
+
+    def search_local_points(self, frame, lmap, cam, rows, flags, kp_occupied, scale_factors, th, nnratio=0.8, cos_limit=0.5):
+        """Projection + SearchByProjection(F, vpLocalMapPoints, th) in one submission: dict of nmatches, kp_assigned,
+        n_in_view and the projection's in_view, proj_xy, level, view_cos."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        occ = np.ascontiguousarray(kp_occupied, np.uint8)
+        n = len(rows)
+        iv = np.zeros(max(n, 1), np.uint8)
+        xy = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        vc = np.zeros(max(n, 1), np.float32)
+        assigned = np.full(max(len(frame), 1), -1, np.int32)
+        nm, cnt = C.c_int(0), C.c_int(0)
+        _check(self.L.orbfe_search_local_points_frame(self.h, frame.h, lmap.h, C.byref(cam), cos_limit, _p(rows), _p(flags), n,
+                                                      _p(sf), len(sf), _p(occ), th, nnratio, _p(iv), _p(xy), _p(lv), _p(vc),
+                                                      _p(assigned), C.byref(nm), C.byref(cnt)))
+        return dict(nmatches=nm.value, kp_assigned=assigned[:len(frame)], n_in_view=cnt.value, in_view=iv[:n], proj_xy=xy[:n],
+                    level=lv[:n], view_cos=vc[:n])
+
+    def logf(self, x):
+        """The device restatement of glibc logf, evaluated on this matcher's GPU."""
+        a = np.ascontiguousarray(x, np.float32)
+        out = np.zeros_like(a)
+        _check(self.L.orbfe_debug_logf(self.h, _p(a), a.size, _p(out)))
+        return out
 
     def upload_async(self, dst_device, src_host_ptr, nbytes):
         _check(self.L.orbfe_matcher_upload_async(self.h, C.c_void_p(dst_device), C.c_void_p(src_host_ptr), nbytes))
@@ -801,6 +913,14 @@ def compute_image_bounds(cols, rows, mode, fx, fy, cx, cy, dist=()):
 def sincos_host_mismatches(lo_bits, hi_bits, step=1):
     bad = C.c_longlong(0)
     _check(load_library().orbfe_debug_sincos_host_check(lo_bits, hi_bits, step, C.byref(bad)))
+    return bad.value
+
+
+def logf_host_mismatches(lo_bits, hi_bits, step=1):
+    """Floats with bit patterns lo_bits, lo_bits + step, ... <= hi_bits on which the host build of the device logf
+    restatement differs from the host libm."""
+    bad = C.c_longlong(0)
+    _check(load_library().orbfe_debug_logf_host_check(lo_bits, hi_bits, step, C.byref(bad)))
     return bad.value
 
 

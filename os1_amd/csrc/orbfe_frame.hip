@@ -672,6 +672,9 @@ struct RawQ {
   const int* descRow = nullptr;       // indexed descriptor rows (orbfe_search_by_projection_frame_rows): host array [nq] ...
   const uint8_t* descHost = nullptr;  // ... and the table's complete page-locked host mirror
   int descRowWhere = 0;
+  // internal route (orbfe_search_local_points_frame): xy, level, aux, flags, claimSrc, descRow and the descriptor table are
+  // already in the frame's device memory, written there earlier on the matcher's stream; only occ is a host array
+  bool device = false;
   // where each array lives (gpu_readable), filled by classify_host_arrays: xy, level, aux, flags, claimSrc, angle, occ
   int where[7] = {0, 0, 0, 0, 0, 0, 0};
 };
@@ -788,8 +791,9 @@ int run_search(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const uint
   // queries: one copy for the scalar arrays; descriptor rows straight from the caller's memory when it is page-locked
   // (the kernel fetches rows as two 16-byte words: rows it reads in place must be 16-byte aligned)
   const bool indexed = raw && raw->descRow;
+  const bool devQ = raw && raw->device;
   const int rowsWhere = gpu_readable(qdescHost, m->device);
-  if (indexed && (rowsWhere != 2 || gpu_readable(raw->descHost, m->device) != 1 || ((uintptr_t)raw->descHost & 15u) != 0)) {
+  if (indexed && !devQ && (rowsWhere != 2 || gpu_readable(raw->descHost, m->device) != 1 || ((uintptr_t)raw->descHost & 15u) != 0)) {
     set_err("indexed descriptor rows: the table must live in the frame's device memory and its mirror in page-locked host memory, both 16-byte aligned");
     return ORBFE_ERR_INVALID;
   }
@@ -803,9 +807,12 @@ int run_search(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const uint
   // own latency plus a copy-engine -> compute hand-over (16 + 8 us measured for the 490 KB of 10 000 MapPoints).
   // ORBFE_FRAME_ZEROCOPY=0 brings the upload back.
   const bool zeroCopy = frame_zero_copy();
-  if (raw && !zeroCopy) { set_err("raw queries need the zero-copy route"); return ORBFE_ERR_INVALID; }
+  if (raw && !zeroCopy && !devQ) { set_err("raw queries need the zero-copy route"); return ORBFE_ERR_INVALID; }
+  if (devQ && rowsWhere != 2) { set_err("device-resident queries: the descriptor table must live in the frame's device memory"); return ORBFE_ERR_INVALID; }
   const uint8_t* qdescDev = m->d_q.p + P.oQd;
-  if (zeroCopy) {
+  if (devQ) {
+    qdescDev = qdescHost;   // (nothing to upload: every query array is in device memory, the occupancy bytes are read below)
+  } else if (zeroCopy) {
     if (pinned) qdescDev = qdescHost;
     else { memcpy(P.qdesc, qdescHost, 32 * (size_t)nq); qdescDev = P.qdesc; }
   } else if (pinned) {
@@ -1354,5 +1361,59 @@ int projected_via_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uin
   if (rc) return rc;
   return orbfe_search_projected_frame(m, f, n_src, src_uv, src_radius, src_level, src_valid, src_desc, kp_skip, claim,
                                       inv_level_sigma2, nlevels, chi2, max_dist, best_idx, best_dist, nmatches);
+}
+}  // namespace orbfe
+
+namespace orbfe {
+// SearchByProjection(F, vpLocalMapPoints, th) on queries that are already in the frame's device memory
+// (orbfe_search_local_points_frame, orbfe_localmap.hip: k_project_local_map wrote them earlier on the matcher's stream).
+// MapPoint i: d_xy[2i..], d_level[i], d_viewcos[i], d_flags[i] (ORBFE_MP_* bits), descriptor row d_desc_row[i] of d_desc
+// (32-byte rows; bit 31 clear).  The host reads none of them: the window bound comes from th and the largest of the nlevels
+// scale factors, and every query the projection kernel flagged IN_VIEW carries a level inside [0, nlevels) -- it clears the
+// flag of any other one, before this search reads it.  kp_occupied is host memory (page-locked: read in place).
+int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                             const float* d_xy, const int32_t* d_level, const float* d_viewcos, const uint8_t* d_flags,
+                             const uint8_t* d_desc, const int32_t* d_desc_row, int n_mp, float th, float nnratio,
+                             int32_t* kp_assigned, int* nmatches) {
+  const double tEntry = orbfe_matcher::nowMs();
+  if (!m || !f || !nmatches || n_mp < 0 || !scale_factors || nlevels < 1 || nlevels > 32 || (f->n && (!kp_occupied || !kp_assigned)) ||
+      (n_mp && (!d_xy || !d_level || !d_viewcos || !d_flags || !d_desc || !d_desc_row))) {
+    set_err("bad argument");
+    return ORBFE_ERR_INVALID;
+  }
+  const int n = f->n;
+  *nmatches = 0;
+  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
+  if (n_mp == 0 || n == 0) return ORBFE_OK;
+  if (gpu_readable(kp_occupied, m->device) == 2) { set_err("the occupancy bytes must be host memory"); return ORBFE_ERR_INVALID; }
+  m->tEntry = tEntry;
+  SearchPlan P;
+  int rc = plan_search(m, f, kModeMapPoints, n_mp, true, 0, &P);
+  if (rc) return rc;
+  const bool bFactor = th != 1.0;
+  RawQ Q;
+  Q.kind = 1; Q.xy = d_xy; Q.level = d_level; Q.aux = d_viewcos; Q.flags = d_flags;
+  Q.claimSrc = d_flags; Q.claimMask = ORBFE_MP_OBSERVED;
+  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th; Q.factor = bFactor ? 1 : 0;
+  Q.descRow = d_desc_row; Q.descRowWhere = 2;
+  Q.device = true;
+  for (int k = 0; k < 5; k++) Q.where[k] = 2;
+  Q.where[6] = gpu_readable(kp_occupied, m->device);
+  float maxSf = 0.f;
+  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
+  float rmaxRaw = 4.0f;
+  if (bFactor) rmaxRaw *= th;
+  const int* out = nullptr;
+  if ((rc = run_search(m, f, P, d_desc, rmaxRaw * maxSf, nnratio, TH_HIGH, 0.0, 0, &out, nmatches, &Q))) return rc;
+  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
+  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
+  return ORBFE_OK;
+}
+}  // namespace orbfe
+
+namespace orbfe {
+// mnMinX, mnMaxX, mnMinY, mnMaxY of a resident frame (the projection of orbfe_localmap.hip checks against them)
+void frame_bounds(const orbfe_frame* f, float out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = f->bounds[i];
 }
 }  // namespace orbfe

@@ -1,0 +1,448 @@
+// orbfe_localmap.hip -- the local map on the device: Frame::isInFrustum over Tracking's local MapPoints, and that
+// projection fused with SearchByProjection(F, vpLocalMapPoints, th).
+//
+// Tracking::SearchLocalPoints (reference src/Tracking.cc:798-825) calls Frame::isInFrustum(pMP, 0.5) (src/Frame.cc:151-207)
+// for every local MapPoint on the tracking thread, then ORBmatcher::SearchByProjection on the ones in view.  Here the
+// MapPoint fields the projection reads live in a device table (one 64-byte row per MapPoint, kept current by the caller
+// with orbfe_local_map_set_rows), k_project_local_map restates isInFrustum one lane per MapPoint, and the fused call leaves
+// its results in device memory where the resident frame's window search (orbfe_frame.hip) reads them: one submission of
+// three kernels on the matcher's stream, no copy command in between.
+//
+// The arithmetic is the reference's cv::Mat float arithmetic as the oracle pins it (oracle/orb_oracle.cpp cvGemm3, cvNorm3,
+// cvDot3, predictScale; include/orbfe/orb_shim.hpp RestatedOps): Rcw*P+tcw is a float dot in source order with a double
+// epilogue, cv::norm and Mat::dot accumulate in double, and PredictScale's log is glibc logf (glibc_logf.h).  The library is
+// built with -ffp-contract=off, so every float operation rounds on its own as in the reference.
+#include "orbfe_matcher_internal.h"
+#include "glibc_logf.h"
+
+#include <atomic>
+
+struct orbfe_frame;
+namespace orbfe {
+void frame_bounds(const orbfe_frame* f, float out[4]);
+int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                             const float* d_xy, const int32_t* d_level, const float* d_viewcos, const uint8_t* d_flags,
+                             const uint8_t* d_desc, const int32_t* d_desc_row, int n_mp, float th, float nnratio,
+                             int32_t* kp_assigned, int* nmatches);
+}  // namespace orbfe
+
+namespace {
+
+constexpr int kRowBytes = 64;        // pos[3], normal[3], mfMinDistance, mfMaxDistance, descriptor[32]
+constexpr int kProjThreads = 256;
+constexpr int kStageBytes = 80;      // set_rows staging record: row, field mask, pad, the 64-byte row
+
+// set_rows: staged records (page-locked, read in place) -> table rows; fields whose mask bit is clear keep their value.
+// Mask bits: 1 pos, 2 normal, 4 min, 8 max, 16 descriptor.
+__global__ __launch_bounds__(256) void k_local_map_scatter(const uint8_t* __restrict__ stage, int n, uint8_t* __restrict__ table) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* rec = stage + (size_t)i * kStageBytes;
+  const int row = reinterpret_cast<const int*>(rec)[0];
+  const unsigned mask = reinterpret_cast<const unsigned*>(rec)[1];
+  const float* src = reinterpret_cast<const float*>(rec + 16);
+  float* dst = reinterpret_cast<float*>(table + (size_t)row * kRowBytes);
+  if (mask & 1u) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; }
+  if (mask & 2u) { dst[3] = src[3]; dst[4] = src[4]; dst[5] = src[5]; }
+  if (mask & 4u) dst[6] = src[6];
+  if (mask & 8u) dst[7] = src[7];
+  if (mask & 16u) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(rec + 48);
+    uint4* d4 = reinterpret_cast<uint4*>(table + (size_t)row * kRowBytes + 32);
+    d4[0] = s4[0];
+    d4[1] = s4[1];
+  }
+}
+
+struct ProjParams {
+  const uint8_t* table;
+  const int32_t* rows;         // [n] (page-locked host memory)
+  const uint8_t* flags;        // [n]
+  int n;
+  OrbfeCamera cam;
+  float minX, maxX, minY, maxY;
+  float cosLimit;
+  int nlevels;                 // fused call: levels outside [0, nlevels) are taken out of the search and reported
+  // outputs in page-locked host memory (any may be null)
+  uint8_t* inView;
+  float* xy;
+  int32_t* level;
+  float* vcos;
+  // fused call: the search's queries in device memory (null: projection only)
+  float* dxy;
+  int32_t* dlevel;
+  float* dvcos;
+  uint8_t* dflags;
+  int32_t* drow;
+  int* blockInfo;              // [2 * blocks] page-locked: MapPoints in view, first MapPoint with an out-of-range level (-1)
+};
+
+// bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit)  (src/Frame.cc:151-207), one lane per listed MapPoint
+__global__ __launch_bounds__(kProjThreads) void k_project_local_map(ProjParams P) {
+  __shared__ int firstBad;
+  if (threadIdx.x == 0) firstBad = INT_MAX;
+  __syncthreads();
+  const int i = blockIdx.x * kProjThreads + threadIdx.x;
+  bool inView = false;
+  float u = 0.f, v = 0.f, viewCos = 0.f;
+  int lvl = 0, row = 0;
+  unsigned fl = 0;
+  if (i < P.n) {
+    fl = P.flags[i];
+    row = P.rows[i];
+    // Tracking.cc:804-807: mnLastFrameSeen == mCurrentFrame.mnId, isBad()
+    if (!(fl & (ORBFE_MP_BAD | ORBFE_MP_SKIP))) {
+      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
+      const float4 a = R[0], b = R[1];
+      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
+      const float Pn[3] = {a.w, b.x, b.y};                  // GetNormal()
+      const float minRaw = b.z, maxRaw = b.w;               // mfMinDistance, mfMaxDistance
+      const OrbfeCamera& C = P.cam;
+      // Pc = mRcw*P+mtcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
+      float Pc[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const float t = C.Rcw[3 * k] * Pw[0] + C.Rcw[3 * k + 1] * Pw[1] + C.Rcw[3 * k + 2] * Pw[2];
+        Pc[k] = (float)((double)t * 1.0 + (double)C.tcw[k] * 1.0);
+      }
+      if (!(Pc[2] < 0.0f)) {                                // Frame.cc:166-167
+        const float invz = 1.0f / Pc[2];
+        u = C.fx * Pc[0] * invz + C.cx;
+        v = C.fy * Pc[1] * invz + C.cy;
+        if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {   // Frame.cc:173-176
+          const float maxDistance = 1.2f * maxRaw;          // GetMaxDistanceInvariance (MapPoint.cc:364-368)
+          const float minDistance = 0.8f * minRaw;          // GetMinDistanceInvariance (MapPoint.cc:358-362)
+          const float PO[3] = {Pw[0] - C.Ow[0], Pw[1] - C.Ow[1], Pw[2] - C.Ow[2]};
+          double s = 0.0;                                   // cv::norm(PO)
+#pragma unroll
+          for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
+          const float dist = (float)sqrt(s);
+          if (!(dist < minDistance || dist > maxDistance)) {
+            double d = 0.0;                                 // PO.dot(Pn)
+#pragma unroll
+            for (int k = 0; k < 3; k++) d += (double)PO[k] * (double)Pn[k];
+            viewCos = (float)(d / (double)dist);
+            if (!(viewCos < P.cosLimit)) {
+              // PredictScale (MapPoint.cc:370-379): ceil(log(ratio)/logScaleFactor) with float ratio, converted to int as
+              // the host does (an out-of-range value becomes INT_MIN)
+              const float ratio = maxRaw / dist;
+              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
+              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+              inView = true;
+            }
+          }
+        }
+      }
+    }
+    if (!inView) { u = 0.f; v = 0.f; viewCos = 0.f; lvl = 0; }
+    if (P.inView) P.inView[i] = inView ? 1 : 0;
+    if (P.xy) { P.xy[2 * i] = u; P.xy[2 * i + 1] = v; }
+    if (P.level) P.level[i] = lvl;
+    if (P.vcos) P.vcos[i] = viewCos;
+    if (P.dxy) {
+      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
+      const bool levelOk = lvl >= 0 && lvl < P.nlevels;
+      if (inView && !levelOk) atomicMin(&firstBad, i);
+      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
+      P.dlevel[i] = levelOk ? lvl : 0;
+      P.dvcos[i] = viewCos;
+      P.dflags[i] = (uint8_t)((inView && levelOk ? ORBFE_MP_IN_VIEW : 0u) | (fl & (ORBFE_MP_CANDIDATO | ORBFE_MP_OBSERVED)));
+      P.drow[i] = inView ? 2 * row : 0;   // descriptor = 32-byte row 2*row of (table + 32)
+    }
+  }
+  const int count = __syncthreads_count(inView ? 1 : 0);
+  if (threadIdx.x == 0) {
+    P.blockInfo[2 * blockIdx.x] = count;
+    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
+    __threadfence_system();
+  }
+}
+
+__global__ void k_debug_logf(const float* __restrict__ x, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = orbfe::logf_glibc(x[i]);
+}
+
+// > 0: page-locked host memory (read by the kernel in place); 0: ordinary host memory; -1: device memory
+int host_readable(const void* p) {
+  hipPointerAttribute_t attr;
+  if (p && hipPointerGetAttributes(&attr, p) == hipSuccess) {
+    if (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged) return 1;
+    if (attr.type == hipMemoryTypeDevice) return -1;
+    return 0;
+  }
+  (void)hipGetLastError();
+  return 0;
+}
+
+}  // namespace
+
+struct orbfe_local_map {
+  orbfe_matcher* m = nullptr;
+  int capacity = 0;
+  DevBuf<uint8_t> table;
+  PinBuf<uint8_t> stage;           // set_rows records, read by k_local_map_scatter in place
+  hipEvent_t staged = nullptr;     // recorded after the last scatter: the staging is free again once it has completed
+  PinBuf<uint8_t> io;              // per call: copies of ordinary rows / flags arrays, outputs, per-block summary
+  DevBuf<uint8_t> q;               // fused call: the search's queries
+  std::vector<uint8_t> seen;       // set_rows duplicate check
+  ~orbfe_local_map() {
+    (void)hipSetDevice(m->device);
+    if (staged) { (void)hipEventSynchronize(staged); (void)hipEventDestroy(staged); }
+    table.release(); stage.release(); io.release(); q.release();
+    (void)hipGetLastError();
+  }
+};
+
+namespace {
+
+struct CallArea {
+  const int32_t* rows;
+  const uint8_t* flags;
+  uint8_t* inView;
+  float* xy;
+  int32_t* level;
+  float* vcos;
+  int* blockInfo;
+  int blocks;
+};
+
+// checks shared by both calls; carves the page-locked area (caller's rows / flags read in place when page-locked)
+int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam, const int32_t* rows, const uint8_t* flags,
+            int n_mp, CallArea* A) {
+  if (!m || !f || !map || !cam || n_mp < 0 || (n_mp && (!rows || !flags))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (map->m != m) { set_err("the local map belongs to another matcher (its uploads are ordered on that matcher's stream)"); return ORBFE_ERR_INVALID; }
+  if (orbfe_frame_device(f) != m->device) { set_err("frame and matcher live on different devices"); return ORBFE_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(m->device));
+  (void)hipGetLastError();
+  const int wr = host_readable(rows), wf = host_readable(flags);
+  if (n_mp && (wr < 0 || wf < 0)) { set_err("rows and flags must be host memory"); return ORBFE_ERR_INVALID; }
+  // a row is an address: one branch-free sweep, and only if it finds a row outside the table a second one over the MapPoints
+  // that are projected (skipped and bad ones may carry anything)
+  unsigned hi = 0;
+  for (int i = 0; i < n_mp; i++) hi = std::max(hi, (unsigned)rows[i]);
+  if (hi >= (unsigned)map->capacity)
+    for (int i = 0; i < n_mp; i++)
+      if (!(flags[i] & (ORBFE_MP_BAD | ORBFE_MP_SKIP)) && (unsigned)rows[i] >= (unsigned)map->capacity) {
+        set_err("MapPoint %d: row %d outside the local map (%d rows)", i, rows[i], map->capacity);
+        return ORBFE_ERR_INVALID;
+      }
+  const size_t c = (size_t)std::max(n_mp, 1);
+  A->blocks = (n_mp + kProjThreads - 1) / kProjThreads;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  const size_t oR = take(4 * c), oF = take(c), oI = take(c), oX = take(8 * c), oL = take(4 * c), oV = take(4 * c),
+               oB = take(8 * (size_t)std::max(A->blocks, 1));
+  int rc;
+  if ((rc = map->io.ensure(o))) return rc;
+  uint8_t* H = map->io.p;
+  A->rows = rows; A->flags = flags;
+  if (n_mp && wr == 0) { memcpy(H + oR, rows, 4 * (size_t)n_mp); A->rows = (const int32_t*)(H + oR); }
+  if (n_mp && wf == 0) { memcpy(H + oF, flags, (size_t)n_mp); A->flags = H + oF; }
+  A->inView = H + oI; A->xy = (float*)(H + oX); A->level = (int32_t*)(H + oL); A->vcos = (float*)(H + oV);
+  A->blockInfo = (int*)(H + oB);
+  return ORBFE_OK;
+}
+
+ProjParams params(orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam, float cosLimit, int n_mp, const CallArea& A) {
+  ProjParams P{};
+  P.table = map->table.p;
+  P.rows = A.rows; P.flags = A.flags; P.n = n_mp;
+  P.cam = *cam;
+  float b[4];
+  orbfe::frame_bounds(f, b);
+  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
+  P.cosLimit = cosLimit;
+  P.blockInfo = A.blockInfo;
+  return P;
+}
+
+// after the stream has passed the kernel: MapPoints in view, first MapPoint whose level is outside the search's range
+void summary(const CallArea& A, int* nInView, int* firstBad) {
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const volatile int* B = A.blockInfo;
+  int cnt = 0, bad = -1;
+  for (int b = 0; b < A.blocks; b++) {
+    cnt += B[2 * b];
+    if (bad < 0 && B[2 * b + 1] >= 0) bad = B[2 * b + 1];
+  }
+  *nInView = cnt;
+  *firstBad = bad;
+}
+
+void copy_out(const CallArea& A, int n_mp, uint8_t* in_view, float* proj_xy, int32_t* level, float* view_cos) {
+  if (in_view) memcpy(in_view, A.inView, (size_t)n_mp);
+  if (proj_xy) memcpy(proj_xy, A.xy, 8 * (size_t)n_mp);
+  if (level) memcpy(level, A.level, 4 * (size_t)n_mp);
+  if (view_cos) memcpy(view_cos, A.vcos, 4 * (size_t)n_mp);
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbfe_local_map_create(orbfe_matcher* m, int capacity, orbfe_local_map** out) {
+  if (!m || !out || capacity <= 0 || capacity > (1 << 26)) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(m->device));
+  orbfe_local_map* map = new orbfe_local_map();
+  map->m = m;
+  map->capacity = capacity;
+  int rc = map->table.ensure((size_t)capacity * kRowBytes);
+  if (!rc && hipMemsetAsync(map->table.p, 0, (size_t)capacity * kRowBytes, m->stream) != hipSuccess) {
+    set_err("hipMemsetAsync failed");
+    rc = ORBFE_ERR_HIP;
+  }
+  if (!rc && hipEventCreateWithFlags(&map->staged, hipEventDisableTiming) != hipSuccess) {
+    set_err("hipEventCreate failed");
+    rc = ORBFE_ERR_HIP;
+  }
+  if (rc) { delete map; return rc; }
+  *out = map;
+  return ORBFE_OK;
+}
+
+void orbfe_local_map_destroy(orbfe_local_map* map) { delete map; }
+
+int orbfe_local_map_capacity(const orbfe_local_map* map) { return map ? map->capacity : 0; }
+
+int orbfe_local_map_set_rows(orbfe_local_map* map, int n, const int32_t* rows, const float* pos, const float* normal,
+                             const float* min_raw, const float* max_raw, const uint8_t* desc) {
+  if (!map || n < 0 || (n && !rows)) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (n == 0) return ORBFE_OK;
+  map->seen.assign((size_t)map->capacity, 0);
+  for (int i = 0; i < n; i++) {
+    if (rows[i] < 0 || rows[i] >= map->capacity) { set_err("row %d outside the local map (%d rows)", rows[i], map->capacity); return ORBFE_ERR_INVALID; }
+    if (map->seen[rows[i]]) { set_err("row %d named twice", rows[i]); return ORBFE_ERR_INVALID; }
+    map->seen[rows[i]] = 1;
+  }
+  orbfe_matcher* m = map->m;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipEventSynchronize(map->staged));   // the previous upload has read its records
+  int rc;
+  if ((rc = map->stage.ensure((size_t)n * kStageBytes))) return rc;
+  const unsigned mask = (pos ? 1u : 0u) | (normal ? 2u : 0u) | (min_raw ? 4u : 0u) | (max_raw ? 8u : 0u) | (desc ? 16u : 0u);
+  for (int i = 0; i < n; i++) {
+    uint8_t* rec = map->stage.p + (size_t)i * kStageBytes;
+    int32_t* hdr = reinterpret_cast<int32_t*>(rec);
+    hdr[0] = rows[i];
+    hdr[1] = (int32_t)mask;
+    float* r = reinterpret_cast<float*>(rec + 16);
+    if (pos) memcpy(r, pos + 3 * (size_t)i, 12);
+    if (normal) memcpy(r + 3, normal + 3 * (size_t)i, 12);
+    if (min_raw) r[6] = min_raw[i];
+    if (max_raw) r[7] = max_raw[i];
+    if (desc) memcpy(rec + 48, desc + 32 * (size_t)i, 32);
+  }
+  hipLaunchKernelGGL(k_local_map_scatter, dim3((n + 255) / 256), dim3(256), 0, m->stream, (const uint8_t*)map->stage.p, n, map->table.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(map->staged, m->stream));
+  return ORBFE_OK;
+}
+
+int orbfe_project_local_map(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
+                            float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp, uint8_t* in_view,
+                            float* proj_xy, int32_t* level, float* view_cos, int* n_in_view) {
+  CallArea A;
+  int rc = prepare(m, f, map, cam, rows, flags, n_mp, &A);
+  if (rc) return rc;
+  if (n_in_view) *n_in_view = 0;
+  if (n_mp == 0) return ORBFE_OK;
+  ProjParams P = params(f, map, cam, view_cos_limit, n_mp, A);
+  P.inView = A.inView; P.xy = A.xy; P.level = A.level; P.vcos = A.vcos;
+  hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  copy_out(A, n_mp, in_view, proj_xy, level, view_cos);
+  if (n_in_view) *n_in_view = cnt;
+  return ORBFE_OK;
+}
+
+int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
+                                    float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp,
+                                    const float* scale_factors, int nlevels, const uint8_t* kp_occupied, float th, float nnratio,
+                                    uint8_t* in_view, float* proj_xy, int32_t* level, float* view_cos, int32_t* kp_assigned,
+                                    int* nmatches, int* n_in_view) {
+  if (!nmatches || !n_in_view || !scale_factors || nlevels < 1 || nlevels > 32) {
+    set_err("bad argument (scale factors of 1..32 levels, nmatches and n_in_view are required)");
+    return ORBFE_ERR_INVALID;
+  }
+  CallArea A;
+  int rc = prepare(m, f, map, cam, rows, flags, n_mp, &A);
+  if (rc) return rc;
+  const int n = orbfe_frame_size(f);
+  if (n && (!kp_occupied || !kp_assigned)) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  *nmatches = 0;
+  *n_in_view = 0;
+  if (n_mp == 0) {
+    for (int i = 0; i < n; i++) kp_assigned[i] = -1;
+    return ORBFE_OK;
+  }
+  const size_t c = (size_t)n_mp;
+  const size_t oXY = 0, oL = al(8 * c), oV = oL + al(4 * c), oF = oV + al(4 * c), oR = oF + al(c), total = oR + al(4 * c);
+  if ((rc = map->q.ensure(total))) return rc;
+  uint8_t* D = map->q.p;
+  ProjParams P = params(f, map, cam, view_cos_limit, n_mp, A);
+  if (in_view) P.inView = A.inView;
+  if (proj_xy) P.xy = A.xy;
+  if (level) P.level = A.level;
+  if (view_cos) P.vcos = A.vcos;
+  P.nlevels = nlevels;
+  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.dvcos = (float*)(D + oV); P.dflags = D + oF; P.drow = (int32_t*)(D + oR);
+  hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
+  if ((rc = orbfe::sbp_frame_device_queries(m, f, scale_factors, nlevels, kp_occupied, P.dxy, P.dlevel, P.dvcos, P.dflags,
+                                            map->table.p + 32, P.drow, n_mp, th, nnratio, kp_assigned, nmatches))) {
+    (void)hipStreamSynchronize(m->stream);
+    return rc;
+  }
+  if (n == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  *n_in_view = cnt;
+  copy_out(A, n_mp, in_view, proj_xy, level, view_cos);
+  if (bad >= 0) {
+    *nmatches = 0;
+    set_err("MapPoint %d: predicted level outside [0, %d)", bad, nlevels);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+int orbfe_debug_logf(orbfe_matcher* m, const float* x, int n, float* out) {
+  if (!m || n < 0 || (n && (!x || !out))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (n == 0) return ORBFE_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  float* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, 2 * sizeof(float) * (size_t)n));
+  hipError_t e = hipMemcpyAsync(d, x, sizeof(float) * n, hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_logf, dim3((n + 255) / 256), dim3(256), 0, m->stream, (const float*)d, n, d + n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d + n, sizeof(float) * n, hipMemcpyDeviceToHost, m->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  (void)hipFree(d);
+  HIP_TRY(e);
+  return ORBFE_OK;
+}
+
+int orbfe_debug_logf_host_check(uint32_t lo_bits, uint32_t hi_bits, uint32_t step, long long* mismatches) {
+  if (!mismatches || step == 0) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  long long bad = 0;
+  for (uint64_t u = lo_bits; u <= hi_bits; u += step) {
+    const uint32_t b = (uint32_t)u;
+    float f;
+    memcpy(&f, &b, 4);
+    volatile float vf = f;
+    const float r = orbfe::logf_glibc(f), r0 = logf(vf);
+    if (memcmp(&r, &r0, 4) && !(r != r && r0 != r0)) bad++;   // (NaN results compare as equal whatever their payload)
+  }
+  *mismatches = bad;
+  return ORBFE_OK;
+}
+
+}  // extern "C"
