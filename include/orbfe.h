@@ -257,12 +257,14 @@ int orbfe_debug_logf_host_check(uint32_t lo_bits, uint32_t hi_bits, uint32_t ste
 /* ---------------------------------------------------------------------------------------------
  * Stream runner (throughput path; no counterpart class in the reference, whose Tracking thread drives
  * ORBextractor / ORBmatcher one frame at a time -- System.cc:115-152, Tracking.cc:92-121,344-419).
- * A stream owns `depth` extractor handles + one matcher on one GPU and two native worker threads:
+ * A stream owns `depth` extractor handles on one GPU and one native worker thread, the extract worker:
  * batches pushed with orbfe_stream_push are extracted (asynchronous submit/collect, `depth` batches in
  * flight) and every frame is matched against its predecessor in the stream with
- * SearchForInitialization (vbPrevMatched := predecessor keypoints, as Tracking.cc:355-357); results come
- * back in push order from orbfe_stream_pop.  Identical results to calling orbfe_extract_batch and
- * orbfe_search_for_initialization frame by frame.
+ * SearchForInitialization (vbPrevMatched := predecessor keypoints, as Tracking.cc:355-357), chained
+ * behind the extraction on the GPU; results come back in push order from orbfe_stream_pop.  A frame 0
+ * whose predecessor that chain does not hold is matched with orbfe_search_for_initialization on a
+ * matcher the stream creates when it first needs one.  Identical results to calling orbfe_extract_batch
+ * and orbfe_search_for_initialization frame by frame.
  * ------------------------------------------------------------------------------------------- */
 typedef struct orbfe_stream orbfe_stream;
 /* PREDECESSOR CONTRACT (orbfe_stream_* and orbfe_stream_multi_*).  Frame 0 of a batch is matched against the last frame pushed before
@@ -331,8 +333,9 @@ int orbfe_stream_push(orbfe_stream* s, const uint8_t* const* gray, int in_device
  *   nmatches [batch]: return values of the searches (0 for the very first frame of the stream). */
 int orbfe_stream_pop(orbfe_stream* s, const OrbfeKeyPoint** kps, const uint8_t** desc, const int** n_kps,
                      const int32_t** matches12, const int** nmatches);
-/* Host wall-clock ms the workers spent in submit / collect (incl. waiting for the GPU) / match calls, and the
- * number of finished batches, since the last reset: out = {submit, collect, match, batches}. */
+/* Host wall-clock ms the extract worker spent in submit / collect calls (incl. waiting for the GPU), and the number of
+ * finished batches, since the last reset: out = {submit, collect, match, batches}.  Matching runs inside submit / collect,
+ * so out[2] is always 0 (the slot is kept for ABI compatibility). */
 int orbfe_stream_stats(orbfe_stream* s, double out[4], int reset);
 /* Sum of orbfe_debug_kernel_ms over the stream's extractor handles. */
 int orbfe_stream_kernel_ms(orbfe_stream* s, double out_ms[5], long long* batches, long long* frames, int reset);
@@ -506,9 +509,8 @@ const uint8_t* orbfe_frame_descriptors_device(orbfe_frame* f);
 int orbfe_frame_download(orbfe_frame* f, OrbfeKeyPoint* kps_un, uint8_t* desc, int32_t* grid_order, int32_t* cell_start);
 
 /* orbfe_search_by_projection / _uv / orbfe_search_projected on a resident frame: same arguments minus the frame's
- * arrays, same results.  (The host-array forms above run through these with a transient frame owned by the matcher;
- * ORBFE_MATCH_HOST_RESOLVE=1 keeps their round-2 route -- candidate lists to the host, bookkeeping there -- for A/B
- * runs and the parity tests.)  WHERE THE INPUT ARRAYS MAY LIVE: the DESCRIPTOR ROWS may lie in ordinary host memory,
+ * arrays, same results.  (The host-array forms above run through these with a transient frame owned by the matcher.)
+ * WHERE THE INPUT ARRAYS MAY LIVE: the DESCRIPTOR ROWS may lie in ordinary host memory,
  * in page-locked host memory (orbfe_host_alloc) or in the memory of the frame's device (16-byte aligned there, e.g.
  * orbfe_frame_descriptors_device, or a table the caller maintains with orbfe_matcher_upload_async); page-locked and
  * device rows are read by the search kernel in place.  EVERY OTHER per-query array (coordinates, levels, viewing cosines /

@@ -1233,7 +1233,8 @@ class Stream:
         _check(self.L.orbfe_stream_set_isolated_batches(self.h, int(on)))
 
     def stats(self, reset=False):
-        """{submit, collect, match} worker busy ms and batches done since the last reset."""
+        """[submit ms, collect ms, match ms, batches done] since the last reset: the extract worker's busy time in submit and in
+        collect (incl. waiting for the GPU).  Matching runs inside those calls, so the match slot is always 0."""
         out = np.zeros(4, np.float64)
         _check(self.L.orbfe_stream_stats(self.h, _p(out), int(reset)))
         return out

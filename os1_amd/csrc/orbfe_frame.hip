@@ -991,13 +991,6 @@ int scratch_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps, const uint8_t* des
 
 }  // namespace
 
-namespace orbfe {
-bool match_host_resolve() {   // ORBFE_MATCH_HOST_RESOLVE=1: the host-array searches keep the round-2 route (candidate lists to the host, bookkeeping there)
-  const char* e = getenv("ORBFE_MATCH_HOST_RESOLVE");   // read per call: the parity tests run both routes in one process
-  return e && atoi(e) != 0;
-}
-}  // namespace orbfe
-
 extern "C" {
 
 int orbfe_frame_create(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n, const float bounds[4],

@@ -14,13 +14,13 @@
 // (vMatchedDistance / vnMatches21, F.mvpMapPoints occupancy).  The data-parallel part -- window
 // test, level filter and Hamming distance for every (query, candidate) pair, emitted in exactly
 // the order Frame::GetFeaturesInArea would return them -- is one kernel (one wave per query,
-// ballot-ordered compaction).  The order-dependent bookkeeping is replayed on the host over those
-// short candidate lists, statement for statement.
+// ballot-ordered compaction).  SearchForInitialization's order-dependent bookkeeping is replayed on
+// the host over those short candidate lists, statement for statement; the SearchByProjection family
+// runs on a transient resident frame with its bookkeeping on the GPU (orbfe_frame.hip).
 #include "orbfe_matcher_internal.h"
 
 namespace orbfe {
 // orbfe_frame.hip: the host-array searches run on a transient device-resident frame + GPU-side bookkeeping
-bool match_host_resolve();
 int sbp_via_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n, const float bounds[4],
                   const float* scale_factors, int nlevels, const uint8_t* kp_occupied, const float* mp_proj_xy,
                   const int32_t* mp_level, const float* mp_viewcos, const uint8_t* mp_flags, const uint8_t* mp_desc, int n_mp,
@@ -446,59 +446,8 @@ int orbfe_search_by_projection(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, co
     set_err("bad argument (note: at most 65535 keypoints per frame)");
     return ORBFE_ERR_INVALID;
   }
-  if (!orbfe::match_host_resolve())
-    return orbfe::sbp_via_frame(m, kps_un, desc, n, bounds, scale_factors, nlevels, kp_occupied, mp_proj_xy, mp_level, mp_viewcos,
-                                mp_flags, mp_desc, n_mp, th, nnratio, kp_assigned, nmatches);
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_mp == 0 || n == 0) return ORBFE_OK;
-  const bool bFactor = th != 1.0;
-  std::vector<float> qr(n_mp);
-  std::vector<float> qx(n_mp), qy(n_mp);
-  std::vector<int> qa(n_mp), qb(n_mp);
-  for (int i = 0; i < n_mp; i++) {
-    const uint8_t fl = mp_flags[i];
-    qx[i] = mp_proj_xy[2 * i];
-    qy[i] = mp_proj_xy[2 * i + 1];
-    const int lvl = mp_level[i];
-    qa[i] = lvl - 1;
-    qb[i] = lvl;
-    if (!(fl & ORBFE_MP_IN_VIEW) || (fl & ORBFE_MP_BAD)) { qr[i] = -1.f; continue; }
-    if (lvl < 0 || lvl >= nlevels) { set_err("MapPoint %d: level %d out of range", i, lvl); return ORBFE_ERR_INVALID; }
-    float r = (fl & ORBFE_MP_CANDIDATO) ? 4.0 : (mp_viewcos[i] > 0.998 ? 2.5 : 4.0);  // ORBmatcher.cc:63-65,126-132
-    if (bFactor) r *= th;
-    qr[i] = r * scale_factors[lvl];
-  }
-  int rc = m->candidates(kps_un, desc, n, bounds, qx.data(), qy.data(), qr.data(), qa.data(), qb.data(), mp_desc, n_mp);
-  if (rc) return rc;
-  const uint32_t* pool = m->h_pool.p;
-  std::vector<uint8_t> occ(kp_occupied, kp_occupied + n);
-  int nm = 0;
-  for (int iMP = 0; iMP < n_mp; iMP++) {
-    if (qr[iMP] < 0.f) continue;
-    const uint32_t cnt = m->qcount[iMP];
-    if (cnt == 0) continue;
-    const uint32_t* cl = pool + m->qoff[iMP];
-    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-    for (uint32_t c = 0; c < cnt; c++) {
-      const int idx = (int)(cl[c] & 0xffff), dist = (int)(cl[c] >> 16);
-      if (occ[idx]) continue;
-      if (dist < bestDist) {
-        bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel;
-        bestLevel = kps_un[idx].octave; bestIdx = idx;
-      } else if (dist < bestDist2) {
-        bestLevel2 = kps_un[idx].octave; bestDist2 = dist;
-      }
-    }
-    if (bestDist <= TH_HIGH) {
-      if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-      kp_assigned[bestIdx] = iMP;
-      occ[bestIdx] = (mp_flags[iMP] & ORBFE_MP_OBSERVED) ? 1 : 0;
-      nm++;
-    }
-  }
-  *nmatches = nm;
-  return ORBFE_OK;
+  return orbfe::sbp_via_frame(m, kps_un, desc, n, bounds, scale_factors, nlevels, kp_occupied, mp_proj_xy, mp_level, mp_viewcos,
+                              mp_flags, mp_desc, n_mp, th, nnratio, kp_assigned, nmatches);
 }
 
 int orbfe_search_by_projection_uv(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n,
@@ -513,63 +462,9 @@ int orbfe_search_by_projection_uv(orbfe_matcher* m, const OrbfeKeyPoint* kps_un,
     set_err("bad argument (note: at most 65535 keypoints per frame)");
     return ORBFE_ERR_INVALID;
   }
-  if (!orbfe::match_host_resolve())
-    return orbfe::sbp_uv_via_frame(m, kps_un, desc, n, bounds, scale_factors, nlevels, kp_occupied, src_uv, src_level, src_angle,
-                                   src_flags, src_valid, src_desc, n_src, th, max_dist, skip_any_occupied, check_orientation,
-                                   kp_assigned, nmatches);
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_src == 0 || n == 0) return ORBFE_OK;
-  std::vector<float> qx(n_src), qy(n_src), qr(n_src);
-  std::vector<int> qa(n_src), qb(n_src);
-  for (int i = 0; i < n_src; i++) {
-    qx[i] = src_uv[2 * i];
-    qy[i] = src_uv[2 * i + 1];
-    const int lvl = src_level[i];
-    qa[i] = lvl - 1;
-    qb[i] = lvl + 1;
-    if (!src_valid[i]) { qr[i] = -1.f; continue; }
-    if (lvl < 0 || lvl >= nlevels) { set_err("source %d: level %d out of range", i, lvl); return ORBFE_ERR_INVALID; }
-    qr[i] = th * scale_factors[lvl];
-  }
-  int rc = m->candidates(kps_un, desc, n, bounds, qx.data(), qy.data(), qr.data(), qa.data(), qb.data(), src_desc, n_src);
-  if (rc) return rc;
-  const uint32_t* pool = m->h_pool.p;
-  std::vector<uint8_t> occ(kp_occupied, kp_occupied + n);
-  std::vector<int> rotHist[HISTO_LENGTH];
-  int nm = 0;
-  for (int i = 0; i < n_src; i++) {
-    if (qr[i] < 0.f) continue;
-    const uint32_t cnt = m->qcount[i];
-    if (cnt == 0) continue;
-    const uint32_t* cl = pool + m->qoff[i];
-    int bestDist = 256, bestIdx2 = -1;
-    for (uint32_t c = 0; c < cnt; c++) {
-      const int i2 = (int)(cl[c] & 0xffff), dist = (int)(cl[c] >> 16);
-      if (occ[i2]) continue;
-      if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-    }
-    if (bestDist <= max_dist) {
-      kp_assigned[bestIdx2] = i;
-      occ[bestIdx2] = skip_any_occupied ? 1 : ((src_flags[i] & ORBFE_MP_OBSERVED) ? 1 : 0);
-      nm++;
-      if (check_orientation) rotHist[rotBin(src_angle[i], kps_un[bestIdx2].angle)].push_back(bestIdx2);
-    }
-  }
-  if (check_orientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    computeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i != ind1 && i != ind2 && i != ind3) {
-        for (int idx : rotHist[i]) {
-          kp_assigned[idx] = -2;
-          nm--;
-        }
-      }
-    }
-  }
-  *nmatches = nm;
-  return ORBFE_OK;
+  return orbfe::sbp_uv_via_frame(m, kps_un, desc, n, bounds, scale_factors, nlevels, kp_occupied, src_uv, src_level, src_angle,
+                                 src_flags, src_valid, src_desc, n_src, th, max_dist, skip_any_occupied, check_orientation,
+                                 kp_assigned, nmatches);
 }
 
 // The projected best-match loop of SearchByProjection(KeyFrame*, Scw, ...) (ORBmatcher.cc:357-392), Fuse x2
@@ -593,51 +488,8 @@ int orbfe_search_projected(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const 
   if (inv_level_sigma2)
     for (int i = 0; i < n; i++)
       if (kps_un[i].octave < 0 || kps_un[i].octave >= nlevels) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
-  if (!orbfe::match_host_resolve())
-    return orbfe::projected_via_frame(m, kps_un, desc, n, bounds, n_src, src_uv, src_radius, src_level, src_valid, src_desc, kp_skip,
-                                      claim, inv_level_sigma2, nlevels, chi2, max_dist, best_idx, best_dist, nmatches);
-  std::vector<float> qx(n_src), qy(n_src), qr(n_src);
-  std::vector<int> qa(n_src), qb(n_src);
-  for (int i = 0; i < n_src; i++) {
-    qx[i] = src_uv[2 * i];
-    qy[i] = src_uv[2 * i + 1];
-    qa[i] = src_level[i] - 1;                      // kpLevel < nPredictedLevel-1 || kpLevel > nPredictedLevel => skip
-    qb[i] = src_level[i];
-    qr[i] = (src_valid[i] && src_level[i] >= 0) ? src_radius[i] : -1.f;   // no octave lies in [level-1, level] for level < 0
-  }
-  int rc = m->candidates(kps_un, desc, n, bounds, qx.data(), qy.data(), qr.data(), qa.data(), qb.data(), src_desc, n_src);
-  if (rc) return rc;
-  const uint32_t* pool = m->h_pool.p;
-  std::vector<uint8_t> occ(n, 0);
-  if (kp_skip) occ.assign(kp_skip, kp_skip + n);
-  const bool useOcc = kp_skip || claim;
-  int nm = 0;
-  for (int i = 0; i < n_src; i++) {
-    if (qr[i] < 0.f) continue;
-    const uint32_t cnt = m->qcount[i];
-    const uint32_t* cl = pool + m->qoff[i];
-    const float u = qx[i], v = qy[i];
-    int bestDist = INT_MAX, bestIdx = -1;
-    for (uint32_t c = 0; c < cnt; c++) {
-      const int idx = (int)(cl[c] & 0xffff), dist = (int)(cl[c] >> 16);
-      if (useOcc && occ[idx]) continue;
-      if (inv_level_sigma2) {   // ORBmatcher.cc:896-903
-        const float ex = u - kps_un[idx].x;
-        const float ey = v - kps_un[idx].y;
-        const float e2 = ex * ex + ey * ey;
-        if (e2 * inv_level_sigma2[kps_un[idx].octave] > chi2) continue;
-      }
-      if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-    }
-    if (bestDist <= max_dist) {
-      best_idx[i] = bestIdx;
-      if (best_dist) best_dist[i] = bestDist;
-      if (claim) occ[bestIdx] = 1;
-      nm++;
-    }
-  }
-  *nmatches = nm;
-  return ORBFE_OK;
+  return orbfe::projected_via_frame(m, kps_un, desc, n, bounds, n_src, src_uv, src_radius, src_level, src_valid, src_desc, kp_skip,
+                                    claim, inv_level_sigma2, nlevels, chi2, max_dist, best_idx, best_dist, nmatches);
 }
 
 }  // extern "C"

@@ -163,131 +163,7 @@ __device__ __forceinline__ int sfi_rot_bin(float a1, float a2) {   // ORBmatcher
   return bin;
 }
 
-__global__ __launch_bounds__(64) void k_sfi_resolve_seq(SfiParams S) {
-  extern __shared__ int sm[];
-  const int fr = blockIdx.x, lane = threadIdx.x;
-  const int f = S.frameBase + fr;
-  const SfiFrame F2 = sfi_frame(S, f);
-  const SfiFrame F1 = sfi_frame(S, fr == 0 ? -1 : f - 1);
-  int32_t* out = S.matches12 + (long long)f * S.n0cap;
-  if (F1.n < 0) {   // no predecessor: first frame of the stream
-    for (int i = lane; i < S.n0cap; i += 64) out[i] = -1;
-    if (lane == 0) S.nmatches[f] = 0;
-    return;
-  }
-  const int n1 = F1.n, n2 = F2.n, cap = S.n0cap;
-  int* vMatchedDistance = sm;            // [cap]
-  int* vnMatches21 = sm + cap;           // [cap]
-  int* vnMatches12 = sm + 2 * cap;       // [cap]
-  int* binOf = sm + 3 * cap;             // [cap] rotation bin of a pushed query, -1 = never pushed
-  int* pcnt = sm + 4 * cap;              // [cap] candidate counts of the queries
-  int* hist = sm + 5 * cap;              // [32]
-  for (int i = lane; i < cap; i += 64) {
-    vMatchedDistance[i] = 0x7fffffff;
-    vnMatches21[i] = -1;
-    vnMatches12[i] = -1;
-    binOf[i] = -1;
-    pcnt[i] = i < n1 ? (int)S.pcount[(long long)f * cap + i] : 0;
-  }
-  if (lane < 32) hist[lane] = 0;
-  __syncthreads();
-  const uint32_t* pool = S.pool + (long long)f * cap * cap;
-  int nm = 0;
-  // software pipeline: the first chunk of query i1+1 is fetched while query i1 is resolved
-  uint32_t nextEntry = 0;
-  if (n1 > 0 && lane < pcnt[0]) nextEntry = pool[lane];
-  for (int i1 = 0; i1 < n1; i1++) {
-    const int cnt = pcnt[i1];
-    uint32_t entry = nextEntry;
-    if (i1 + 1 < n1 && lane < pcnt[i1 + 1]) nextEntry = pool[(long long)(i1 + 1) * cap + lane];
-    if (cnt == 0) continue;
-    int bestDist = 0x7fffffff, bestDist2 = 0x7fffffff, bestIdx2 = -1;
-    for (int c0 = 0; c0 < cnt; c0 += 64) {
-      if (c0 > 0) entry = (c0 + lane < cnt) ? pool[(long long)i1 * cap + c0 + lane] : 0u;
-      int d = 0x7fffffff, i2 = -1;
-      if (c0 + lane < cnt) {
-        i2 = (int)(entry & 0xffff);
-        const int dist = (int)(entry >> 16);
-        if (!(vMatchedDistance[i2] <= dist)) d = dist;   // :439 candidate owned by an equal-or-better match
-      }
-      // Chunk minimum / second minimum by bitwise bisection with ballots (distances fit 9 bits; 511 = skipped):
-      // after the loop `c1` holds exactly the lanes with the smallest distance; its lowest lane is the first
-      // position (candidate order = lane order).  Scalar mask arithmetic instead of 19 dependent cross-lane
-      // permutes per query.
-      const unsigned dd = (d == 0x7fffffff) ? 511u : (unsigned)d;
-      unsigned long long c1 = ~0ull;
-#pragma unroll
-      for (int b = 8; b >= 0; b--) {
-        const unsigned long long z = __ballot(((dd >> b) & 1u) == 0u) & c1;
-        if (z) c1 = z;
-      }
-      const int ml = (int)__builtin_ctzll(c1);
-      const unsigned d1 = (unsigned)__shfl((int)dd, ml, 64);
-      unsigned long long c2 = ~(1ull << ml);   // everyone but the winner
-#pragma unroll
-      for (int b = 8; b >= 0; b--) {
-        const unsigned long long z = __ballot(((dd >> b) & 1u) == 0u) & c2;
-        if (z) c2 = z;
-      }
-      const unsigned d2 = (unsigned)__shfl((int)dd, (int)__builtin_ctzll(c2), 64);
-      const int md = d1 >= 511u ? 0x7fffffff : (int)d1;
-      const int sd = d2 >= 511u ? 0x7fffffff : (int)d2;
-      const int mi2 = __shfl(i2, ml, 64);
-      // merge with the running (best, second) -- sequential semantics of :441-450, earlier chunk wins ties
-      if (md < bestDist) {
-        bestDist2 = min(bestDist, sd);
-        bestDist = md;
-        bestIdx2 = mi2;
-      } else {
-        bestDist2 = min(bestDist2, md);
-      }
-    }
-    if (bestDist <= kSfiThLow && (float)bestDist < (float)bestDist2 * S.nnratio) {
-      if (lane == 0) {
-        const int old = vnMatches21[bestIdx2];
-        if (old >= 0) vnMatches12[old] = -1;
-        vnMatches12[i1] = bestIdx2;
-        vnMatches21[bestIdx2] = i1;
-        vMatchedDistance[bestIdx2] = bestDist;
-        if (S.checkOri) {
-          const int bin = sfi_rot_bin(F1.angle[i1], F2.angle[bestIdx2]);
-          binOf[i1] = bin;
-          hist[bin]++;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  if (S.checkOri) {
-    // ComputeThreeMaxima, ORBmatcher.cc:1554-1595 (every lane evaluates it identically)
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kSfiHisto; i++) {
-      const int s = hist[i];
-      if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-      else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-      else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-    for (int i = lane; i < n1; i += 64) {
-      const int b = binOf[i];
-      if (b >= 0 && b != ind1 && b != ind2 && b != ind3 && vnMatches12[i] >= 0) vnMatches12[i] = -1;
-    }
-    __syncthreads();
-  }
-  for (int i = lane; i < cap; i += 64) {
-    const int v = i < n1 ? vnMatches12[i] : -1;
-    out[i] = v;
-    nm += v >= 0;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nm += __shfl_xor(nm, o, 64);
-  if (lane == 0) S.nmatches[f] = nm;
-  (void)n2;
-}
-
-// The same bookkeeping without the serial walk.  Query i1's outcome (its accepted match, or none) is a function of
+// The reference's bookkeeping without its serial walk.  Query i1's outcome (its accepted match, or none) is a function of
 // its own candidate list and of vMatchedDistance at the moment the reference reaches i1, and vMatchedDistance[i2] at
 // that moment is the smallest distance among the matches accepted for i2 by queries j < i1 (:439, :455-466: every
 // accepted match lowers it).  So the vector of outcomes M satisfies M[i1] = g(i1, {M[j] : j < i1}); that recurrence
@@ -574,11 +450,6 @@ void launch_sfi(const SfiParams& S, int nframes, hipStream_t st) {
   sfi_debug_setup();
   hipLaunchKernelGGL(k_sfi_sort, dim3(nframes), dim3(256), sizeof(int) * 3 * S.n0cap, st, S);
   hipLaunchKernelGGL(k_sfi_candidates, dim3(S.n0cap, nframes), dim3(64), 0, st, S);
-  const bool seq = getenv("ORBFE_SFI_SEQUENTIAL") != nullptr;   // the serial replay, kept for A/B runs and tests
-  if (seq) {
-    hipLaunchKernelGGL(k_sfi_resolve_seq, dim3(nframes), dim3(64), sizeof(int) * (5 * S.n0cap + 32), st, S);
-    return;
-  }
   const int fixedWords = 6 * S.n0cap + 1 + 32 + 2;
   int ldsPool = (60 * 1024 / 4) - fixedWords;   // candidate entries kept in LDS; longer pools are read from HBM
   if (ldsPool > 8192) ldsPool = 8192;

@@ -4,14 +4,15 @@
 // time (System::TrackMonocular -> Frame::Frame -> ORBextractor, then ORBmatcher).
 // For throughput over a stream (BASELINE.json config 4: independent streams, one per GPU) this
 // runner keeps the GPU fed without any per-frame host orchestration in the caller's language:
-//   push(batch of frames)  ->  [extract thread]  async submit on one of `depth` extractor handles,
+//   push(batch of frames)  ->  [extract thread]  async submit on one of `depth` extractor handles, with
+//                              SearchForInitialization of every frame against its predecessor in the
+//                              stream chained behind the extraction on the GPU (orbfe_sfi_chain);
 //                              collect in order
-//                          ->  [match thread]    SearchForInitialization of every frame against its
-//                              predecessor in the stream (one batched GPU submission)
 //   pop()                  ->  results of the oldest finished batch, in push order.
-// Everything the GPU computes goes through the same entry points a single-frame caller uses
-// (orbfe_extract_batch_submit/_collect, orbfe_search_for_initialization_batch), so results are
-// identical to calling those one by one.
+// Everything the GPU computes goes through the extractor / matcher C ABI
+// (orbfe_extract_batch_submit_matched/_collect_matched, orbfe_search_for_initialization for a frame 0
+// whose predecessor the chain does not hold), so results are identical to calling orbfe_extract_batch
+// and orbfe_search_for_initialization frame by frame.
 #include <pthread.h>
 
 #include <algorithm>
@@ -45,7 +46,7 @@ struct Slot {
   std::vector<int> n;
   std::vector<int32_t> m12;
   std::vector<int> nm;
-  std::vector<float> prevxy;
+  std::vector<float> prevxy;   // [cap][2] query centres of row 0 (matchFrame0)
   std::vector<uint32_t> bowLeaf, bowNode;   // [batch][cap], with a vocabulary set
   // predecessor of frame 0 (last frame of the previous batch), copied at collect time
   std::vector<OrbfeKeyPoint> prevKps;
@@ -54,7 +55,7 @@ struct Slot {
   long long seq = 0;
   bool done = false;
   bool held = false;        // handed out by orbfe_stream_pop_hold and not released yet
-  bool frame0OnHost = false;   // GPU matching path: the chain does not hold frame 0's predecessor, the runner matches it on the host
+  bool frame0OnHost = false;   // the chain does not hold frame 0's predecessor: the runner matches it on the host (matchFrame0)
   int status = ORBFE_OK;
   std::string err;
   // match parameters of the stream at push time (orbfe_stream_set_matching only works on an idle stream, but the
@@ -72,11 +73,9 @@ struct orbfe_stream {
   float nnratio = 0.9f;
   float bounds[4] = {0, 0, 0, 0};
   std::vector<orbfe_extractor*> ext;
-  std::vector<orbfe_matcher*> matchers;   // one per match worker (host-side matching path)
-  orbfe_sfi_chain* chain = nullptr;       // GPU-resident matching path (default)
-  orbfe_matcher* frame0Matcher = nullptr; // GPU path: frame 0 of a batch whose predecessor the chain does not hold (created when first needed)
+  orbfe_sfi_chain* chain = nullptr;       // GPU-resident matching
+  orbfe_matcher* frame0Matcher = nullptr; // frame 0 of a batch whose predecessor the chain does not hold (created when first needed)
   int chainRows = 0, chainCols = 0;       // geometry of the previous batch if the chain matched it (its last frame is the chain's carry), else 0
-  bool gpuMatch = true;
   bool isolated = false;                  // orbfe_stream_set_isolated_batches: frame 0 of a batch has no predecessor
   std::vector<Slot> slots;
   void growSlots(int nslots) {     // caller holds no batch in flight (or is the constructor)
@@ -91,14 +90,14 @@ struct orbfe_stream {
       sl.n.assign(batch, 0);
       sl.m12.assign((size_t)batch * cap, -1);
       sl.nm.assign(batch, 0);
-      sl.prevxy.resize((size_t)batch * cap * 2);
+      sl.prevxy.resize((size_t)cap * 2);
       freeQ.push_back(i);
     }
   }
 
   std::mutex mu;
   std::condition_variable cv;
-  std::deque<int> freeQ, extractQ, matchQ, doneQ;
+  std::deque<int> freeQ, extractQ;
   int popped = -1;  // slot handed to the caller by the last pop (returned to freeQ on the next pop)
   int nHeld = 0;     // slots handed out by orbfe_stream_pop_hold and not released
   bool idle() const { return pushSeq == popSeq && nHeld == 0; }   // (caller holds mu)
@@ -115,13 +114,12 @@ struct orbfe_stream {
       sl.kps.resize((size_t)batch * need);
       sl.desc.resize((size_t)batch * need * 32);
       sl.m12.assign((size_t)batch * need, -1);
-      sl.prevxy.resize((size_t)batch * need * 2);
+      sl.prevxy.resize((size_t)need * 2);
     }
     return ORBFE_OK;
   }
   bool stop = false;
   std::thread tExtract;
-  std::vector<std::thread> tMatch;
   long long pushSeq = 0, popSeq = 0;
   int channels = 1;   // bytes per pixel of the pushed frames (orbfe_stream_set_input_format)
   bool bow = false;   // orbfe_stream_set_vocabulary
@@ -131,14 +129,14 @@ struct orbfe_stream {
   std::vector<uint8_t> lastDesc;
   int lastN = -1;
 
-  // busy time of the two workers (ms) and batches done, for orbfe_stream_stats
-  double busySubmit = 0, busyCollect = 0, busyMatch = 0;
+  // busy time of the extract worker (ms) and batches done, for orbfe_stream_stats
+  double busySubmit = 0, busyCollect = 0;
   long long nBatches = 0;
   static double nowMs() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   }
 
-  // GPU matching path, frame 0 of a batch whose predecessor (the last frame of the batch before, s.prevKps) the chain does not hold:
+  // frame 0 of a batch whose predecessor (the last frame of the batch before, s.prevKps) the chain does not hold:
   // the host-array search (the same kernels), row 0 overwritten
   int matchFrame0(Slot& s) {
     if (!frame0Matcher) {
@@ -174,7 +172,7 @@ struct orbfe_stream {
         Slot& s = slots[job];
         orbfe_extractor* h = ext[nextExt];
         const double ta = nowMs();
-        if (gpuMatch && s.window > 0) {
+        if (s.window > 0) {
           // the chain's carry is frame 0's predecessor only if the chain matched the batch before, on the same geometry (so the same
           // route: the GPU and the host quadtree route keep a carry each); otherwise frame 0 is matched on the host at collect time
           s.frame0OnHost = s.rows != chainRows || s.cols != chainCols;
@@ -202,7 +200,7 @@ struct orbfe_stream {
       Slot& s = slots[slot];
       if (s.status == ORBFE_OK) {
         const double ta = nowMs();
-        if (gpuMatch && s.window > 0)
+        if (s.window > 0)
           s.status = orbfe_extract_batch_collect_matched(ext[e], s.kps.data(), s.desc.data(), cap, s.n.data(), s.m12.data(),
                                                          s.nm.data());
         else
@@ -227,7 +225,7 @@ struct orbfe_stream {
         if (s.window <= 0) {   // extraction only: no matches
           std::fill(s.nm.begin(), s.nm.end(), 0);
           std::fill(s.m12.begin(), s.m12.end(), -1);
-        } else if (gpuMatch && s.frame0OnHost && s.prevN >= 0) {
+        } else if (s.frame0OnHost && s.prevN >= 0) {
           s.status = matchFrame0(s);
           if (s.status != ORBFE_OK) s.err = orbfe_last_error();
         }
@@ -236,83 +234,7 @@ struct orbfe_stream {
         lastDesc.assign(s.desc.begin() + (size_t)(batch - 1) * cap * 32, s.desc.begin() + ((size_t)(batch - 1) * cap + lastN) * 32);
       }
       {
-        std::lock_guard<std::mutex> lk(mu);
-        if (gpuMatch || s.window <= 0) {   // matches (if any) came back with the batch: done
-          nBatches++;
-          s.done = true;
-        } else {
-          matchQ.push_back(slot);
-        }
-      }
-      cv.notify_all();
-    }
-  }
-
-  void matchLoop(int worker) {
-    orbfe_matcher* matcher = matchers[worker];
-    std::vector<const OrbfeKeyPoint*> k1, k2;
-    std::vector<const uint8_t*> d1, d2;
-    std::vector<int> n1, n2;
-    std::vector<float*> prev;
-    std::vector<int32_t*> m12;
-    std::vector<int> nm;
-    for (;;) {
-      int slot = -1;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || !matchQ.empty(); });
-        if (matchQ.empty()) {
-          if (stop) return;
-          continue;
-        }
-        slot = matchQ.front();
-        matchQ.pop_front();
-      }
-      Slot& s = slots[slot];
-      const double tm0 = nowMs();
-      if (s.status == ORBFE_OK && s.window > 0 && !gpuMatch) {
-        const int window = s.window, checkOri = s.checkOri;
-        const float nnratio = s.nnratio;
-        const float* bounds = s.bounds;
-        // pairs (predecessor, frame): Tracking::MonocularInitialization style, vbPrevMatched := F1 keypoints
-        k1.clear(); k2.clear(); d1.clear(); d2.clear(); n1.clear(); n2.clear(); prev.clear(); m12.clear();
-        std::vector<int> frameOfPair;
-        for (int i = 0; i < batch; i++) {
-          const OrbfeKeyPoint* pk;
-          const uint8_t* pd;
-          int pn;
-          if (i == 0) {
-            if (s.prevN < 0) {  // very first frame of the stream: no predecessor
-              s.nm[0] = 0;
-              std::fill(s.m12.begin(), s.m12.begin() + cap, -1);
-              continue;
-            }
-            pk = s.prevKps.data(); pd = s.prevDesc.data(); pn = s.prevN;
-          } else {
-            pk = s.kps.data() + (size_t)(i - 1) * cap; pd = s.desc.data() + (size_t)(i - 1) * cap * 32; pn = s.n[i - 1];
-          }
-          std::fill(s.m12.begin() + (size_t)i * cap + pn, s.m12.begin() + (size_t)(i + 1) * cap, -1);   // (the search writes the first pn)
-          float* pxy = s.prevxy.data() + (size_t)i * cap * 2;
-          for (int j = 0; j < pn; j++) { pxy[2 * j] = pk[j].x; pxy[2 * j + 1] = pk[j].y; }
-          k1.push_back(pk); d1.push_back(pd); n1.push_back(pn);
-          k2.push_back(s.kps.data() + (size_t)i * cap); d2.push_back(s.desc.data() + (size_t)i * cap * 32); n2.push_back(s.n[i]);
-          prev.push_back(pxy);
-          m12.push_back(s.m12.data() + (size_t)i * cap);
-          frameOfPair.push_back(i);
-        }
-        nm.assign(k1.size(), 0);
-        if (!k1.empty()) {
-          s.status = orbfe_search_for_initialization_batch(matcher, (int)k1.size(), k1.data(), d1.data(), n1.data(), k2.data(),
-                                                           d2.data(), n2.data(), bounds, prev.data(), m12.data(), window,
-                                                           nnratio, checkOri, nm.data());
-          if (s.status != ORBFE_OK) s.err = orbfe_last_error();
-          for (size_t p = 0; p < frameOfPair.size(); p++) s.nm[frameOfPair[p]] = nm[p];
-        }
-      }
-      const double tmBusy = nowMs() - tm0;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        busyMatch += tmBusy;
+        std::lock_guard<std::mutex> lk(mu);   // matches (if any) came back with the batch: done
         nBatches++;
         s.done = true;
       }
@@ -344,29 +266,10 @@ int orbfe_stream_create(int nfeatures, float scaleFactor, int nlevels, int iniTh
     }
     s->ext.push_back(h);
   }
-  if (const char* hv = getenv("ORBFE_STREAM_HOST_MATCH")) s->gpuMatch = atoi(hv) == 0;
-  // host-side matching path only: SearchForInitialization workers, each with its own matcher (and HIP stream; streams
-  // are not created unless used, because the runtime folds them onto a handful of hardware queues)
-  int nMatch = 0;
-  if (!s->gpuMatch) {
-    nMatch = 2;
-  }
-  for (int w = 0; w < nMatch; w++) {
-    orbfe_matcher* mm = nullptr;
-    int rc = orbfe_matcher_create(device_id, &mm);
-    if (rc != ORBFE_OK) {
-      for (auto* e : s->ext) orbfe_extractor_destroy(e);
-      for (auto* q : s->matchers) orbfe_matcher_destroy(q);
-      delete s;
-      return rc;
-    }
-    s->matchers.push_back(mm);
-  }
   {
     int rc = orbfe_sfi_chain_create(s->ext[0], &s->chain);
     if (rc != ORBFE_OK) {
       for (auto* e : s->ext) orbfe_extractor_destroy(e);
-      for (auto* q : s->matchers) orbfe_matcher_destroy(q);
       delete s;
       return rc;
     }
@@ -381,7 +284,6 @@ int orbfe_stream_create(int nfeatures, float scaleFactor, int nlevels, int iniTh
     const int k = orbfe_concurrent_streams(s->ext.data(), depth);
     if (k < 0) {
       for (auto* e : s->ext) orbfe_extractor_destroy(e);
-      for (auto* q : s->matchers) orbfe_matcher_destroy(q);
       orbfe_sfi_chain_destroy(s->chain);
       delete s;
       return k;
@@ -406,7 +308,6 @@ int orbfe_stream_create(int nfeatures, float scaleFactor, int nlevels, int iniTh
   // orbfe_stream_set_queue_slots; a slot is host memory only (4 MB at 1080p / 2000 features / 32 frames).
   s->growSlots(depth + 4);
   s->tExtract = std::thread([s] { pthread_setname_np(pthread_self(), "orbfe-runner"); s->extractLoop(); });
-  for (int w = 0; w < nMatch; w++) s->tMatch.emplace_back([s, w] { pthread_setname_np(pthread_self(), "orbfe-match"); s->matchLoop(w); });
   *out = s;
   return ORBFE_OK;
 }
@@ -419,9 +320,7 @@ void orbfe_stream_destroy(orbfe_stream* s) {
   }
   s->cv.notify_all();
   if (s->tExtract.joinable()) s->tExtract.join();
-  for (auto& t : s->tMatch) if (t.joinable()) t.join();
   for (auto* e : s->ext) orbfe_extractor_destroy(e);
-  for (auto* q : s->matchers) orbfe_matcher_destroy(q);
   if (s->frame0Matcher) orbfe_matcher_destroy(s->frame0Matcher);
   orbfe_sfi_chain_destroy(s->chain);
   delete s;
@@ -642,8 +541,8 @@ int orbfe_stream_release(orbfe_stream* s, int ticket) {
 int orbfe_stream_stats(orbfe_stream* s, double out[4], int reset) {
   if (!s || !out) { set_err("NULL argument"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
-  out[0] = s->busySubmit; out[1] = s->busyCollect; out[2] = s->busyMatch; out[3] = (double)s->nBatches;
-  if (reset) { s->busySubmit = s->busyCollect = s->busyMatch = 0; s->nBatches = 0; }
+  out[0] = s->busySubmit; out[1] = s->busyCollect; out[2] = 0; out[3] = (double)s->nBatches;   // (out[2]: matching runs inside submit / collect)
+  if (reset) { s->busySubmit = s->busyCollect = 0; s->nBatches = 0; }
   return ORBFE_OK;
 }
 

@@ -2,7 +2,6 @@
 
 Every windowed search is driven through all of its call forms:
   host     host arrays; the library builds a transient resident frame and keeps the bookkeeping on the GPU (default)
-  hostres  host arrays, ORBFE_MATCH_HOST_RESOLVE=1: candidate lists to the host, bookkeeping there (the round-2 route)
   frame    an orbfe_frame created from host arrays once, searched repeatedly
   extract  an orbfe_frame created from the extractor's result arena (nothing but the queries is uploaded)
 Reference: Frame::AssignFeaturesToGrid src/Frame.cc:114-129, GetFeaturesInArea :209-262, ORBmatcher::SearchByProjection
@@ -63,7 +62,7 @@ def _routes(api, m, ex, k, d, bounds, monkeypatch, xy_un=None):
     """(name, first-argument factory) per call form; `ex` has just extracted (k, d) as frame 0 of its last batch."""
     fr_host = api.Frame.from_host(m, k, d, bounds)
     fr_ex = api.Frame.from_extract(ex, 0, bounds, xy_un)
-    return [('host', k, None), ('hostres', k, ('ORBFE_MATCH_HOST_RESOLVE', '1')), ('frame', fr_host, None), ('extract', fr_ex, None),
+    return [('host', k, None), ('frame', fr_host, None), ('extract', fr_ex, None),
             # marshalled query arrays + an upload instead of raw arrays read in place by the window kernel
             ('upload', fr_host, ('ORBFE_FRAME_ZEROCOPY', '0'))]
 

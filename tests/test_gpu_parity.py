@@ -405,15 +405,13 @@ def test_search_for_initialization_batch_parity(api, oracle):
     assert got[0][0] > 50
 
 
-@pytest.mark.parametrize('mode', ['gpu', 'gpu-noori', 'gpu-tight', 'host'])
-def test_stream_runner_parity(api, oracle, mode, monkeypatch):
+@pytest.mark.parametrize('mode', ['gpu', 'gpu-noori', 'gpu-tight'])
+def test_stream_runner_parity(api, oracle, mode):
     """orbfe_stream_*: pushed batches come back in order with the same keypoints / descriptors / matches as
     the oracle computes frame by frame (frame i matched against frame i-1 of the stream).  Modes: GPU-resident
-    SearchForInitialization (k_sfi_*, default) with several parameter sets, and the host-side match workers."""
+    SearchForInitialization (k_sfi_*) with several parameter sets."""
     W, H, N, B = 800, 600, 800, 3
-    window, ratio, ori = {'gpu': (100, 0.9, True), 'gpu-noori': (100, 0.9, False), 'gpu-tight': (25, 0.7, True),
-                          'host': (100, 0.9, True)}[mode]
-    monkeypatch.setenv('ORBFE_STREAM_HOST_MATCH', '1' if mode == 'host' else '0')
+    window, ratio, ori = {'gpu': (100, 0.9, True), 'gpu-noori': (100, 0.9, False), 'gpu-tight': (25, 0.7, True)}[mode]
     base = synth(60, W, H)
     frames = [base] + [shifted(base, 3 * i, -2 * i, 600 + i) for i in range(1, 3 * B)]
     frames[4] = np.full((H, W), 90, np.uint8)          # a frame without any keypoint in the middle of the stream
@@ -831,16 +829,13 @@ def test_isolated_batches_and_multi_runner_odd_geometries(api, oracle, cfg):
     st.close()
 
 
-@pytest.mark.parametrize('seq', ['0', '1', 'cap1', 'cap3'])
+@pytest.mark.parametrize('seq', ['0', 'cap1', 'cap3'])
 def test_stream_matching_dense_clusters(api, oracle, seq, monkeypatch):
     """SearchForInitialization bookkeeping under stress: many level-0 keypoints in a small image, a window that covers a
     large part of it and nnratio 1.0, so that almost every query finds a match, keypoints are taken away from earlier
     queries all the time (ORBmatcher.cc:455-466) and the dependency chains between queries are long.  k_sfi_resolve
-    iterates the bookkeeping to its fixed point; ORBFE_SFI_SEQUENTIAL=1 replays it serially; ORBFE_SFI_MAX_ROUNDS=1 / 3
-    stops the fixed point early, so the kernel's serial finish (the bound on adversarial steal chains) does the work.
-    All equal the oracle."""
-    if seq == '1':
-        monkeypatch.setenv('ORBFE_SFI_SEQUENTIAL', '1')
+    iterates the bookkeeping to its fixed point; ORBFE_SFI_MAX_ROUNDS=1 / 3 stops the fixed point early, so the kernel's
+    serial finish (the bound on adversarial steal chains) does the work.  All equal the oracle."""
     if seq.startswith('cap'):
         monkeypatch.setenv('ORBFE_SFI_MAX_ROUNDS', seq[3:])
     W, H, N, nl, B = 420, 300, 1500, 2, 3
@@ -871,8 +866,6 @@ def test_stream_matching_dense_clusters(api, oracle, seq, monkeypatch):
                 total += on
         st.close()
     assert total > 1000
-    if seq == '1':
-        monkeypatch.delenv('ORBFE_SFI_SEQUENTIAL')
     if seq.startswith('cap'):
         monkeypatch.delenv('ORBFE_SFI_MAX_ROUNDS')
 

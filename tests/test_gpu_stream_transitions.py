@@ -146,14 +146,12 @@ def api():
     return a
 
 
-@pytest.mark.parametrize('bd', [(1, 4), (3, 2)], ids=['batch1-depth4', 'batch3-depth2'])
-@pytest.mark.parametrize('path', ['gpu-chain', 'host-workers'])
-def test_stream_transitions_follow_the_predecessor_contract(api, oracle, path, bd, monkeypatch):
+@pytest.mark.parametrize('bd', [(1, 4), (3, 2)], ids=['gpu-chain-batch1-depth4', 'gpu-chain-batch3-depth2'])
+def test_stream_transitions_follow_the_predecessor_contract(api, oracle, bd):
     """orbfe_stream_*: matching off and on, isolated batches on and off, other matching parameters, the host-quadtree route (with a
     larger row stride) and back while batches are in flight, and a keypoint-less frame on a batch boundary -- on the GPU-resident
-    matching chain and on the host match workers."""
+    matching chain."""
     B, depth = bd
-    monkeypatch.setenv('ORBFE_STREAM_HOST_MATCH', '1' if path == 'host-workers' else '0')
     st = api.Stream(N, 1.2, NL, 20, 7, 0, B, depth)
     _run(api, oracle, st, _script(B, True))
 
