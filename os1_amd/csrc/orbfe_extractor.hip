@@ -36,7 +36,7 @@ void launch_ingest(const uint8_t* src, long long sstride, uint8_t* dst, long lon
 void launch_to_gray(const uint8_t* const* raw, long long rawStride, const uint8_t* const* gray, long long grayPitch, int rows,
                     int cols, int channels, const int coef[3], int shift, bool aligned, int nframes, hipStream_t st);
 void launch_fast(const PyramidParams& P, int nframes, hipStream_t st);
-uint32_t fast_task_geo(int fastW, int hCell);
+uint32_t fast_cell_geo(int wCell, int hCell);
 void launch_compact(const PyramidParams& P, int nframes, hipStream_t st);
 void launch_compact_local(const PyramidParams& P, int nframes, hipStream_t st, int level0, int level1);
 void launch_describe(const PyramidParams& P, const SelKp* sel, int nsel, float* angle, uint8_t* desc,
@@ -217,10 +217,8 @@ struct orbfe_extractor {
   bool ingestKernel = true;       // small batches from page-locked host memory: fetched by a kernel on the compute stream (ORBFE_INGEST_KERNEL=0: copy command)
   int coneTile = 0;        // tile edge on the top level (0 = chosen from the level's size)
   int coneMaxFrames = 2;   // batches up to this size build the pyramid with k_pyramid_cone
-  DevBuf<CellInfo> d_cells;
-  DevBuf<FastTask> d_tasks;
+  DevBuf<FastCell> d_cells;
   DevBuf<uint8_t> d_zeros;
-  bool pairCells = false;  // ORBFE_FAST_PAIRS=1: two adjacent cells per wave (7 % fewer vector instructions, but 10 % slower: DESIGN.md s5)
   DevBuf<uint32_t> d_cellCount, d_slots, d_cand;
   DevBuf<const uint8_t*> d_frame0;
   // results leave the GPU in ONE copy: [levelStart][selCount][sel][angle][desc] carved from one arena
@@ -282,7 +280,7 @@ struct orbfe_extractor {
     d_bow.release(); h_bow.release();
     d_tables.release(); d_coneTab.release(); d_coneTailTab.release(); d_slab.release(); d_in.release(); d_cellCount.release();
     d_sfiOrder.release(); d_sfiOrderCount.release(); d_sfiPool.release(); d_sfiPcount.release();
-    d_cells.release(); d_tasks.release(); d_zeros.release(); d_slots.release(); d_cand.release(); d_frame0.release(); d_gray.release(); d_outArena.release(); h_outArena.release();
+    d_cells.release(); d_zeros.release(); d_slots.release(); d_cand.release(); d_frame0.release(); d_gray.release(); d_outArena.release(); h_outArena.release();
     d_f32tmp.release();
     h_frame0.release(); h_cand.release();
     for (auto& es : ev) for (auto& e : es) if (e) (void)hipEventDestroy(e);
@@ -485,74 +483,40 @@ struct orbfe_extractor {
     if (tailBase > 0 && tailBase < nlevels - 2)
       if ((rc = buildCone(tailTile, tailBase, coneTail, d_coneTailTab, tailOk))) return rc;
     if (tailOk && coneTail.base != tailBase) tailOk = false;
-    // per-cell geometry (emit regions of ComputeKeyPointsOctTree's cell grid, ORBextractor.cc:826-844)
-    std::vector<CellInfo> cells(Q.ncells);
+    // per-cell records (emit regions of ComputeKeyPointsOctTree's cell grid, ORBextractor.cc:826-844), in cell order
+    std::vector<FastCell> cells(Q.ncells);
+    Q.fastLean = 1;
     for (int l = 0; l < nlevels; l++) {
       const LevelGeom& L = Q.lv[l];
+      const uint32_t geo = fast_cell_geo(L.wCell, L.hCell);
+      if (geo == 0u && L.nRows * L.nCols > 0) Q.fastLean = 0;
       for (int i = 0; i < L.nRows; i++)
         for (int j = 0; j < L.nCols; j++) {
-          CellInfo ci{};
           const int ex0 = kEdge + j * L.wCell, ey0 = kEdge + i * L.hCell;
-          const int ew = std::min(L.wCell, L.w - kEdge - ex0), eh = std::min(L.hCell, L.h - kEdge - ey0);
-          ci.ex0 = (uint16_t)ex0;
-          ci.ey0 = (uint16_t)ey0;
-          ci.ew = (int8_t)std::max(-1, std::min(ew, 127));
-          ci.eh = (int8_t)std::max(-1, std::min(eh, 127));
-          ci.level = (uint8_t)l;
-          ci.local = (uint32_t)(i * L.nCols + j);
-          ci.slotOff = (uint32_t)(L.slotBase + (long long)ci.local * L.slotCap);
-          cells[L.cellBase + ci.local] = ci;
+          const int ew = std::min(std::min(L.wCell, L.w - kEdge - ex0), 127), eh = std::min(std::min(L.hCell, L.h - kEdge - ey0), 127);
+          const bool valid = ew > 0 && eh > 0;
+          FastCell c{};
+          c.ex0 = (uint16_t)ex0; c.ey0 = (uint16_t)ey0; c.level = (uint8_t)l;
+          c.ew = valid ? (uint8_t)ew : 0;
+          c.eh = valid ? (uint8_t)eh : 0;
+          c.cell = (uint32_t)(L.cellBase + i * L.nCols + j);
+          c.slotOff = (uint32_t)(L.slotBase + (long long)(i * L.nCols + j) * L.slotCap);
+          c.roiOff = l == 0 ? 0u : (uint32_t)(L.off + (long long)(ey0 - 3) * L.pitch + (ex0 - 3));
+          c.pitch = l == 0 ? 0u : (uint32_t)L.pitch;
+          c.wCell = (uint8_t)L.wCell; c.hCell = (uint8_t)L.hCell;
+          c.geo = geo;
+          cells[c.cell] = c;
         }
     }
     if ((rc = d_cells.ensure(cells.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_cells.p, cells.data(), sizeof(CellInfo) * cells.size(), hipMemcpyHostToDevice, stream));
-    // FAST tasks (k_fast_tasks): two horizontally adjacent cells of a cell row per wave where the pair is at most 64
-    // pixels wide (queue entries hold x in 8 bits, the pre-test handles 4 groups of 16 pixels per row)
-    std::vector<FastTask> tasks;
-    tasks.reserve(Q.ncells);
-    Q.fastLean = 1;
-    for (int l = 0; l < nlevels; l++) {
-      LevelGeom& L = Q.lv[l];
-      Q.taskStart[l] = (int)tasks.size();
-      const bool pairOk = pairCells && 2 * L.wCell <= 64 && L.nCols >= 2;
-      L.fastW = pairOk ? 2 * L.wCell : L.wCell;
-      const uint32_t geo = fast_task_geo(L.fastW, L.hCell);
-      if (geo == 0u && L.nRows * L.nCols > 0) Q.fastLean = 0;
-      for (int i = 0; i < L.nRows; i++)
-        for (int j = 0; j < L.nCols;) {
-          const CellInfo& c0 = cells[L.cellBase + i * L.nCols + j];
-          FastTask t{};
-          t.ex0 = c0.ex0; t.ey0 = c0.ey0; t.level = (uint8_t)l;
-          t.cell0 = (uint32_t)(L.cellBase + i * L.nCols + j);
-          t.slotOff0 = c0.slotOff;
-          t.roiOff = l == 0 ? 0u : (uint32_t)(L.off + (long long)((int)c0.ey0 - 3) * L.pitch + ((int)c0.ex0 - 3));
-          t.pitch = l == 0 ? 0u : (uint32_t)L.pitch;
-          t.fastW = (uint8_t)L.fastW; t.hCell = (uint8_t)L.hCell; t.slotCap = (uint16_t)L.slotCap;
-          t.geo = geo;
-          const bool valid0 = c0.ew > 0 && c0.eh > 0;
-          t.ew0 = valid0 ? (uint8_t)c0.ew : 0;
-          t.eh = valid0 ? (uint8_t)c0.eh : 0;
-          int used = 1;
-          if (pairOk && valid0 && j + 1 < L.nCols && c0.ew == L.wCell) {
-            const CellInfo& c1 = cells[L.cellBase + i * L.nCols + j + 1];
-            if (c1.ew > 0 && c1.eh == c0.eh) { t.ew1 = (uint8_t)c1.ew; used = 2; }
-          }
-          tasks.push_back(t);
-          j += used;
-        }
-    }
-    for (int l = nlevels; l <= kMaxLevels; l++) Q.taskStart[l] = (int)tasks.size();
-    if ((rc = d_tasks.ensure(tasks.size()))) return rc;
     if (!d_zeros.p) {
       if ((rc = d_zeros.ensure(256))) return rc;
       HIP_TRY(hipMemsetAsync(d_zeros.p, 0, 256, stream));
     }
     Q.zeros = d_zeros.p;
-    HIP_TRY(hipMemcpyAsync(d_tasks.p, tasks.data(), sizeof(FastTask) * tasks.size(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_cells.p, cells.data(), sizeof(FastCell) * cells.size(), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     Q.cells = d_cells.p;
-    Q.tasks = d_tasks.p;
-    Q.ntasks = (int)tasks.size();
     P = Q;
     rows = r;
     geomGpuQtOk = qtOk;
@@ -1463,7 +1427,6 @@ int orbfe_extractor_create(int nfeatures, float scaleFactor, int nlevels, int in
   for (auto& e : h->evQt) evOk = evOk && hipEventCreate(&e) == hipSuccess;
   if (!evOk) { set_err("hipEventCreate failed"); delete h; return ORBFE_ERR_HIP; }
   if (const char* hv = getenv("ORBFE_HOST_QUADTREE")) h->gpuQuadtree = atoi(hv) == 0;
-  if (const char* pv = getenv("ORBFE_FAST_PAIRS")) h->pairCells = atoi(pv) != 0;
   if (const char* cv = getenv("ORBFE_CONE_MAX_FRAMES")) h->coneMaxFrames = atoi(cv);
   if (const char* pv = getenv("ORBFE_POLL_WAIT_US")) h->pollWaitUs = atoi(pv);
   if (const char* dw = ORBFE_EXP_ENV("ORBFE_DESCRIBE_WAVES")) h->describe4 = atoi(dw) != 1;

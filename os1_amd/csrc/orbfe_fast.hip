@@ -9,20 +9,19 @@
 // s = S-1 where S > t and 0 elsewhere.  The emit region of cell (i,j) is [19+j*wCell, min(19+(j+1)*wCell, w-19)) x
 // [19+i*hCell, ...); the regions tile the level exactly.
 //
-// Work decomposition: ONE WAVE PER TASK, a task being one cell or two horizontally adjacent cells of one cell row
-// (FastTask; the union's ROI is one contiguous tile of at most 70 x (hCell+6) bytes).  Two cells per wave fill the
-// 64 lanes of the score stage (a 31x31 cell leaves about 91 candidates = 1.4 wave iterations; two cells need 3 instead
-// of 4) and halve the per-wave fixed cost, at less LDS per cell than one cell per wave.  All stages keep row-major
-// order over the union, which restricted to either cell is that cell's row-major order = cv::FAST's emission order:
+// Work decomposition: ONE WAVE PER CELL (FastCell, one 32-byte record per cell in the order of the per-frame cell arrays:
+// level-major, cell-row-major).  The cell's ROI is one tile of at most 70 x (hCell+6) bytes in LDS; a 31x31 cell is one wave
+// iteration of stage 1 and about 91 candidates = 1.4 wave iterations of stage 2.  All stages keep the cell's row-major order =
+// cv::FAST's emission order:
 //   stage 1  every emit pixel, 16 per lane (one row, 16 adjacent columns): compass pre-test (a 9-arc always contains
 //            two ADJACENT compass points of one polarity) on packed 16-bit lanes -> DPP-scan-compacted queue
 //   stage 2  queue: S = max over both polarities of max_arc min9, both polarities per packed op; S > t keeps the
 //            entry (compacted in place) and writes the score S-1 to the score tile
-//   stage 3  queue: 3x3 NMS against the score tile (neighbours across the boundary between the two cells count 0),
-//            ballot-ordered emission into each cell's slots
+//   stage 3  queue: 3x3 NMS against the score tile (a zero ring stands for the neighbours outside the emit region),
+//            ballot-ordered emission into the cell's slots
 // Two passes at most, like the reference (:846-856): cv::FAST at iniThFAST; only a cell left without a keypoint (after
 // NMS) is emitted again from a pass at minThFAST.
-// Blocks are remapped so that the blocks an XCD receives (b, b+8, b+16, ...) are CONSECUTIVE tasks: neighbouring cells
+// Blocks are remapped so that the blocks an XCD receives (b, b+8, b+16, ...) are CONSECUTIVE cells: neighbouring cells
 // share ROI halos and cache lines in that XCD's L2.
 #include <hip/hip_runtime.h>
 
@@ -58,8 +57,6 @@ __device__ __forceinline__ unsigned pk_max3_h(unsigned a, unsigned b, unsigned c
 // compiler-level memory fence plus the LDS counter is enough.
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// NPX = pixels per lane in the pre-test (8 or 16)
-// PAIRS = false: every task is a single cell (the default task table); the second cell's bookkeeping compiles away
 // ABL = 0 is the product, and the only instantiation of a default build.  A build with -DORBFE_EXPERIMENTS (make EXPERIMENTS=1)
 // also instantiates the measurement modes ORBFE_FAST_ABLATE selects (tools/fast_ablation.sh, tools/fast_phases.py): the kernel stops
 // after its set-up + ROI load (1), after the pre-test and its compaction (2), after the score stage (3) -- every cell then reports no
@@ -67,9 +64,9 @@ __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmc
 // without the second pass at minThFAST (what that pass costs)
 // What the kernel needs of PyramidParams, as a compact argument block of its own (136 bytes): the whole of it arrives with the
 // first scalar load of a wave; out of the 1.4 KB PyramidParams the fields came in three dependent groups, the last one behind
-// the task fetch.
+// the cell record fetch.
 struct FastArgs {
-  const FastTask* tasks;
+  const FastCell* cells;
   const uint8_t* const* frame0;
   const uint8_t* frameInline[2];
   long long stride0;
@@ -79,13 +76,13 @@ struct FastArgs {
   uint32_t* slots;
   long long slotsPerFrame;
   const uint8_t* zeros;
-  int ncells, ntasks, iniTh, minTh, frameBase;
+  int ncells, pad, iniTh, minTh, frameBase;   // (pad: keeps the offsets of what follows)
 };
 static FastArgs fast_args(const PyramidParams& P) {
   FastArgs A{};
-  A.tasks = P.tasks; A.frame0 = P.frame0; A.frameInline[0] = P.frameInline[0]; A.frameInline[1] = P.frameInline[1];
+  A.cells = P.cells; A.frame0 = P.frame0; A.frameInline[0] = P.frameInline[0]; A.frameInline[1] = P.frameInline[1];
   A.stride0 = P.stride0; A.slab = P.slab; A.slabBytes = P.slabBytes; A.cellCount = P.cellCount; A.slots = P.slots;
-  A.slotsPerFrame = P.slotsPerFrame; A.zeros = P.zeros; A.ncells = P.ncells; A.ntasks = P.ntasks; A.iniTh = P.iniTh; A.minTh = P.minTh;
+  A.slotsPerFrame = P.slotsPerFrame; A.zeros = P.zeros; A.ncells = P.ncells; A.iniTh = P.iniTh; A.minTh = P.minTh;
   A.frameBase = P.frameBase;
   return A;
 }
@@ -94,36 +91,36 @@ __device__ uint32_t* g_fastStampBuf;   // [waves of the launch][8]
 // LEAN (round 5): the prologue for the case every batch launch is in -- LDS-DMA with 16 bytes per lane, row pitches that are
 // multiples of 4, the zero line present, and every per-frame offset (frame * slab bytes, frame * slots, frame * cells) below 4 GiB,
 // all checked on the HOST (launch_fast) instead of by every wave: no staging-mode branches, the LDS carve and the rows-per-instruction
-// quotient come precomputed in the task record (FastTask::geo), pointer arithmetic is 32-bit offsets on 64-bit bases.  The set-up was
+// quotient come precomputed in the cell record (FastCell::geo), pointer arithmetic is 32-bit offsets on 64-bit bases.  The set-up was
 // 242 of the wave's 339 scalar instructions (profiles/r04_fast_ablation.txt); the scalar port is a shared resource of the CU
 // (profiles/r05_salu_rate.txt) and those instructions sit in front of the wave's first memory request.
-template <int NPX, bool PAIRS, int ABL = 0, bool LEAN = false>
+template <int ABL = 0, bool LEAN = false>
 // (amdgpu_num_sgpr(96): the kernel asks for 105 scalar registers by itself, which caps a SIMD at 6 waves; 94 with 3 values parked in
 // a vector register allow 7 -- +1 % in the pipeline, 80 / 88 measured the same)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fast_tasks(FastArgs P, int t0, int nt) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fast_tasks(FastArgs P, int cb, int nc) {
   extern __shared__ __align__(16) uint8_t lds[];
   unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0};
   if constexpr (ABL == 4) stamp[0] = __builtin_amdgcn_s_memtime();
-  // this launch works on tasks [t0, t0 + nt): the levels of one LDS class (launch_fast)
+  // this launch works on cells [cb, cb + nc): the levels of one LDS class (launch_fast)
   // the whole argument block is requested by the wave's first scalar loads, before anything waits (left alone the compiler
-  // fetches t0 / nt, tests the bound below, and only then asks for the rest)
-  asm volatile("" ::"s"(P.tasks), "s"(P.frame0), "s"(P.frameInline[0]), "s"(P.frameInline[1]), "s"(P.stride0), "s"(P.slab), "s"(P.slabBytes),
+  // fetches cb / nc, tests the bound below, and only then asks for the rest)
+  asm volatile("" ::"s"(P.cells), "s"(P.frame0), "s"(P.frameInline[0]), "s"(P.frameInline[1]), "s"(P.stride0), "s"(P.slab), "s"(P.slabBytes),
                "s"(P.cellCount), "s"(P.slots), "s"(P.slotsPerFrame), "s"(P.zeros), "s"(P.ncells), "s"(P.iniTh), "s"(P.minTh), "s"(P.frameBase),
-               "s"(t0), "s"(nt));
-  const int chunk = (nt + 7) >> 3;
-  const int tloc = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-  if (tloc >= nt) return;
-  const int tix = t0 + tloc;
+               "s"(cb), "s"(nc));
+  const int chunk = (nc + 7) >> 3;
+  const int cloc = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (cloc >= nc) return;
+  const int cix = cb + cloc;
   const int f = P.frameBase + blockIdx.y;
   const int lane = threadIdx.x;
-  // A wave's life begins with memory round trips it cannot overlap with anything: keep that chain SHORT.  The task record
+  // A wave's life begins with memory round trips it cannot overlap with anything: keep that chain SHORT.  The cell record
   // (32 bytes: cell, slots AND the level's geometry) and the level-0 pointer of the frame come by two SCALAR loads issued
-  // together -- one round trip through the scalar cache -- and then the ROI loads go out.  (Before round 4: the task by vector
+  // together -- one round trip through the scalar cache -- and then the ROI loads go out.  (Before round 4: the record by vector
   // loads because of its sub-dword fields, a second vector round trip for the rest of it, the level table by a dependent
   // scalar load, the frame pointer by a dependent flat load: eight dependent round trips, 2-3 us of a 7 us wave.)
   typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  const u32x8 tw = *reinterpret_cast<const u32x8 __attribute__((address_space(4)))*>(reinterpret_cast<uintptr_t>(P.tasks + tix));
+  const u32x8 tw = *reinterpret_cast<const u32x8 __attribute__((address_space(4)))*>(reinterpret_cast<uintptr_t>(P.cells + cix));
   u32x2 fpw;
   if (P.frame0) {
     fpw = *reinterpret_cast<const u32x2 __attribute__((address_space(4)))*>(reinterpret_cast<uintptr_t>(P.frame0 + f));
@@ -133,17 +130,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
     fpw.y = (uint32_t)(v >> 32);
   }
   const int ex0 = (int)(tw[0] & 0xffffu), ey0 = (int)(tw[0] >> 16);
-  const int ew0 = (int)(tw[1] & 0xffu), ew1 = PAIRS ? (int)((tw[1] >> 8) & 0xffu) : 0, eh = (int)((tw[1] >> 16) & 0xffu), level = (int)(tw[1] >> 24);
-  const uint32_t cell0 = tw[2], slotOff0 = tw[3], roiOff = tw[4], pitchL = tw[5];
-  const int fastW = (int)(tw[6] & 0xffu), hCell = (int)((tw[6] >> 8) & 0xffu), slotCap = (int)(tw[6] >> 16);
+  const int ew = (int)(tw[1] & 0xffu), eh = (int)((tw[1] >> 16) & 0xffu), level = (int)(tw[1] >> 24);
+  const uint32_t cell = tw[2], slotOff = tw[3], roiOff = tw[4], pitchL = tw[5];
+  const int wCell = (int)(tw[6] & 0xffu), hCell = (int)((tw[6] >> 8) & 0xffu);
   uint32_t* cnt;
-  if constexpr (LEAN) cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.cellCount) + 4u * ((uint32_t)f * (uint32_t)P.ncells + cell0));
-  else cnt = P.cellCount + (long long)f * P.ncells + cell0;
-  if (ew0 == 0) {
+  if constexpr (LEAN) cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.cellCount) + 4u * ((uint32_t)f * (uint32_t)P.ncells + cell));
+  else cnt = P.cellCount + (long long)f * P.ncells + cell;
+  if (ew == 0) {
     if (lane == 0) cnt[0] = 0;
     return;
   }
-  const int W2 = ew0 + ew1;   // emit width of the task
   long long stride;
   const uint8_t* roi;
   if constexpr (LEAN) {
@@ -163,24 +159,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
   }
   // LDS carve (level-uniform): ROI tile, score tile with a zero ring, queue (y<<8|x)
   // (the tile pitch is a multiple of 16 -- the ROI arrives in 16-byte LDS-DMA pieces -- that holds alignment offset + widest ROI row)
-  // LEAN: the carve comes with the task (FastTask::geo = pieces per tile row | rows per instruction << 3 | score tile offset / 16 << 8 |
-  // queue offset / 16 << 18, written by fast_task_geo() below from the same formulas)
+  // LEAN: the carve comes with the cell (FastCell::geo = pieces per tile row | rows per instruction << 3 | score tile offset / 16 << 8 |
+  // queue offset / 16 << 18, written by fast_cell_geo() below from the same formulas)
   const uint32_t geo = tw[7];
-  const int TP = LEAN ? (int)(geo & 7u) << 4 : ((fastW + 6 + 3 + 15) & ~15);
-  const int SP = fastW + 2;
+  const int TP = LEAN ? (int)(geo & 7u) << 4 : ((wCell + 6 + 3 + 15) & ~15);
+  const int SP = wCell + 2;
   uint8_t* tile = lds;
   const int scOff = LEAN ? (int)((geo >> 8) & 0x3ffu) << 4 : (TP * (hCell + 6) + 15) & ~15;   // 16-byte aligned: it is cleared by 16-byte LDS-DMA pieces
   uint8_t* sc = tile + scOff;
   uint16_t* queue = reinterpret_cast<uint16_t*>(lds + (LEAN ? (int)((geo >> 18) & 0x7ffu) << 4 : ((scOff + SP * (hCell + 2) + 15) & ~15)));
 
-  const int rw = W2 + 6, rh = eh + 6;
+  const int rw = ew + 6, rh = eh + 6;
   const int istr = (int)stride;
   // ROI -> LDS by LDS-DMA where the row pitch is a multiple of 4 (every level of the pyramid slab; level 0 when the caller's
   // stride allows it), byte by byte otherwise.  `a` is the byte offset of the ROI inside its first dword.
   const int a = (int)(reinterpret_cast<uintptr_t>(roi) & 3);
   if constexpr (ABL == 4) { asm volatile("" ::"s"(a), "s"(istr), "s"(TP) : "memory"); stamp[1] = __builtin_amdgcn_s_memtime(); }
   if constexpr (LEAN) {
-    // the staging below with everything wave-uniform taken from the task: pieces per row, rows per instruction
+    // the staging below with everything wave-uniform taken from the cell record: pieces per row, rows per instruction
     const int ppr = (int)(geo & 7u), rpi = (int)((geo >> 3) & 31u);
     const float rn = __builtin_amdgcn_rcpf((float)ppr);
     const int lrow = (int)(((float)lane + 0.5f) * rn), lcol = lane - m24(lrow, ppr);
@@ -275,24 +271,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
   }
 
   const unsigned long long below = (1ull << lane) - 1ull;
-  uint32_t* slot0;
-  if constexpr (LEAN) slot0 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.slots) + 4u * ((uint32_t)f * (uint32_t)P.slotsPerFrame + slotOff0));
-  else slot0 = P.slots + (long long)f * P.slotsPerFrame + slotOff0;
-  uint32_t* slot1 = slot0 + slotCap;
-  int base0 = 0, base1 = 0;
-  bool emit0 = true, emit1 = ew1 > 0;
+  uint32_t* slot;
+  if constexpr (LEAN) slot = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.slots) + 4u * ((uint32_t)f * (uint32_t)P.slotsPerFrame + slotOff));
+  else slot = P.slots + (long long)f * P.slotsPerFrame + slotOff;
+  int base = 0;
   for (int pass = 0; pass < 2; pass++) {
     const int tlo = pass ? P.minTh : P.iniTh;
-    // ---- stage 1: compass pre-test, NPX horizontally adjacent pixels per lane --------------------------------------
-    // Lane item i = (row y, group g): pixels x = NPX*g .. NPX*g + NPX-1.  The centre-row bytes and the bytes of rows
+    // ---- stage 1: compass pre-test, 16 horizontally adjacent pixels per lane ----------------------------------------
+    // Lane item i = (row y, group g): pixels x = 16*g .. 16*g + 15.  The centre-row bytes and the bytes of rows
     // y-3 / y+3 come from aligned LDS dwords and one funnel shift per 4-pixel window (the byte alignment `a` of the ROI
-    // is uniform for the task, so it is a template constant of the loop body).
+    // is uniform for the cell, so it is a template constant of the loop body).
     int nq = 0;
-    constexpr int GS = NPX == 16 ? 4 : 3, NS = NPX / 4;   // log2(NPX), 4-pixel windows per lane
-    const int G = (W2 + NPX - 1) >> GS, nItems = G * eh;
+    constexpr int NPX = 16, GS = 4, NS = 4;   // pixels per lane, its log2, 4-pixel windows per lane
+    const int G = (ew + NPX - 1) >> GS, nItems = G * eh;
     // item i+64 = (y + stepY, g + stepG) with one carry.  64 / G from a byte table for G = 1..4 (all there is with 16 pixels per lane
-    // and tasks at most 64 pixels wide): the generic quotient is a 25-instruction reciprocal sequence per wave and pass
-    const int stepY = NPX == 16 ? (int)((0x10152040u >> ((G - 1) << 3)) & 0xffu) : 64 / G, stepG = 64 - stepY * G;
+    // and cells at most 64 pixels wide): the generic quotient is a 25-instruction reciprocal sequence per wave and pass
+    const int stepY = (int)((0x10152040u >> ((G - 1) << 3)) & 0xffu), stepG = 64 - stepY * G;
     auto stage1 = [&](auto aTag) {
       constexpr int A = decltype(aTag)::value;
       // The test is CONSERVATIVE (a superset of "two adjacent compass points of one polarity", stage 2 decides
@@ -324,19 +318,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
       int y = (int)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)G)), g = lane - m24(y, G);   // lane / G (see the ROI load)
       int ro = m24(y, TP) + (g << GS);               // byte offset of (row y, column NPX*g) in the tile
       const int roStep = m24(stepY, TP) + (stepG << GS), roCarry = TP - (G << GS);
-      const uint8_t* t0 = tile - a;   // (A == a: written with the run-time value so that the four alignment variants share their row bases instead of each hoisting its own set out of the pass loop)
+      const uint8_t* tb = tile - a;   // (A == a: written with the run-time value so that the four alignment variants share their row bases instead of each hoisting its own set out of the pass loop)
       for (int i0 = 0; i0 < nItems; i0 += 64) {
         unsigned m = 0;   // bit k = pixel NPX*g + k passes
         if (i0 + lane < nItems) {
           // aligned dwords of (row y+3, tile column NPX*g): byte windows of a row: left = bytes [A, A+NPX),
           // centre / up / down = [A+3, A+3+NPX), right = [A+6, A+6+NPX)
           constexpr int c0 = (A + 3) >> 2, cs = (A + 3) & 3, q0 = (A + 6) >> 2, qs = (A + 6) & 3;
-          const uint32_t* cw = reinterpret_cast<const uint32_t*>(t0 + 3 * TP + ro);
+          const uint32_t* cw = reinterpret_cast<const uint32_t*>(tb + 3 * TP + ro);
           uint32_t w[NS + 3];
 #pragma unroll
           for (int k = 0; k < NS + 3; k++) w[k] = cw[k];
-          const uint32_t* uw = reinterpret_cast<const uint32_t*>(t0 + ro) + c0;               // row y-3 (+3 halo)
-          const uint32_t* dw = reinterpret_cast<const uint32_t*>(t0 + 6 * TP + ro) + c0;      // row y+3
+          const uint32_t* uw = reinterpret_cast<const uint32_t*>(tb + ro) + c0;               // row y-3 (+3 halo)
+          const uint32_t* dw = reinterpret_cast<const uint32_t*>(tb + 6 * TP + ro) + c0;      // row y+3
           uint32_t u[NS + 1], d[NS + 1];
 #pragma unroll
           for (int k = 0; k < NS + 1; k++) { u[k] = uw[k]; d[k] = dw[k]; }
@@ -354,7 +348,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
             O |= fo << (4 * j);   // bit 4j = pixel 4j+1, bit 16+4j = pixel 4j+3
           }
           const unsigned T = E | (O << 1);
-          const int rem = W2 - (g << GS);   // pixels of this group inside the emit width (>= 1)
+          const int rem = ew - (g << GS);   // pixels of this group inside the emit width (>= 1)
           m = (T | (T >> 14)) & ((1u << min(rem, NPX)) - 1u);
         }
         // ordered compaction: inclusive wave scan of the per-lane counts (DPP, 6 adds)
@@ -372,8 +366,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
         // bit-reversed once, so that `rev + rev` shifts the next bit out as the carry -- v_add_co writes it straight into VCC, which
         // masks the store and the advance of the lane's write address; the entry counts up unconditionally.
         {
-          unsigned rev = __builtin_bitreverse32(m) >> (16 - NPX), ent = e;   // bit k of m -> bit 31 - k ... (NPX = 8: bits 0..7 -> 31..24)
-          rev <<= (16 - NPX);
+          unsigned rev = __builtin_bitreverse32(m), ent = e;   // bit k of m -> bit 31 - k
           unsigned addr = (unsigned)(uintptr_t)(queue + pos);   // LDS byte address
           unsigned long long saved;
           asm volatile(
@@ -467,7 +460,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
       if (lane == 0) cnt[0] = (acc == 0xffffffffu) ? 1u : 0u;
       return;
     }
-    // ---- stage 3: NMS inside each cell's emit region and ordered emission (every survivor has score >= tlo) --------
+    // ---- stage 3: NMS inside the cell's emit region and ordered emission (every survivor has score >= tlo) ---------
     for (int i0 = 0; i0 < nq2; i0 += 64) {
       const int i = i0 + lane;
       int keep = 0, y = 0, x = 0;
@@ -477,45 +470,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(96))) void k_fas
         x = e & 0xff;
         const uint8_t* q = sc + m24(y + 1, SP) + (x + 1);
         const int sv = q[0];
-        // neighbours on the other side of the boundary between the two cells count 0 (each cell is its own cv::FAST ROI)
-        const int lm = (ew1 && x == ew0) ? 0 : 0xff, rm = (ew1 && x == ew0 - 1) ? 0 : 0xff;
         // strictly greater than all eight neighbours = greater than their maximum (three-input maxima: 4 instructions for 8 values)
-        const int nmax = max(max(max(q[-1] & lm, q[-SP - 1] & lm), q[SP - 1] & lm), max(max(max(q[1] & rm, q[-SP + 1] & rm), q[SP + 1] & rm), max((int)q[-SP], (int)q[SP])));
+        const int nmax = max(max(max((int)q[-1], (int)q[-SP - 1]), (int)q[SP - 1]), max(max(max((int)q[1], (int)q[-SP + 1]), (int)q[SP + 1]), max((int)q[-SP], (int)q[SP])));
         if (sv > nmax) keep = sv;   // (sv > 0 follows: nmax >= 0)
       }
-      const bool in1 = x >= ew0;
       const uint32_t rec = (uint32_t)(ex0 + x) | ((uint32_t)(ey0 + y) << 12) | ((uint32_t)keep << 24);
-      if (emit0) {
-        const unsigned long long mk = __ballot(keep > 0 && !in1);
-        if (keep > 0 && !in1) slot0[base0 + __popcll(mk & below)] = rec;
-        base0 += __popcll(mk);
-      }
-      if (emit1) {
-        const unsigned long long mk = __ballot(keep > 0 && in1);
-        if (keep > 0 && in1) slot1[base1 + __popcll(mk & below)] = rec;
-        base1 += __popcll(mk);
-      }
+      const unsigned long long mk = __ballot(keep > 0);
+      if (keep > 0) slot[base + __popcll(mk & below)] = rec;
+      base += __popcll(mk);
     }
     if (pass == 1 || P.minTh == P.iniTh) break;
     if constexpr (ABL == 5) break;   // measurement: what the second pass costs
     // ORBextractor.cc:850-856: a cell whose first cv::FAST call returned nothing is detected again at minThFAST
-    emit0 = base0 == 0;
-    emit1 = ew1 > 0 && base1 == 0;
-    if (!emit0 && !emit1) break;
+    if (base != 0) break;
     wave_lds_fence();   // the queue is rebuilt by the second pass
   }
-  if (lane == 0) {
-    cnt[0] = (uint32_t)base0;
-    if (ew1) cnt[1] = (uint32_t)base1;
-  }
+  if (lane == 0) cnt[0] = (uint32_t)base;
   if constexpr (ABL == 4) {
     stamp[5] = __builtin_amdgcn_s_memtime();
     // one record per wave, plain stores (same-address atomics from 200 000 waves back up the memory pipeline and inflate the
     // very latencies being measured)
     if (lane == 0 && g_fastStampBuf) {
-      // indexed by the TASK (unique across the LDS-class launches of a batch), not by the block: blocks are dealt XCD-consecutively,
-      // so blockIdx.x runs up to 8 * ceil(nt / 8) - 1 and the tail of one class used to land on the first records of the next
-      uint32_t* rec = g_fastStampBuf + 8ull * ((unsigned long long)blockIdx.y * (P.ntasks + 64) + tix);
+      // indexed by the CELL (unique across the LDS-class launches of a batch), not by the block: blocks are dealt XCD-consecutively,
+      // so blockIdx.x runs up to 8 * ceil(nc / 8) - 1 and the tail of one class used to land on the first records of the next
+      uint32_t* rec = g_fastStampBuf + 8ull * ((unsigned long long)blockIdx.y * (P.ncells + 64) + cix);
       for (int k = 0; k < 5; k++) rec[k] = (uint32_t)(stamp[k + 1] - stamp[k]);
       rec[5] = 1u;
     }
@@ -559,20 +537,20 @@ int fast_stamps(unsigned long long out[8], int) {   // (a default build has no s
 #endif
 
 static size_t fast_lds_bytes_level(const LevelGeom& L) {
-  const size_t TP = (size_t)((L.fastW + 6 + 3 + 15) & ~15);
+  const size_t TP = (size_t)((L.wCell + 6 + 3 + 15) & ~15);
   const size_t scOff = (TP * (L.hCell + 6) + 15) & ~(size_t)15;
-  const size_t b = ((scOff + (size_t)(L.fastW + 2) * (L.hCell + 2) + 15) & ~(size_t)15) +
-                   2 * (size_t)L.fastW * L.hCell + 64;  // tile + score tile + u16 queue + slack for the group over-read
+  const size_t b = ((scOff + (size_t)(L.wCell + 2) * (L.hCell + 2) + 15) & ~(size_t)15) +
+                   2 * (size_t)L.wCell * L.hCell + 64;  // tile + score tile + u16 queue + slack for the group over-read
   return (b + 15) & ~(size_t)15;
 }
-// FastTask::geo of a level (the LEAN prologue's LDS carve and staging constants); 0: not representable -> the level's launches
+// FastCell::geo of a level (the LEAN prologue's LDS carve and staging constants); 0: not representable -> the level's launches
 // take the generic prologue
-uint32_t fast_task_geo(int fastW, int hCell) {
-  const uint32_t TP = (uint32_t)((fastW + 6 + 3 + 15) & ~15), ppr = TP >> 4;
+uint32_t fast_cell_geo(int wCell, int hCell) {
+  const uint32_t TP = (uint32_t)((wCell + 6 + 3 + 15) & ~15), ppr = TP >> 4;
   if (ppr == 0 || ppr > 7) return 0u;
   const uint32_t rpi = 64u / ppr;
   const uint32_t scOff = (TP * (uint32_t)(hCell + 6) + 15u) & ~15u;
-  const uint32_t qOff = (scOff + (uint32_t)(fastW + 2) * (uint32_t)(hCell + 2) + 15u) & ~15u;
+  const uint32_t qOff = (scOff + (uint32_t)(wCell + 2) * (uint32_t)(hCell + 2) + 15u) & ~15u;
   if (rpi > 31u || (scOff >> 4) > 0x3ffu || (qOff >> 4) > 0x7ffu) return 0u;
   return ppr | (rpi << 3) | ((scOff >> 4) << 8) | ((qOff >> 4) << 18);
 }
@@ -582,8 +560,6 @@ void launch_fast(const PyramidParams& P, int nframes, hipStream_t st) {
   // equal in time, 9.9 us per 1080p frame, with more instructions)
   const FastArgs FA = fast_args(P);
   const int level0 = 0, level1 = P.nlevels;
-  bool pairs = false;
-  for (int l = 0; l < P.nlevels; l++) pairs = pairs || P.lv[l].fastW != P.lv[l].wCell;
   // LDS CLASSES (round 4).  LDS is handed out in 1 KB granules and a CU has 160 of them: a one-wave workgroup that asks for up
   // to 5 120 bytes leaves room for 32 waves per CU (8 per SIMD), one that asks for 5 121 .. 6 144 for 26 (6.5 per SIMD) --
   // measured with tools/ubench/dispatch_rate.hip: 7.35 / 5.85 / 4.96 resident waves per SIMD at 4 608 / 5 632 / 6 656 bytes.
@@ -607,10 +583,11 @@ void launch_fast(const PyramidParams& P, int nframes, hipStream_t st) {
     } else {
       while (e < level1) { need = std::max(need, fast_lds_bytes_level(P.lv[e])); e++; }
     }
-    const int t0 = P.taskStart[l], nt = P.taskStart[e] - t0;
+    // cells [cb, cb + nc) of levels l .. e-1 (the cell table is level-major)
+    const int cb = P.lv[l].cellBase, nc = (e < P.nlevels ? P.lv[e].cellBase : P.ncells) - cb;
     l = e;
-    if (nt <= 0) continue;
-    const dim3 grid(8 * ((nt + 7) / 8), nframes);
+    if (nc <= 0) continue;
+    const dim3 grid(8 * ((nc + 7) / 8), nframes);
     // the LEAN prologue's preconditions, checked once per launch instead of by every wave (level 0: the ROI offset
     // (ey0 - 3) * stride0 + ex0 - 3 of the last cell row must fit 32 bits)
     const unsigned long long frames = (unsigned long long)P.frameBase + (unsigned long long)nframes;
@@ -619,12 +596,12 @@ void launch_fast(const PyramidParams& P, int nframes, hipStream_t st) {
                       frames * (unsigned long long)P.ncells * 4ull < (1ull << 32) &&
                       (unsigned long long)P.lv[0].h * (unsigned long long)P.stride0 < (1ull << 32);
 #ifdef ORBFE_EXPERIMENTS
-    if (ablate && !pairs) {
-      if (ablate == 4 && t0 == 0) stamp_buffer_for((size_t)(P.ntasks + 64) * nframes);
+    if (ablate) {
+      if (ablate == 4 && cb == 0) stamp_buffer_for((size_t)(P.ncells + 64) * nframes);
 #define ORBFE_FAST_ABL(A)                                                                                              \
   do {                                                                                                                 \
-    if (lean) hipLaunchKernelGGL((k_fast_tasks<16, false, A, true>), grid, dim3(64), need, st, FA, t0, nt);            \
-    else hipLaunchKernelGGL((k_fast_tasks<16, false, A, false>), grid, dim3(64), need, st, FA, t0, nt);                \
+    if (lean) hipLaunchKernelGGL((k_fast_tasks<A, true>), grid, dim3(64), need, st, FA, cb, nc);                       \
+    else hipLaunchKernelGGL((k_fast_tasks<A, false>), grid, dim3(64), need, st, FA, cb, nc);                           \
   } while (0)
       switch (ablate) {
         case 1: ORBFE_FAST_ABL(1); break;
@@ -637,9 +614,8 @@ void launch_fast(const PyramidParams& P, int nframes, hipStream_t st) {
       continue;
     }
 #endif
-    if (pairs) hipLaunchKernelGGL((k_fast_tasks<16, true, 0, false>), grid, dim3(64), need, st, FA, t0, nt);
-    else if (lean) hipLaunchKernelGGL((k_fast_tasks<16, false, 0, true>), grid, dim3(64), need, st, FA, t0, nt);
-    else hipLaunchKernelGGL((k_fast_tasks<16, false, 0, false>), grid, dim3(64), need, st, FA, t0, nt);
+    if (lean) hipLaunchKernelGGL((k_fast_tasks<0, true>), grid, dim3(64), need, st, FA, cb, nc);
+    else hipLaunchKernelGGL((k_fast_tasks<0, false>), grid, dim3(64), need, st, FA, cb, nc);
   }
 }
 

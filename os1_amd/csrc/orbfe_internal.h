@@ -29,36 +29,25 @@ struct LevelGeom {
   const short* ybeta;      // [2*h] 11-bit weights (b0,b1)
   const unsigned* yofc;    // [h]   the two source rows of a destination row, clamped to the source: row0 | row1 << 16 (k_resize_fixed)
   int rzPitch, rzRows;     // LDS pitch / rows of the largest 64x64-tile source footprint (k_resize)
-  int fastW;               // widest emit region of a FAST task on this level (2 * wCell when cells are paired, else wCell)
 };
 
-// Per-cell geometry, precomputed on the host so a cell's wave needs one 16-byte load instead of a scalar
-// search over the level table.
-struct CellInfo {
+// One FAST cell (ComputeKeyPointsOctTree's cell grid), precomputed on the host; entry c of the table is cell c of the per-frame
+// cell arrays (level-major, cell-row-major).  One wave of k_fast_tasks works on one record; k_compact reads slotOff.
+struct FastCell {
   uint16_t ex0, ey0;     // first emit pixel (level coordinates)
-  int8_t ew, eh;         // emit size (<= 0: the cell emits nothing)
-  uint8_t level, pad;
-  uint32_t slotOff;      // first slot of the cell inside a frame's slot array (u32 units)
-  uint32_t local;        // cell index inside its level
-};
-
-// One wave of k_fast_tasks: one FAST cell, or two horizontally adjacent cells of the same cell row whose union is at
-// most 64 pixels wide (the second cell starts where the first ends, so the union's ROI is one contiguous tile).
-struct FastTask {
-  uint16_t ex0, ey0;     // first emit pixel of cell 0 (level coordinates)
-  uint8_t ew0, ew1;      // emit widths of cell 0 / cell 1 (ew1 = 0: single cell; ew0 = 0: the cell emits nothing)
+  uint8_t ew, pad0;      // emit width (0: the cell emits nothing)
   uint8_t eh, level;
-  uint32_t cell0;        // index of cell 0 in the per-frame cell arrays (cell 1 = cell0 + 1)
-  uint32_t slotOff0;     // first slot of cell 0 (cell 1: + the level's slotCap)
+  uint32_t cell;         // index of the cell in the per-frame cell arrays = index of this record
+  uint32_t slotOff;      // first slot of the cell inside a frame's slot array (u32 units)
   // the level's geometry as far as the FAST wave needs it, so that ONE 32-byte scalar load gives a wave everything it needs
   // to issue its ROI loads (the level table in the kernel arguments cost a second, dependent scalar round trip per wave):
   uint32_t roiOff;       // levels >= 1: byte offset of ROI pixel (ex0 - 3, ey0 - 3) inside one frame's pyramid slab
   uint32_t pitch;        // levels >= 1: row pitch of the level in the slab (level 0: the caller's stride, PyramidParams::stride0)
-  uint8_t fastW, hCell;  // LevelGeom::fastW / hCell of the level (tile pitch and LDS carve)
-  uint16_t slotCap;      // LevelGeom::slotCap
-  uint32_t geo;          // the LEAN prologue's LDS carve and staging constants of the level (fast_task_geo(); 0: generic prologue only)
+  uint8_t wCell, hCell;  // LevelGeom::wCell / hCell of the level (tile pitch and LDS carve)
+  uint16_t pad1;
+  uint32_t geo;          // the LEAN prologue's LDS carve and staging constants of the level (fast_cell_geo(); 0: generic prologue only)
 };
-static_assert(sizeof(FastTask) == 32, "one s_load_dwordx8 per FAST wave");
+static_assert(sizeof(FastCell) == 32, "one s_load_dwordx8 per FAST wave");
 
 struct PyramidParams {
   LevelGeom lv[kMaxLevels];
@@ -76,15 +65,12 @@ struct PyramidParams {
   uint32_t* slots;                  // [nframes][slotsPerFrame]
   uint32_t* cand;                   // [nframes][candCap]  packed x | y<<12 | score<<24 (level coords)
   uint32_t* levelStart;             // [nframes][kMaxLevels+1]  first candidate of every level (packed list); level-local lists: the levels' COUNTS
-  const CellInfo* cells;            // [ncells]
-  const FastTask* tasks;            // [ntasks] work items of k_fast_tasks, level-major
-  int ntasks;
-  int taskStart[kMaxLevels + 1];    // first task of each level (host side of launch_fast: LDS classes)
+  const FastCell* cells;            // [ncells] level-major, cell-row-major
   const uint8_t* zeros;             // 256 zero bytes in device memory: source of the LDS-DMA that clears a FAST wave's score tile
   int iniTh, minTh;
   int frameBase;                    // first frame of this launch (sub-batch pipelining)
   int gaussVariant;                 // ORBFE_GAUSS_ED / ORBFE_GAUSS_ROUNDED: which GaussianBlur k_describe reproduces
-  int fastLean;                     // every task carries FastTask::geo: k_fast_tasks may take its LEAN prologue (launch_fast decides per launch)
+  int fastLean;                     // every cell carries FastCell::geo: k_fast_tasks may take its LEAN prologue (launch_fast decides per launch)
 };
 
 // Small batches build the pyramid in ONE launch (k_pyramid_cone): a block owns a tile of the top level and computes

@@ -8,7 +8,7 @@
 //   k_resize_fixed  the same with the LDS geometry fixed at compile time (every level at scale 1.2): the kernel that runs
 //   k_pyramid_cone  all levels in one launch for one- and two-frame calls (a block walks down the dependency cone of a
 //                   top-level tile)
-//   (k_fast_tasks   per reference FAST cell, one wave per cell pair: orbfe_fast.hip)
+//   (k_fast_tasks   per reference FAST cell, one wave per cell: orbfe_fast.hip)
 //   k_compact       ordered compaction of the per-cell slots into the reference's candidate order (1 lane/cell)
 //   k_describe      per keypoint (1 wave): IC-angle (dot4), 7x7 fixed-point Gaussian of the 37x37 neighbourhood
 //                   (dot4 rows, dot2 columns), steered BRIEF with __ballot packing

@@ -630,11 +630,9 @@ def test_randomised_sizes_and_parameters(api, oracle):
         _cmp_extract((kps[1, :n[1]], desc[1, :n[1]]), ox.extract(img[::-1].copy()))
 
 
-def test_fast_cell_pairs_variant_bit_exact(api, oracle, monkeypatch):
-    """ORBFE_FAST_PAIRS=1: two horizontally adjacent FAST cells per wave (fewer instructions, kept as an option,
-    DESIGN.md s5) -- same keypoints and descriptors, including the per-cell minThFAST fallback and the NMS cut at the
-    boundary between the two cells of a wave."""
-    monkeypatch.setenv('ORBFE_FAST_PAIRS', '1')
+def test_fast_candidates_per_level_bit_exact(api, oracle):
+    """k_fast_tasks, one FAST cell per wave: same keypoints and descriptors AND the same per-level candidate lists as the
+    oracle, including cells that need the per-cell minThFAST pass (the low-contrast half of the 801 x 333 image)."""
     for seed, W, H, N in ((2, 1920, 1080, 2000), (12, 752, 480, 900), (13, 801, 333, 600)):
         img = synth(seed, W, H)
         if seed == 13:

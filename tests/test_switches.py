@@ -12,7 +12,7 @@ SOURCES = [p for p in SOURCES if p.endswith(('.hip', '.cpp', '.h', '.hpp', '.inc
 
 # configuration a deployment sets, not a code route: which GPU, how many host threads, whether to print, what the HIP runtime was given
 CONFIGURATION = {'GPU_MAX_HW_QUEUES', 'ORBFE_DEVICE', 'ORBFE_QUIET', 'ORBFE_HOST_THREADS'}
-MAX_SWITCHES = 21
+MAX_SWITCHES = 20
 
 
 def _names(pattern):
