@@ -611,6 +611,51 @@ int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_loca
                                     const float* scale_factors, int nlevels, const uint8_t* kp_occupied, float th, float nnratio,
                                     uint8_t* in_view, float* proj_xy, int32_t* level, float* view_cos, int32_t* kp_assigned,
                                     int* nmatches, int* n_in_view);
+/* The projection loops of the two frame-rate searches whose sources are the keypoints of ANOTHER frame, on the GPU:
+ *   ORBFE_SRC_LAST_FRAME  int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th)
+ *                         (src/ORBmatcher.cc:1292-1423; projection :1324-1347)
+ *   ORBFE_SRC_KEYFRAME    int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist)
+ *                         (:1425-1552; projection :1450-1479)
+ * Source i is keypoint i of src_frame (the resident copy of LastFrame / pKF; n_src must equal its size): its octave
+ * (mvKeys[i].octave, the window's level in LAST_FRAME mode) and its angle (mvKeysUn[i].angle, the rotation check) are read
+ * from that copy.  Its MapPoint is row rows[i] of `map` (position, raw mfMinDistance / mfMaxDistance, descriptor); cam is the
+ * CURRENT frame's camera (Ow = -Rcw.t()*tcw as :1431 computes it; read in KEYFRAME mode only), the bounds are cur_frame's.
+ * flags[i]: ORBFE_MP_SKIP = no MapPoint / mvbOutlier[i] (LAST_FRAME), no MapPoint / in sAlreadyFound (KEYFRAME);
+ * ORBFE_MP_BAD = isBad() (KEYFRAME; ignored in LAST_FRAME mode, whose loop does not ask); ORBFE_MP_OBSERVED =
+ * Observations() > 0.  A source that is not projected may carry any row.  Per source:
+ *   valid [n_src]  : 1 = the source reaches GetFeaturesInArea (:1349 / :1481)
+ *   uv [2*n_src]   : the projection u, v              level [n_src] : nLastOctave resp. nPredictedLevel (PredictScale, NOT
+ *                                                                     clamped: reported as it is)
+ * bit for bit the reference's values (float cv::Mat arithmetic, the double division of :1329 / :1455, glibc logf); 0
+ * where valid is 0.  LAST_FRAME rejects invzc < 0 (:1332), KEYFRAME does not (a point behind the camera that lands inside the
+ * bounds stays valid, as in the reference).  A projection that is not finite (z = +-0 with x = y = 0) is invalid: the
+ * reference's GetFeaturesInArea finds no cell for it.  *n_valid = valid sources.  Any output may be NULL.  rows and flags are
+ * host memory; a row outside [0, capacity) of a source that is projected fails the call with ORBFE_ERR_INVALID.  Returns
+ * when the outputs are written. */
+#define ORBFE_SRC_LAST_FRAME 0
+#define ORBFE_SRC_KEYFRAME 1
+int orbfe_project_sources(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame, orbfe_local_map* map,
+                          const OrbfeCamera* cam, int mode, const int32_t* rows, const uint8_t* flags, int n_src, uint8_t* valid,
+                          float* uv, int32_t* level, int* n_valid);
+/* The projection of orbfe_project_sources followed by the rest of that search (the windows, best distance <= max_dist, the
+ * rotation histogram) in ONE submission on the matcher's stream: the projection kernel leaves the queries in device memory
+ * and the search reads them there; per source only rows[i] and flags[i] cross PCIe.  LAST_FRAME: a keypoint is taken once a
+ * source with ORBFE_MP_OBSERVED holds it (:1363-1365; orbfe_search_by_projection_uv_frame's skip_any_occupied = 0), max_dist =
+ * TH_HIGH; KEYFRAME: once any source holds it (:1493-1494; skip_any_occupied = 1), max_dist = ORBdist.  scale_factors
+ * (CurrentFrame.mvScaleFactors, 1..32 levels), kp_occupied, th, check_orientation, kp_assigned (source index, -1, or -2 for a
+ * slot the rotation check cleared), nmatches as for orbfe_search_by_projection_uv_frame.  valid, uv, level: optional outputs
+ * (NULL: not returned).  Results are those of orbfe_project_sources followed by orbfe_search_by_projection_uv_frame on the
+ * same inputs.
+ * LEVEL CONTRACT: a valid source whose level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID, as in
+ * orbfe_search_local_points_frame: the projection kernel takes it out of the search before anything is indexed with that
+ * level (LAST_FRAME: refused up front from the source frame's largest octave); the outputs are then unspecified, and the
+ * matcher, frames and table stay usable. */
+int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame,
+                                             orbfe_local_map* map, const OrbfeCamera* cam, int mode, const int32_t* rows,
+                                             const uint8_t* flags, int n_src, const float* scale_factors, int nlevels,
+                                             const uint8_t* kp_occupied, float th, int max_dist, int check_orientation,
+                                             uint8_t* valid, float* uv, int32_t* level, int32_t* kp_assigned, int* nmatches,
+                                             int* n_valid);
 
 /* Rounds the bookkeeping kernel of the last `_frame` search needed -- the most any chunk of 2 048 consecutive queries took
  * (negative: a chunk hit the bound ORBFE_RESOLVE_MAX_ROUNDS, default 48, and a serial pass on the device finished it). */

@@ -963,6 +963,109 @@ inline int SearchByProjection(MatcherContext& ctx, bool mbCheckOrientation, Fram
   return nmatches;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The two searches above with their projection loops on the GPU (orbfe_search_by_projection_sources_frame): the source
+// frame's resident copy supplies mvKeys[i].octave and mvKeysUn[i].angle (both copies of one record: Frame::UndistortKeyPoints
+// replaces pt only), the MapPoints' positions, depth ranges and descriptors are rows of the context's local-map table -- the
+// rows SearchLocalPoints uses, so a MapPoint known to either keeps ONE row, and only rows whose content changed are sent.
+// Per call and source keypoint one row number and one flag byte cross PCIe.  `geometry` is SearchLocalPoints' functor.
+// With the frame cache off (or a source that cannot be made resident) they ARE the functions above.
+// ---------------------------------------------------------------------------------------------------------------
+namespace detail {
+template <class FrameT>
+inline void currentCamera(const FrameT& F, OrbfeCamera& cam) {
+  poseRt(F.mTcw, cam.Rcw, cam.tcw);
+  RestatedOps::gemmT3(cam.Rcw, cam.tcw, -1.0, cam.Ow);   // -Rcw.t()*tcw (ORBmatcher.cc:1431; the LastFrame form does not read it)
+  cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy;
+  cam.logScaleFactor = F.mfLogScaleFactor;
+}
+template <class MapPointT, class GeometryFn>
+inline int32_t sourceRow(MatcherContext& ctx, MapPointT* p, GeometryFn& geometry) {
+  float row[16];
+  float& minRaw = row[6];
+  float& maxRaw = row[7];
+  geometry(p, row, row + 3, minRaw, maxRaw);
+  const auto d = p->GetDescriptor();
+  std::memcpy(row + 8, d.data, 32);
+  return ctx.localMapRow(p, reinterpret_cast<const uint8_t*>(row));
+}
+}  // namespace detail
+
+// int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th)   (ORBmatcher.cc:1292-1423)
+template <class FrameT, class GeometryFn>
+inline int SearchByProjectionLastFrame(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, const FrameT& LastFrame,
+                                       const float th, GeometryFn geometry) {
+  const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)LastFrame.mvKeysUn.size();
+  orbfe_frame* src = ctx.resident(LastFrame, 0);
+  orbfe_frame* cur = src ? ctx.resident(CurrentFrame, 0) : nullptr;   // (never evicts src: the two most recent frames stay)
+  if (!src || !cur || ns != (int)LastFrame.mvpMapPoints.size()) return SearchByProjection(ctx, mbCheckOrientation, CurrentFrame, LastFrame, th);
+  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
+  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
+  for (int i = 0; i < n; i++)
+    if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) occ[i] = 1;   // :1363-1365
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    auto* pMP = LastFrame.mvpMapPoints[i];
+    if (!pMP || LastFrame.mvbOutlier[i]) { flags[i] = ORBFE_MP_SKIP; continue; }   // :1318-1321
+    flags[i] = pMP->Observations() > 0 ? ORBFE_MP_OBSERVED : 0;
+    rows[i] = detail::sourceRow(ctx, pMP, geometry);
+  }
+  ctx.localMapCommit();
+  OrbfeCamera cam;
+  detail::currentCamera(CurrentFrame, cam);
+  int nmatches = 0, nValid = 0;
+  check(orbfe_search_by_projection_sources_frame(ctx.get(), cur, src, ctx.localMap(), &cam, ORBFE_SRC_LAST_FRAME, rows, flags, ns,
+                                                 CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ, th,
+                                                 /*TH_HIGH*/ 100, mbCheckOrientation ? 1 : 0, nullptr, nullptr, nullptr, assigned,
+                                                 &nmatches, &nValid));
+  for (int i = 0; i < n; i++) {
+    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[assigned[i]];
+    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;    // rotation check, :1409-1419
+  }
+  return nmatches;
+}
+
+// int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound,
+//                                    const float th, const int ORBdist)   (ORBmatcher.cc:1425-1552)
+template <class FrameT, class KeyFrameT, class SetT, class GeometryFn>
+inline int SearchByProjectionKeyFrame(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, KeyFrameT* pKF,
+                                      const SetT& sAlreadyFound, const float th, const int ORBdist, GeometryFn geometry) {
+  const auto vpMPs = pKF->GetMapPointMatches();
+  const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)vpMPs.size();
+  orbfe_frame* src = ns == (int)pKF->mvKeysUn.size() ? ctx.resident(*pKF, 1) : nullptr;
+  orbfe_frame* cur = src ? ctx.resident(CurrentFrame, 0) : nullptr;
+  if (!src || !cur) return SearchByProjection(ctx, mbCheckOrientation, CurrentFrame, pKF, sAlreadyFound, th, ORBdist);
+  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
+  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
+  for (int i = 0; i < n; i++)
+    if (CurrentFrame.mvpMapPoints[i]) occ[i] = 1;                         // :1493-1494
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    auto* pMP = vpMPs[i];
+    if (!pMP) { flags[i] = ORBFE_MP_SKIP; continue; }
+    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }              // :1447
+    if (sAlreadyFound.count(pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
+    rows[i] = detail::sourceRow(ctx, pMP, geometry);
+  }
+  ctx.localMapCommit();
+  OrbfeCamera cam;
+  detail::currentCamera(CurrentFrame, cam);
+  int nmatches = 0, nValid = 0;
+  check(orbfe_search_by_projection_sources_frame(ctx.get(), cur, src, ctx.localMap(), &cam, ORBFE_SRC_KEYFRAME, rows, flags, ns,
+                                                 CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ, th,
+                                                 ORBdist, mbCheckOrientation ? 1 : 0, nullptr, nullptr, nullptr, assigned, &nmatches,
+                                                 &nValid));
+  for (int i = 0; i < n; i++) {
+    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = vpMPs[assigned[i]];
+    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;
+  }
+  return nmatches;
+}
+
 // int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
 //                                    vector<MapPoint*>& vpMatched, int th)   (ORBmatcher.cc:285-398)
 template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>

@@ -186,6 +186,9 @@ def load_library():
     L.orbfe_project_local_map.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_search_local_points_frame.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, ci, vp, cf, cf, vp, vp, vp, vp, vp,
                                                   C.POINTER(ci), C.POINTER(ci)]
+    L.orbfe_project_sources.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, C.POINTER(ci)]
+    L.orbfe_search_by_projection_sources_frame.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, cf, ci, ci, vp, vp, vp,
+                                                           vp, C.POINTER(ci), C.POINTER(ci)]
     _lib = L
     return L
 
@@ -410,6 +413,7 @@ class Camera(C.Structure):
 
 
 MP_IN_VIEW, MP_BAD, MP_CANDIDATO, MP_OBSERVED, MP_SKIP = 1, 2, 4, 8, 16
+SRC_LAST_FRAME, SRC_KEYFRAME = 0, 1
 
 
 class LocalMap:
@@ -665,6 +669,40 @@ class Matcher:
                                                       _p(assigned), C.byref(nm), C.byref(cnt)))
         return dict(nmatches=nm.value, kp_assigned=assigned[:len(frame)], n_in_view=cnt.value, in_view=iv[:n], proj_xy=xy[:n],
                     level=lv[:n], view_cos=vc[:n])
+
+    def project_sources(self, cur, src, lmap, cam, mode, rows, flags):
+        """The projection loop of SearchByProjection(CurrentFrame, LastFrame, th) (mode SRC_LAST_FRAME) or (CurrentFrame, pKF,
+        sAlreadyFound, th, ORBdist) (SRC_KEYFRAME): source i = keypoint i of the resident frame `src`, its MapPoint row rows[i]
+        of `lmap` (flags: MP_SKIP / MP_BAD skip it): dict of valid, uv, level arrays and n_valid."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        n = len(rows)
+        va = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        cnt = C.c_int(0)
+        _check(self.L.orbfe_project_sources(self.h, cur.h, src.h, lmap.h, C.byref(cam), mode, _p(rows), _p(flags), n, _p(va),
+                                            _p(uv), _p(lv), C.byref(cnt)))
+        return dict(valid=va[:n], uv=uv[:n], level=lv[:n], n_valid=cnt.value)
+
+    def search_by_projection_sources(self, cur, src, lmap, cam, mode, rows, flags, kp_occupied, scale_factors, th, max_dist=100,
+                                     check_ori=True):
+        """project_sources + the rest of that search in one submission: dict of nmatches, kp_assigned (source index, -1, or -2
+        for a slot the rotation check cleared), n_valid and the projection's valid, uv, level."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        occ = np.ascontiguousarray(kp_occupied, np.uint8)
+        n = len(rows)
+        va = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        assigned = np.full(max(len(cur), 1), -1, np.int32)
+        nm, cnt = C.c_int(0), C.c_int(0)
+        _check(self.L.orbfe_search_by_projection_sources_frame(self.h, cur.h, src.h, lmap.h, C.byref(cam), mode, _p(rows), _p(flags),
+                                                               n, _p(sf), len(sf), _p(occ), th, int(max_dist), 1 if check_ori else 0,
+                                                               _p(va), _p(uv), _p(lv), _p(assigned), C.byref(nm), C.byref(cnt)))
+        return dict(nmatches=nm.value, kp_assigned=assigned[:len(cur)], n_valid=cnt.value, valid=va[:n], uv=uv[:n], level=lv[:n])
 
     def logf(self, x):
         """The device restatement of glibc logf, evaluated on this matcher's GPU."""

@@ -1405,6 +1405,62 @@ int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scal
 }  // namespace orbfe
 
 namespace orbfe {
+// SearchByProjection(CurrentFrame, LastFrame, th) / (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) from the projection on
+// (orbfe_search_by_projection_uv_frame's search) on sources that are already in device memory
+// (orbfe_search_by_projection_sources_frame, orbfe_localmap.hip: k_project_sources wrote them earlier on the matcher's stream).
+// Source i: d_xy[2i..], d_level[i], d_valid[i] (0 / 1), d_claim[i] (ORBFE_MP_OBSERVED bit; read only when skip_any_occupied
+// is 0), d_angle[i] (the source frame's resident angles, read by the rotation check), descriptor row d_desc_row[i] of d_desc
+// (32-byte rows; bit 31 clear).  The host reads none of them: the window bound comes from th and the largest of the nlevels
+// scale factors, and every source the projection kernel left valid carries a level inside [0, nlevels).  kp_occupied is host
+// memory (page-locked: read in place).
+int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                                const float* d_xy, const int32_t* d_level, const float* d_angle, const uint8_t* d_valid,
+                                const uint8_t* d_claim, const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, float th,
+                                int max_dist, int skip_any_occupied, int check_orientation, int32_t* kp_assigned, int* nmatches) {
+  const double tEntry = orbfe_matcher::nowMs();
+  if (!m || !f || !nmatches || n_src < 0 || !scale_factors || nlevels < 1 || nlevels > 32 || (f->n && (!kp_occupied || !kp_assigned)) ||
+      (n_src && (!d_xy || !d_level || !d_angle || !d_valid || !d_claim || !d_desc || !d_desc_row))) {
+    set_err("bad argument");
+    return ORBFE_ERR_INVALID;
+  }
+  const int n = f->n;
+  *nmatches = 0;
+  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
+  if (n_src == 0 || n == 0) return ORBFE_OK;
+  if (gpu_readable(kp_occupied, m->device) == 2) { set_err("the occupancy bytes must be host memory"); return ORBFE_ERR_INVALID; }
+  m->tEntry = tEntry;
+  SearchPlan P;
+  int rc = plan_search(m, f, kModeUv, n_src, true, 0, &P);
+  if (rc) return rc;
+  RawQ Q;
+  Q.kind = 2; Q.xy = d_xy; Q.level = d_level; Q.flags = d_valid; Q.angle = d_angle;
+  Q.claimSrc = d_claim; Q.claimMask = ORBFE_MP_OBSERVED;
+  if (skip_any_occupied) { Q.claimSrc = nullptr; Q.claimMask = 0xff; Q.claimConst = 1; }
+  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th;
+  Q.descRow = d_desc_row; Q.descRowWhere = 2;
+  Q.device = true;
+  for (int k = 0; k < 6; k++) Q.where[k] = 2;
+  Q.where[6] = gpu_readable(kp_occupied, m->device);
+  float maxSf = 0.f;
+  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
+  const int* out = nullptr;
+  if ((rc = run_search(m, f, P, d_desc, th * maxSf, 0.f, max_dist, 0.0, check_orientation, &out, nmatches, &Q))) return rc;
+  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
+  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
+  return ORBFE_OK;
+}
+
+// what the projection of a SOURCE frame's keypoints reads of its resident copy (k_project_sources): octaves and angles in
+// keypoint order, the largest octave; and the stream order behind the frame's build
+void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave) {
+  *oct = f->D.oct; *angle = f->D.angle; *maxOctave = f->maxOctave;
+}
+void frame_wait_ready(orbfe_frame* f, hipStream_t st) {
+  if (f->ready && hipStreamWaitEvent(st, f->ready, 0) != hipSuccess) (void)hipGetLastError();   // (the recording stream is gone: the build is complete)
+}
+}  // namespace orbfe
+
+namespace orbfe {
 // mnMinX, mnMaxX, mnMinY, mnMaxY of a resident frame (the projection of orbfe_localmap.hip checks against them)
 void frame_bounds(const orbfe_frame* f, float out[4]) {
   for (int i = 0; i < 4; i++) out[i] = f->bounds[i];

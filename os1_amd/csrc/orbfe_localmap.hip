@@ -24,6 +24,12 @@ int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scal
                              const float* d_xy, const int32_t* d_level, const float* d_viewcos, const uint8_t* d_flags,
                              const uint8_t* d_desc, const int32_t* d_desc_row, int n_mp, float th, float nnratio,
                              int32_t* kp_assigned, int* nmatches);
+int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                                const float* d_xy, const int32_t* d_level, const float* d_angle, const uint8_t* d_valid,
+                                const uint8_t* d_claim, const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, float th,
+                                int max_dist, int skip_any_occupied, int check_orientation, int32_t* kp_assigned, int* nmatches);
+void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
+void frame_wait_ready(orbfe_frame* f, hipStream_t st);
 }  // namespace orbfe
 
 namespace {
@@ -158,6 +164,113 @@ __global__ __launch_bounds__(kProjThreads) void k_project_local_map(ProjParams P
   }
 }
 
+struct SrcParams {
+  const uint8_t* table;
+  const int32_t* rows;         // [n] (page-locked host memory)
+  const uint8_t* flags;        // [n]
+  const int* srcOct;           // [n] the SOURCE frame's resident octaves (mvKeys[i].octave)
+  int n;
+  int mode;                    // ORBFE_SRC_LAST_FRAME / ORBFE_SRC_KEYFRAME
+  OrbfeCamera cam;
+  float minX, maxX, minY, maxY;   // the CURRENT frame's bounds
+  int nlevels;                 // fused call: levels outside [0, nlevels) are taken out of the search and reported
+  // outputs in page-locked host memory (any may be null)
+  uint8_t* valid;
+  float* uv;
+  int32_t* level;
+  // fused call: the search's queries in device memory (null: projection only)
+  float* dxy;
+  int32_t* dlevel;
+  uint8_t* dvalid;
+  uint8_t* dclaim;
+  int32_t* drow;
+  int* blockInfo;              // [2 * blocks] page-locked: sources valid, first valid source with an out-of-range level (-1)
+};
+
+// The projection loops of ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th)
+// (src/ORBmatcher.cc:1313-1347) and (Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist) (:1441-1479), one lane
+// per source keypoint: everything between GetWorldPos() and GetFeaturesInArea.  The source keypoint's angle (the rotation
+// check, :1386 / :1515) is not touched here: the search reads it from the source frame's resident copy.
+__global__ __launch_bounds__(kProjThreads) void k_project_sources(SrcParams P) {
+  __shared__ int firstBad;
+  if (threadIdx.x == 0) firstBad = INT_MAX;
+  __syncthreads();
+  const int i = blockIdx.x * kProjThreads + threadIdx.x;
+  bool valid = false;
+  float u = 0.f, v = 0.f;
+  int lvl = 0, row = 0;
+  unsigned fl = 0;
+  if (i < P.n) {
+    fl = P.flags[i];
+    row = P.rows[i];
+    // :1318-1321 no MapPoint / mvbOutlier[i] (isBad() is not asked); :1445-1447 no MapPoint / isBad() / in sAlreadyFound
+    if (!(fl & (P.mode == ORBFE_SRC_KEYFRAME ? (ORBFE_MP_BAD | ORBFE_MP_SKIP) : ORBFE_MP_SKIP))) {
+      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
+      const float4 a = R[0], b = R[1];
+      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
+      const float maxRaw = b.w, minRaw = b.z;               // mfMaxDistance, mfMinDistance
+      const OrbfeCamera& C = P.cam;
+      // x3Dc = Rcw*x3Dw+tcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
+      float Pc[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const float t = C.Rcw[3 * k] * Pw[0] + C.Rcw[3 * k + 1] * Pw[1] + C.Rcw[3 * k + 2] * Pw[2];
+        Pc[k] = (float)((double)t * 1.0 + (double)C.tcw[k] * 1.0);
+      }
+      const float invzc = (float)(1.0 / (double)Pc[2]);     // :1329 / :1455: a DOUBLE division, rounded to float
+      if (P.mode == ORBFE_SRC_KEYFRAME || !(invzc < 0)) {   // :1332-1333 (the KeyFrame form has no such test)
+        u = C.fx * Pc[0] * invzc + C.cx;
+        v = C.fy * Pc[1] * invzc + C.cy;
+        if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {   // :1339-1342 / :1460-1463
+          if (P.mode == ORBFE_SRC_KEYFRAME) {
+            const float PO[3] = {Pw[0] - C.Ow[0], Pw[1] - C.Ow[1], Pw[2] - C.Ow[2]};   // :1466
+            double s = 0.0;                                 // cv::norm(PO)
+#pragma unroll
+            for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
+            const float dist3D = (float)sqrt(s);
+            const float maxDistance = 1.2f * maxRaw;        // GetMaxDistanceInvariance (MapPoint.cc:364-368)
+            const float minDistance = 0.8f * minRaw;        // GetMinDistanceInvariance (MapPoint.cc:358-362)
+            if (!(dist3D < minDistance || dist3D > maxDistance)) {   // :1473-1474
+              // PredictScale (MapPoint.cc:370-379), converted to int as the host does (an out-of-range value becomes INT_MIN)
+              const float ratio = maxRaw / dist3D;
+              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
+              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+              valid = true;
+            }
+          } else {
+            lvl = P.srcOct[i];                              // nLastOctave = LastFrame.mvKeys[i].octave (:1344)
+            valid = true;
+          }
+          // z = +-0 with x = y = 0 makes u or v NaN, which passes the bounds tests above (every comparison is false).  The
+          // reference then calls GetFeaturesInArea(u, v, ...) (:1349 / :1481) with it, whose cell range (Frame.cc:216-230)
+          // comes out empty (nMaxCellX or nMaxCellY < 0): no candidate, no match.  Such a source is written as invalid.
+          if (!(fabsf(u) <= 3.402823466e+38f) || !(fabsf(v) <= 3.402823466e+38f)) valid = false;
+        }
+      }
+    }
+    if (!valid) { u = 0.f; v = 0.f; lvl = 0; }
+    if (P.valid) P.valid[i] = valid ? 1 : 0;
+    if (P.uv) { P.uv[2 * i] = u; P.uv[2 * i + 1] = v; }
+    if (P.level) P.level[i] = lvl;
+    if (P.dxy) {
+      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
+      const bool levelOk = lvl >= 0 && lvl < P.nlevels;
+      if (valid && !levelOk) atomicMin(&firstBad, i);
+      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
+      P.dlevel[i] = levelOk ? lvl : 0;
+      P.dvalid[i] = valid && levelOk ? 1 : 0;
+      P.dclaim[i] = (uint8_t)(fl & ORBFE_MP_OBSERVED);
+      P.drow[i] = valid ? 2 * row : 0;    // descriptor = 32-byte row 2*row of (table + 32)
+    }
+  }
+  const int count = __syncthreads_count(valid ? 1 : 0);
+  if (threadIdx.x == 0) {
+    P.blockInfo[2 * blockIdx.x] = count;
+    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
+    __threadfence_system();
+  }
+}
+
 __global__ void k_debug_logf(const float* __restrict__ x, int n, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = orbfe::logf_glibc(x[i]);
@@ -275,6 +388,46 @@ void copy_out(const CallArea& A, int n_mp, uint8_t* in_view, float* proj_xy, int
   if (proj_xy) memcpy(proj_xy, A.xy, 8 * (size_t)n_mp);
   if (level) memcpy(level, A.level, 4 * (size_t)n_mp);
   if (view_cos) memcpy(view_cos, A.vcos, 4 * (size_t)n_mp);
+}
+
+}  // namespace
+
+namespace {
+
+// checks shared by the two source-projection calls, then prepare()'s
+int prepare_sources(orbfe_matcher* m, orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map, const OrbfeCamera* cam, int mode,
+                    const int32_t* rows, const uint8_t* flags, int n_src, CallArea* A) {
+  if (!cur || !src) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (mode != ORBFE_SRC_LAST_FRAME && mode != ORBFE_SRC_KEYFRAME) { set_err("mode must be ORBFE_SRC_LAST_FRAME or ORBFE_SRC_KEYFRAME"); return ORBFE_ERR_INVALID; }
+  if (m && orbfe_frame_device(src) != m->device) { set_err("source frame and matcher live on different devices"); return ORBFE_ERR_INVALID; }
+  if (n_src != orbfe_frame_size(src)) {
+    set_err("n_src (%d) is not the source frame's size (%d): source i is its keypoint i", n_src, orbfe_frame_size(src));
+    return ORBFE_ERR_INVALID;
+  }
+  const int rc = prepare(m, cur, map, cam, rows, flags, n_src, A);
+  if (rc) return rc;
+  // LAST_FRAME projects a source whatever ORBFE_MP_BAD says (prepare() let the rows of such sources pass unchecked)
+  if (mode == ORBFE_SRC_LAST_FRAME)
+    for (int i = 0; i < n_src; i++)
+      if ((flags[i] & (ORBFE_MP_BAD | ORBFE_MP_SKIP)) == ORBFE_MP_BAD && (unsigned)rows[i] >= (unsigned)map->capacity) {
+        set_err("source %d: row %d outside the local map (%d rows)", i, rows[i], map->capacity);
+        return ORBFE_ERR_INVALID;
+      }
+  return ORBFE_OK;
+}
+
+SrcParams source_params(orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map, const OrbfeCamera* cam, int mode, int n_src,
+                        const CallArea& A) {
+  SrcParams P{};
+  P.table = map->table.p;
+  P.rows = A.rows; P.flags = A.flags; P.n = n_src;
+  P.mode = mode;
+  P.cam = *cam;
+  float b[4];
+  orbfe::frame_bounds(cur, b);
+  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
+  P.blockInfo = A.blockInfo;
+  return P;
 }
 
 }  // namespace
@@ -407,6 +560,92 @@ int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_loca
   if (bad >= 0) {
     *nmatches = 0;
     set_err("MapPoint %d: predicted level outside [0, %d)", bad, nlevels);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+int orbfe_project_sources(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame, orbfe_local_map* map,
+                          const OrbfeCamera* cam, int mode, const int32_t* rows, const uint8_t* flags, int n_src, uint8_t* valid,
+                          float* uv, int32_t* level, int* n_valid) {
+  CallArea A;
+  int rc = prepare_sources(m, cur_frame, src_frame, map, cam, mode, rows, flags, n_src, &A);
+  if (rc) return rc;
+  if (n_valid) *n_valid = 0;
+  if (n_src == 0) return ORBFE_OK;
+  SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A);
+  const float* srcAngle = nullptr;
+  int maxOctave = 0;
+  orbfe::frame_source_arrays(src_frame, &P.srcOct, &srcAngle, &maxOctave);
+  P.valid = A.inView; P.uv = A.xy; P.level = A.level;
+  orbfe::frame_wait_ready(src_frame, m->stream);
+  hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  copy_out(A, n_src, valid, uv, level, nullptr);
+  if (n_valid) *n_valid = cnt;
+  return ORBFE_OK;
+}
+
+int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame,
+                                             orbfe_local_map* map, const OrbfeCamera* cam, int mode, const int32_t* rows,
+                                             const uint8_t* flags, int n_src, const float* scale_factors, int nlevels,
+                                             const uint8_t* kp_occupied, float th, int max_dist, int check_orientation,
+                                             uint8_t* valid, float* uv, int32_t* level, int32_t* kp_assigned, int* nmatches,
+                                             int* n_valid) {
+  if (!nmatches || !n_valid || !scale_factors || nlevels < 1 || nlevels > 32) {
+    set_err("bad argument (scale factors of 1..32 levels, nmatches and n_valid are required)");
+    return ORBFE_ERR_INVALID;
+  }
+  CallArea A;
+  int rc = prepare_sources(m, cur_frame, src_frame, map, cam, mode, rows, flags, n_src, &A);
+  if (rc) return rc;
+  const int n = orbfe_frame_size(cur_frame);
+  if (n && (!kp_occupied || !kp_assigned)) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  *nmatches = 0;
+  *n_valid = 0;
+  if (n_src == 0) {
+    for (int i = 0; i < n; i++) kp_assigned[i] = -1;
+    return ORBFE_OK;
+  }
+  SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A);
+  const float* srcAngle = nullptr;
+  int maxOctave = 0;
+  orbfe::frame_source_arrays(src_frame, &P.srcOct, &srcAngle, &maxOctave);
+  // nLastOctave indexes mvScaleFactors (:1347): refused up front from the source frame's largest octave
+  if (mode == ORBFE_SRC_LAST_FRAME && maxOctave >= nlevels) {
+    set_err("the source frame holds a keypoint of octave %d: outside [0, %d)", maxOctave, nlevels);
+    return ORBFE_ERR_INVALID;
+  }
+  const size_t c = (size_t)n_src;
+  const size_t oXY = 0, oL = al(8 * c), oR = oL + al(4 * c), oV = oR + al(4 * c), oC = oV + al(c), total = oC + al(c);
+  if ((rc = map->q.ensure(total))) return rc;
+  uint8_t* D = map->q.p;
+  if (valid) P.valid = A.inView;
+  if (uv) P.uv = A.xy;
+  if (level) P.level = A.level;
+  P.nlevels = nlevels;
+  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.drow = (int32_t*)(D + oR); P.dvalid = D + oV; P.dclaim = D + oC;
+  orbfe::frame_wait_ready(src_frame, m->stream);
+  hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
+  if ((rc = orbfe::sbp_uv_frame_device_queries(m, cur_frame, scale_factors, nlevels, kp_occupied, P.dxy, P.dlevel, srcAngle, P.dvalid,
+                                               P.dclaim, map->table.p + 32, P.drow, n_src, th, max_dist,
+                                               mode == ORBFE_SRC_KEYFRAME ? 1 : 0, check_orientation, kp_assigned, nmatches))) {
+    (void)hipStreamSynchronize(m->stream);
+    return rc;
+  }
+  if (n == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  *n_valid = cnt;
+  copy_out(A, n_src, valid, uv, level, nullptr);
+  if (bad >= 0) {
+    *nmatches = 0;
+    set_err("source %d: predicted level outside [0, %d)", bad, nlevels);
     return ORBFE_ERR_INVALID;
   }
   return ORBFE_OK;
