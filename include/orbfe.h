@@ -656,6 +656,70 @@ int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_
                                              const uint8_t* kp_occupied, float th, int max_dist, int check_orientation,
                                              uint8_t* valid, float* uv, int32_t* level, int32_t* kp_assigned, int* nmatches,
                                              int* n_valid);
+/* The projection loops of the four KEYFRAME-side searches of LocalMapping and LoopClosing, on the GPU: everything between
+ * GetWorldPos() and KeyFrame::GetFeaturesInArea in
+ *   int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, th)   (src/ORBmatcher.cc:285-398;
+ *                                                                                             projection :316-357)
+ *   int ORBmatcher::Fuse(KeyFrame* pKF, vpMapPoints, th)                                      (:806-939; :833-873)
+ *   int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, vpPoints, th, vpReplacePoint)            (:941-1064; :973-1015)
+ *   int ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th), each direction  (:1066-1290; :1122-1155, :1202-1235)
+ * OrbfeKeyFrameProjection describes one such loop.  The caller computes every matrix ONCE per call, with the reference's own
+ * cv::Mat expressions (Scw's decomposition :293-298, s12*R12, (1.0/s12)*R12.t(), -sR21*t12, GetCameraCenter()); nothing is
+ * recomputed on the device.
+ *   R, t            : p = R*p3Dw + t (Rcw, tcw; R1w, t1w resp. R2w, t2w for SearchBySim3)
+ *   has_second, sR, t2 : SearchBySim3 only: p = sR*p + t2 on the float result of the first (sR21, t21 resp. sR12, t12)
+ *   Ow              : the camera centre PO = p3Dw - Ow is taken from (not read when distance_from_camera_point is set)
+ *   fx, fy, cx, cy  : the intrinsics u = fx*x + cx, v = fy*y + cy use -- apart from the searched keyframe on purpose:
+ *                     SearchBySim3 uses pKF1's in both directions (:1069-1072)
+ *   logScaleFactor  : the SEARCHED keyframe's mfLogScaleFactor (PredictScale)
+ *   invz_in_double  : 0: `1/p3Dc.at<float>(2)`, a float division (:326, :840); 1: `1.0/...`, a double division rounded to
+ *                     float (:983, :1130, :1210)
+ *   check_viewing_angle : 1: reject PO.dot(Pn) < 0.5*dist (:349, :865, :1006); SearchBySim3 has no such test
+ *   distance_from_camera_point : 0: dist3D = cv::norm(p3Dw - Ow); 1: cv::norm of the transformed point p itself (:1143,
+ *                     :1223; not together with check_viewing_angle) */
+typedef struct OrbfeKeyFrameProjection {
+  float R[9];
+  float t[3];
+  int has_second;
+  float sR[9];
+  float t2[3];
+  float Ow[3];
+  float fx, fy, cx, cy;
+  float logScaleFactor;
+  int invz_in_double;
+  int check_viewing_angle;
+  int distance_from_camera_point;
+} OrbfeKeyFrameProjection;
+/* MapPoint i = row rows[i] of `map`, i < n, projected into the resident keyframe kf_frame (its bounds are the ones
+ * KeyFrame::IsInImage, src/KeyFrame.cc:678-681, tests: u >= mnMinX && u < mnMaxX && v >= mnMinY && v < mnMaxY, half-open).
+ * flags[i]: ORBFE_MP_BAD = isBad(); ORBFE_MP_SKIP = whatever else keeps the loop from projecting it (in spAlreadyFound, NULL,
+ * IsInKeyFrame(pKF), vbAlreadyMatched).  Either bit: not projected, and the point may carry any row.  scale_factors = the
+ * searched keyframe's mvScaleFactors (1..32 levels).  Per point:
+ *   valid [n]  : 1 = the point reaches GetFeaturesInArea      uv [2*n] : the projection u, v
+ *   level [n]  : nPredictedLevel (PredictScale, NOT clamped: reported as it is)
+ *   radius [n] : th * scale_factors[level] (0 where the level lies outside [0, nlevels))
+ * bit for bit the reference's values (float cv::Mat arithmetic, x = p[0]*invz rounded before the multiplication by fx, glibc
+ * logf); 0 where valid is 0.  A projection that is not finite (z = +-0) fails IsInImage by itself.  *n_valid = valid points.
+ * Any output may be NULL.  rows and flags are host memory; a row outside [0, capacity) of a point that is projected fails the
+ * call with ORBFE_ERR_INVALID.  Returns when the outputs are written. */
+int orbfe_project_keyframe(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj,
+                           const int32_t* rows, const uint8_t* flags, int n, const float* scale_factors, int nlevels, float th,
+                           uint8_t* valid, float* uv, int32_t* level, float* radius, int* n_valid);
+/* The projection of orbfe_project_keyframe followed by the projected best-match loop (orbfe_search_projected_frame: :357-392,
+ * :873-936, :1015-1050, :1155-1185 / :1235-1265) in ONE submission on the matcher's stream: the projection kernel leaves uv,
+ * level, radius, valid and the descriptor row in device memory and the search reads them there; no copy command runs between
+ * the kernels, and per point only rows[i] and flags[i] cross PCIe.  kp_skip, claim, inv_level_sigma2 (nlevels values or NULL)
+ * with chi2, max_dist, best_idx [n], best_dist [n] (optional) and nmatches as for orbfe_search_projected_frame.  valid, uv,
+ * level: optional outputs (NULL: not returned).  Results are those of orbfe_project_keyframe followed by
+ * orbfe_search_projected_frame on the same inputs.  n == 0 or an empty keyframe: ORBFE_OK, every best_idx -1.
+ * LEVEL CONTRACT: a valid point whose predicted level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID, as in
+ * orbfe_search_local_points_frame: the projection kernel takes it out of the search before anything is indexed with that
+ * level; the outputs are then unspecified, and the matcher, frame and table stay usable. */
+int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map,
+                                          const OrbfeKeyFrameProjection* proj, const int32_t* rows, const uint8_t* flags, int n,
+                                          const float* scale_factors, int nlevels, float th, const uint8_t* kp_skip, int claim,
+                                          const float* inv_level_sigma2, double chi2, int max_dist, uint8_t* valid, float* uv,
+                                          int32_t* level, int32_t* best_idx, int32_t* best_dist, int* nmatches, int* n_valid);
 
 /* Rounds the bookkeeping kernel of the last `_frame` search needed -- the most any chunk of 2 048 consecutive queries took
  * (negative: a chunk hit the bound ORBFE_RESOLVE_MAX_ROUNDS, default 48, and a serial pass on the device finished it). */

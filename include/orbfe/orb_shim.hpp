@@ -1231,6 +1231,243 @@ inline int SearchBySim3(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, s
   return nFound;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The four keyframe-side searches above with their projection loops on the GPU (orbfe_search_projected_keyframe_frame): the
+// MapPoints' positions, normals, depth ranges and descriptors are rows of the context's local-map table -- the rows
+// SearchLocalPoints and the two frame-side forms use, so a MapPoint known to any of them keeps ONE row, and only rows whose
+// content changed are sent.  Per call and MapPoint one row number and one flag byte cross PCIe.  The matrices are computed
+// once per call with Ops, as in the functions above; `geometry` is SearchLocalPoints' functor.  The bookkeeping that follows
+// the search is the functions' own, unchanged.  With the frame cache off (ctx.resident returns null) they ARE the functions
+// above.  The fused call refuses a valid point whose predicted level lies outside the keyframe's pyramid (the reference
+// would index mvScaleFactors out of range with it).
+// ---------------------------------------------------------------------------------------------------------------
+namespace detail {
+template <class KeyFrameT>
+inline void keyFrameProjection(KeyFrameT* intr, KeyFrameT* to, const float R[9], const float t[3], const float* Ow,
+                               OrbfeKeyFrameProjection& P) {
+  std::memset(&P, 0, sizeof P);
+  std::memcpy(P.R, R, sizeof P.R);
+  std::memcpy(P.t, t, sizeof P.t);
+  if (Ow) std::memcpy(P.Ow, Ow, sizeof P.Ow);
+  P.fx = intr->fx; P.fy = intr->fy; P.cx = intr->cx; P.cy = intr->cy;
+  P.logScaleFactor = to->mfLogScaleFactor;
+}
+template <class KeyFrameT>
+inline bool fusedKeyFrameLevels(KeyFrameT* pKF, bool chi2) {
+  const size_t nl = pKF->mvScaleFactors.size();
+  return nl >= 1 && nl <= 32 && (!chi2 || pKF->mvInvLevelSigma2.size() == nl);
+}
+// projection + windows + best match of ns MapPoints (rows / flags) into the resident keyframe rf; bestIdx[ns]
+template <class KeyFrameT>
+inline int searchProjectedKeyFrame(MatcherContext& ctx, orbfe_frame* rf, KeyFrameT* to, const OrbfeKeyFrameProjection& P,
+                                   const int32_t* rows, const uint8_t* flags, int ns, float th, const uint8_t* kp_skip, int claim,
+                                   bool chi2, int max_dist, int32_t* bestIdx) {
+  int nm = 0, nValid = 0;
+  check(orbfe_search_projected_keyframe_frame(ctx.get(), rf, ctx.localMap(), &P, rows, flags, ns, to->mvScaleFactors.data(),
+                                              (int)to->mvScaleFactors.size(), th, kp_skip, claim,
+                                              chi2 ? to->mvInvLevelSigma2.data() : nullptr, 5.99, max_dist, nullptr, nullptr, nullptr,
+                                              bestIdx, nullptr, &nm, &nValid));
+  return nm;
+}
+}  // namespace detail
+
+// int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+//                                    vector<MapPoint*>& vpMatched, int th)   (ORBmatcher.cc:285-398)
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
+inline int SearchByProjectionScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
+                                 std::vector<MapPointT*>& vpMatched, int th, GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return SearchByProjection<Ops>(ctx, pKF, Scw, vpPoints, vpMatched, th);
+  float Rcw[9], tcw[3], Ow[3];
+  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
+  std::vector<MapPointT*> found(vpMatched.begin(), vpMatched.end());     // spAlreadyFound (:301-302)
+  std::sort(found.begin(), found.end());
+  const int ns = (int)vpPoints.size();
+  uint8_t* skip = ctx.scratch<uint8_t>(0, vpMatched.size(), true);
+  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    MapPointT* pMP = vpPoints[i];
+    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                                        // :312-313
+    if (std::binary_search(found.begin(), found.end(), pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
+    rows[i] = detail::sourceRow(ctx, pMP, geometry);
+  }
+  ctx.localMapCommit();
+  for (size_t i = 0; i < vpMatched.size(); i++) skip[i] = vpMatched[i] ? 1 : 0;                     // :366-367
+  OrbfeKeyFrameProjection P;
+  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+  P.invz_in_double = 0; P.check_viewing_angle = 1;
+  const int nmatches = detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, (float)th, skip, /*claim*/ 1, false,
+                                                       /*TH_LOW*/ 50, bestIdx);
+  for (int i = 0; i < ns; i++)
+    if (bestIdx[i] >= 0) vpMatched[bestIdx[i]] = vpPoints[i];
+  return nmatches;
+}
+
+// int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th)   (ORBmatcher.cc:806-939).
+// The flags are taken at entry, which is exact: a point that is bad stays bad, and a point that sits in the keyframe at entry
+// can only leave it by being Replace()d, which makes it bad -- the reference's live check (:822-823) skips it either way.
+// The replay keeps the live checks for points that change DURING the call.
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MapPointT, class GeometryFn>
+inline int FuseKeyFrame(MatcherContext& ctx, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th,
+                        GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, true) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return Fuse<Ops>(ctx, pKF, vpMapPoints, th);
+  float Rcw[9], tcw[3], Ow[3];
+  detail::mat33(pKF->GetRotation(), Rcw);
+  detail::vec3(pKF->GetTranslation(), tcw);
+  detail::vec3(pKF->GetCameraCenter(), Ow);
+  const int ns = (int)vpMapPoints.size();
+  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    MapPointT* pMP = vpMapPoints[i];
+    if (!pMP) { flags[i] = ORBFE_MP_SKIP; continue; }
+    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }
+    if (pMP->IsInKeyFrame(pKF)) { flags[i] = ORBFE_MP_SKIP; continue; }
+    rows[i] = detail::sourceRow(ctx, pMP, geometry);
+  }
+  ctx.localMapCommit();
+  OrbfeKeyFrameProjection P;
+  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+  P.invz_in_double = 0; P.check_viewing_angle = 1;
+  detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, th, nullptr, 0, /*chi2 gate :896-903*/ true, /*TH_LOW*/ 50, bestIdx);
+  int nFused = 0;
+  for (int i = 0; i < ns; i++) {
+    MapPointT* pMP = vpMapPoints[i];
+    if (!pMP) continue;
+    if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+    if (bestIdx[i] < 0) continue;
+    const int best = bestIdx[i];
+    MapPointT* pMPinKF = pKF->GetMapPoint(best);
+    if (pMPinKF) {
+      if (!pMPinKF->isBad()) {
+        if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+        else pMPinKF->Replace(pMP);
+      }
+    } else {
+      pMP->AddObservation(pKF, best);
+      pKF->AddMapPoint(pMP, best);
+    }
+    nFused++;
+  }
+  return nFused;
+}
+
+// int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th,
+//                      vector<MapPoint*>& vpReplacePoint)   (ORBmatcher.cc:941-1064)
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
+inline int FuseScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints, float th,
+                   std::vector<MapPointT*>& vpReplacePoint, GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return Fuse<Ops>(ctx, pKF, Scw, vpPoints, th, vpReplacePoint);
+  float Rcw[9], tcw[3], Ow[3];
+  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
+  const auto spAlreadyFound = pKF->GetMapPoints();
+  const int ns = (int)vpPoints.size();
+  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    MapPointT* pMP = vpPoints[i];
+    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                        // :968-969
+    if (spAlreadyFound.count(pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
+    rows[i] = detail::sourceRow(ctx, pMP, geometry);
+  }
+  ctx.localMapCommit();
+  OrbfeKeyFrameProjection P;
+  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+  P.invz_in_double = 1; P.check_viewing_angle = 1;
+  detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, th, nullptr, 0, false, /*TH_LOW*/ 50, bestIdx);
+  int nFused = 0;
+  for (int i = 0; i < ns; i++) {
+    if (bestIdx[i] < 0) continue;
+    MapPointT* pMP = vpPoints[i];
+    const int best = bestIdx[i];
+    MapPointT* pMPinKF = pKF->GetMapPoint(best);     // live: an earlier point of this call may have been added here
+    if (pMPinKF) {
+      if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
+    } else {
+      pMP->AddObservation(pKF, best);
+      pKF->AddMapPoint(pMP, best);
+    }
+    nFused++;
+  }
+  return nFused;
+}
+
+// int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12,
+//                              const cv::Mat& R12, const cv::Mat& t12, const float th)   (ORBmatcher.cc:1066-1290):
+// two fused calls, one per direction, then the vnMatch agreement on the host.
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
+inline int SearchBySim3Device(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12,
+                              const float& s12, const MatT& R12m, const MatT& t12m, const float th, GeometryFn geometry) {
+  const bool levels = detail::fusedKeyFrameLevels(pKF1, false) && detail::fusedKeyFrameLevels(pKF2, false);
+  orbfe_frame* rf2 = levels ? ctx.resident(*pKF2, 1) : nullptr;
+  orbfe_frame* rf1 = rf2 ? ctx.resident(*pKF1, 1) : nullptr;   // (never evicts rf2: the two most recent frames stay)
+  if (!rf1 || !rf2) return SearchBySim3<Ops>(ctx, pKF1, pKF2, vpMatches12, s12, R12m, t12m, th);
+  float R1w[9], t1w[3], R2w[9], t2w[3], R12[9], t12[3], sR12[9], sR21[9], R12t[9], t21[3];
+  detail::mat33(pKF1->GetRotation(), R1w); detail::vec3(pKF1->GetTranslation(), t1w);
+  detail::mat33(pKF2->GetRotation(), R2w); detail::vec3(pKF2->GetTranslation(), t2w);
+  detail::mat33(R12m, R12); detail::vec3(t12m, t12);
+  Ops::scale(R12, 9, (double)s12, sR12);                                  // s12*R12
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R12t[3 * r + c] = R12[3 * c + r];
+  Ops::scale(R12t, 9, 1.0 / (double)s12, sR21);                           // (1.0/s12)*R12.t()
+  Ops::gemm3(sR21, t12, -1.0, nullptr, 0.0, t21);                         // -sR21*t12
+  const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
+  const int N1 = (int)vpMapPoints1.size(), N2 = (int)vpMapPoints2.size();
+  std::vector<bool> vbAlreadyMatched1(N1, false), vbAlreadyMatched2(N2, false);
+  for (int i = 0; i < N1; i++) {
+    MapPointT* pMP = vpMatches12[i];
+    if (pMP) {
+      vbAlreadyMatched1[i] = true;
+      const int idx2 = pMP->GetIndexInKeyFrame(pKF2);
+      if (idx2 >= 0 && idx2 < N2) vbAlreadyMatched2[idx2] = true;
+    }
+  }
+  // one direction: points of `from` (camera pose Rfw, tfw) through (sR, t) into `to`, pKF1's intrinsics in both (:1069-1072)
+  auto direction = [&](const std::vector<MapPointT*>& pts, const std::vector<bool>& already, const float* Rfw, const float* tfw,
+                       const float* sR, const float* tt, KeyFrameT* to, orbfe_frame* rf, std::vector<int>& vnMatch) {
+    const int ns = (int)pts.size();
+    uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+    int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
+    int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
+    ctx.localMapBegin((size_t)ns);
+    for (int i = 0; i < ns; i++) {
+      MapPointT* pMP = pts[i];
+      if (!pMP || already[i]) { flags[i] = ORBFE_MP_SKIP; continue; }
+      if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }
+      rows[i] = detail::sourceRow(ctx, pMP, geometry);
+    }
+    ctx.localMapCommit();
+    OrbfeKeyFrameProjection P;
+    detail::keyFrameProjection(pKF1, to, Rfw, tfw, nullptr, P);
+    P.has_second = 1;
+    std::memcpy(P.sR, sR, sizeof P.sR);
+    std::memcpy(P.t2, tt, sizeof P.t2);
+    P.invz_in_double = 1; P.check_viewing_angle = 0; P.distance_from_camera_point = 1;
+    detail::searchProjectedKeyFrame(ctx, rf, to, P, rows, flags, ns, th, nullptr, 0, false, /*TH_HIGH*/ 100, bestIdx);
+    vnMatch.assign(bestIdx, bestIdx + ns);
+  };
+  std::vector<int> vnMatch1, vnMatch2;
+  direction(vpMapPoints1, vbAlreadyMatched1, R1w, t1w, sR21, t21, pKF2, rf2, vnMatch1);
+  direction(vpMapPoints2, vbAlreadyMatched2, R2w, t2w, sR12, t12, pKF1, rf1, vnMatch2);
+  int nFound = 0;
+  for (int i1 = 0; i1 < N1; i1++) {
+    const int idx2 = vnMatch1[i1];
+    if (idx2 >= 0) {
+      const int idx1 = vnMatch2[idx2];
+      if (idx1 == i1) { vpMatches12[i1] = vpMapPoints2[idx2]; nFound++; }
+    }
+  }
+  return nFound;
+}
+
 // void Frame::UndistortKeyPoints()   (Frame.cc:286-320) and void Frame::ComputeImageBounds(const cv::Mat& imLeft)
 // (:322-353), both camera models (camaraModo 0 = pinhole with mDistCoef through cv::undistortPoints, 1 = os1's
 // equidistant fisheye).  K = {fx, fy, cx, cy}; dist = mDistCoef (4, 5 or 8 floats; ignored for mode 1).

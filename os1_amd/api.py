@@ -189,6 +189,9 @@ def load_library():
     L.orbfe_project_sources.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_search_by_projection_sources_frame.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, cf, ci, ci, vp, vp, vp,
                                                            vp, C.POINTER(ci), C.POINTER(ci)]
+    L.orbfe_project_keyframe.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, cf, vp, vp, vp, vp, C.POINTER(ci)]
+    L.orbfe_search_projected_keyframe_frame.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, cf, vp, ci, vp, C.c_double, ci, vp, vp,
+                                                        vp, vp, vp, C.POINTER(ci), C.POINTER(ci)]
     _lib = L
     return L
 
@@ -409,6 +412,34 @@ class Camera(C.Structure):
         c.Ow[:] = [float(v) for v in np.asarray(Ow, np.float32).ravel()]
         c.fx, c.fy, c.cx, c.cy = float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy))
         c.logScaleFactor = float(np.float32(log_scale_factor))
+        return c
+
+
+class KeyFrameProjection(C.Structure):
+    """OrbfeKeyFrameProjection: one projection loop of SearchByProjection(KeyFrame*, Scw), Fuse, Fuse(Scw) or a direction of
+    SearchBySim3 -- the matrices the caller computed once, the intrinsics, and the three switches that tell the loops apart."""
+    _fields_ = [('R', C.c_float * 9), ('t', C.c_float * 3), ('has_second', C.c_int), ('sR', C.c_float * 9), ('t2', C.c_float * 3),
+                ('Ow', C.c_float * 3), ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float),
+                ('logScaleFactor', C.c_float), ('invz_in_double', C.c_int), ('check_viewing_angle', C.c_int),
+                ('distance_from_camera_point', C.c_int)]
+
+    @classmethod
+    def make(cls, R, t, fx, fy, cx, cy, log_scale_factor, Ow=None, sR=None, t2=None, invz_in_double=False,
+             check_viewing_angle=True, distance_from_camera_point=False):
+        """sR, t2: the second transform (SearchBySim3); Ow may be None only with distance_from_camera_point"""
+        c = cls()
+        f = lambda a: [float(v) for v in np.asarray(a, np.float32).ravel()]
+        c.R[:], c.t[:] = f(R), f(t)
+        c.has_second = 0 if sR is None else 1
+        if sR is not None:
+            c.sR[:], c.t2[:] = f(sR), f(t2)
+        if Ow is not None:
+            c.Ow[:] = f(Ow)
+        c.fx, c.fy, c.cx, c.cy = float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy))
+        c.logScaleFactor = float(np.float32(log_scale_factor))
+        c.invz_in_double = int(bool(invz_in_double))
+        c.check_viewing_angle = int(bool(check_viewing_angle))
+        c.distance_from_camera_point = int(bool(distance_from_camera_point))
         return c
 
 
@@ -703,6 +734,47 @@ class Matcher:
                                                                n, _p(sf), len(sf), _p(occ), th, int(max_dist), 1 if check_ori else 0,
                                                                _p(va), _p(uv), _p(lv), _p(assigned), C.byref(nm), C.byref(cnt)))
         return dict(nmatches=nm.value, kp_assigned=assigned[:len(cur)], n_valid=cnt.value, valid=va[:n], uv=uv[:n], level=lv[:n])
+
+    def project_keyframe(self, kf, lmap, proj, rows, flags, scale_factors, th):
+        """The projection loop of SearchByProjection(KeyFrame*, Scw) / Fuse / Fuse(Scw) / one direction of SearchBySim3 that
+        `proj` (a KeyFrameProjection) describes: MapPoint i = row rows[i] of `lmap` (flags: MP_SKIP / MP_BAD skip it) into the
+        resident keyframe `kf`: dict of valid, uv, level, radius arrays and n_valid."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        n = len(rows)
+        va = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        ra = np.zeros(max(n, 1), np.float32)
+        cnt = C.c_int(0)
+        _check(self.L.orbfe_project_keyframe(self.h, kf.h, lmap.h, C.byref(proj), _p(rows), _p(flags), n, _p(sf), len(sf), th, _p(va),
+                                             _p(uv), _p(lv), _p(ra), C.byref(cnt)))
+        return dict(valid=va[:n], uv=uv[:n], level=lv[:n], radius=ra[:n], n_valid=cnt.value)
+
+    def search_projected_keyframe(self, kf, lmap, proj, rows, flags, scale_factors, th, kp_skip=None, claim=False, inv_sigma2=None,
+                                  chi2=5.99, max_dist=50):
+        """project_keyframe + the projected best-match loop (search_projected) in one submission: dict of nmatches, best_idx,
+        best_dist, n_valid and the projection's valid, uv, level."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        skip = None if kp_skip is None else np.ascontiguousarray(kp_skip, np.uint8)
+        inv = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+        if inv is not None and len(inv) != len(sf):
+            raise ValueError('inv_sigma2 holds one value per level')
+        n = len(rows)
+        va = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float32)
+        lv = np.zeros(max(n, 1), np.int32)
+        bi = np.full(max(n, 1), -1, np.int32)
+        bd = np.full(max(n, 1), -1, np.int32)
+        nm, cnt = C.c_int(0), C.c_int(0)
+        _check(self.L.orbfe_search_projected_keyframe_frame(self.h, kf.h, lmap.h, C.byref(proj), _p(rows), _p(flags), n, _p(sf),
+                                                            len(sf), th, None if skip is None else _p(skip), int(claim),
+                                                            None if inv is None else _p(inv), chi2, int(max_dist), _p(va), _p(uv),
+                                                            _p(lv), _p(bi), _p(bd), C.byref(nm), C.byref(cnt)))
+        return dict(nmatches=nm.value, best_idx=bi[:n], best_dist=bd[:n], n_valid=cnt.value, valid=va[:n], uv=uv[:n], level=lv[:n])
 
     def logf(self, x):
         """The device restatement of glibc logf, evaluated on this matcher's GPU."""

@@ -886,7 +886,7 @@ int run_search(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const uint
       if (withOcc) { M.bitSrc[1] = W.occ; M.bitDst[1] = dOcc; M.bitN[1] = n; }
       qangleDev = W.angle;
     }
-    M.invSigma2 = P.invSigma2 ? (const float*)(Dq + P.oSig) : nullptr;
+    M.invSigma2 = P.invSigma2 ? (const float*)((devQ ? m->h_q.p : Dq) + P.oSig) : nullptr;   // (device queries: nothing is uploaded, the arena is read in place)
     M.chi2 = chi2;
     M.packOctave = 1;
     M.codeMode = P.mode; M.nnratio = nnratio; M.maxDist = maxDist;
@@ -1447,6 +1447,54 @@ int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* s
   if ((rc = run_search(m, f, P, d_desc, th * maxSf, 0.f, max_dist, 0.0, check_orientation, &out, nmatches, &Q))) return rc;
   memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
   m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
+  return ORBFE_OK;
+}
+
+// The projected best-match loop (orbfe_search_projected_frame's search) on sources that are already in device memory
+// (orbfe_search_projected_keyframe_frame, orbfe_localmap.hip: k_project_keyframe wrote them earlier on the matcher's stream).
+// Source i: d_xy[2i..], d_level[i], d_radius[i], d_valid[i] (0 / 1), descriptor row d_desc_row[i] of d_desc (32-byte rows; bit
+// 31 clear).  The host reads none of them: the window bound comes from th and the largest of the nlevels scale factors (every
+// radius the kernel wrote is th * scale_factors[level] with a level inside [0, nlevels)).  kp_skip (optional) is host memory
+// (page-locked: read in place); inv_level_sigma2 (optional) holds nlevels values.
+int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, float th,
+                                          const float* d_xy, const int32_t* d_level, const float* d_radius, const uint8_t* d_valid,
+                                          const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, const uint8_t* kp_skip, int claim,
+                                          const float* inv_level_sigma2, double chi2, int max_dist, int32_t* best_idx, int32_t* best_dist,
+                                          int* nmatches) {
+  const double tEntry = orbfe_matcher::nowMs();
+  if (!m || !f || !nmatches || n_src < 0 || !scale_factors || nlevels < 1 || nlevels > 32 ||
+      (n_src && (!d_xy || !d_level || !d_radius || !d_valid || !d_desc || !d_desc_row || !best_idx))) {
+    set_err("bad argument");
+    return ORBFE_ERR_INVALID;
+  }
+  const int n = f->n;
+  *nmatches = 0;
+  for (int i = 0; i < n_src; i++) {
+    best_idx[i] = -1;
+    if (best_dist) best_dist[i] = -1;
+  }
+  if (n_src == 0 || n == 0) return ORBFE_OK;
+  if (inv_level_sigma2 && f->maxOctave >= nlevels) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
+  if (kp_skip && gpu_readable(kp_skip, m->device) == 2) { set_err("the skip bytes must be host memory"); return ORBFE_ERR_INVALID; }
+  m->tEntry = tEntry;
+  SearchPlan P;
+  int rc = plan_search(m, f, kModeProjected, n_src, kp_skip != nullptr, inv_level_sigma2 ? nlevels : 0, &P);
+  if (rc) return rc;
+  RawQ Q;
+  Q.kind = 3; Q.xy = d_xy; Q.level = d_level; Q.aux = d_radius; Q.flags = d_valid;
+  Q.claimConst = claim ? 1 : 0;
+  Q.occ = kp_skip;
+  Q.descRow = d_desc_row; Q.descRowWhere = 2;
+  Q.device = true;
+  for (int k = 0; k < 4; k++) Q.where[k] = 2;
+  Q.where[6] = kp_skip ? gpu_readable(kp_skip, m->device) : 0;
+  float maxSf = 0.f;
+  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
+  if (inv_level_sigma2) memcpy(P.invSigma2, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
+  const int* out = nullptr;
+  if ((rc = run_search(m, f, P, d_desc, th * maxSf, 0.f, max_dist, chi2, 0, &out, nmatches, &Q))) return rc;
+  memcpy(best_idx, out, sizeof(int32_t) * (size_t)n_src);
+  if (best_dist) memcpy(best_dist, out + n_src, sizeof(int32_t) * (size_t)n_src);
   return ORBFE_OK;
 }
 

@@ -1,5 +1,7 @@
 // orbfe_localmap.hip -- the local map on the device: Frame::isInFrustum over Tracking's local MapPoints, and that
-// projection fused with SearchByProjection(F, vpLocalMapPoints, th).
+// projection fused with SearchByProjection(F, vpLocalMapPoints, th); the projection loops of the other searches that read the
+// same table (k_project_sources: last frame / keyframe into the current frame; k_project_keyframe: MapPoints into a keyframe
+// for SearchByProjection(KeyFrame*, Scw), Fuse, Fuse(Scw) and SearchBySim3), each fused with its search in the same way.
 //
 // Tracking::SearchLocalPoints (reference src/Tracking.cc:798-825) calls Frame::isInFrustum(pMP, 0.5) (src/Frame.cc:151-207)
 // for every local MapPoint on the tracking thread, then ORBmatcher::SearchByProjection on the ones in view.  Here the
@@ -28,6 +30,11 @@ int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* s
                                 const float* d_xy, const int32_t* d_level, const float* d_angle, const uint8_t* d_valid,
                                 const uint8_t* d_claim, const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, float th,
                                 int max_dist, int skip_any_occupied, int check_orientation, int32_t* kp_assigned, int* nmatches);
+int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, float th,
+                                          const float* d_xy, const int32_t* d_level, const float* d_radius, const uint8_t* d_valid,
+                                          const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, const uint8_t* kp_skip, int claim,
+                                          const float* inv_level_sigma2, double chi2, int max_dist, int32_t* best_idx, int32_t* best_dist,
+                                          int* nmatches);
 void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
 void frame_wait_ready(orbfe_frame* f, hipStream_t st);
 }  // namespace orbfe
@@ -271,6 +278,131 @@ __global__ __launch_bounds__(kProjThreads) void k_project_sources(SrcParams P) {
   }
 }
 
+struct KfParams {
+  const uint8_t* table;
+  const int32_t* rows;         // [n] (page-locked host memory)
+  const uint8_t* flags;        // [n]
+  int n;
+  OrbfeKeyFrameProjection proj;
+  float minX, maxX, minY, maxY;   // the TARGET keyframe's bounds
+  int nlevels;
+  float th;
+  float sf[32];                // the target keyframe's mvScaleFactors
+  // outputs in page-locked host memory (any may be null)
+  uint8_t* valid;
+  float* uv;
+  int32_t* level;
+  float* radius;
+  // fused call: the search's queries in device memory (null: projection only)
+  float* dxy;
+  int32_t* dlevel;
+  float* dradius;
+  uint8_t* dvalid;
+  int32_t* drow;
+  int* blockInfo;              // [2 * blocks] page-locked: points valid, first valid point with an out-of-range level (-1)
+};
+
+// The projection loops of the keyframe-side searches, one lane per listed MapPoint: everything between GetWorldPos() and
+// KeyFrame::GetFeaturesInArea in ORBmatcher::SearchByProjection(KeyFrame*, Scw, ...) (src/ORBmatcher.cc:316-357),
+// Fuse(KeyFrame*, vpMapPoints, th) (:833-873), Fuse(KeyFrame*, Scw, ...) (:973-1015) and both directions of SearchBySim3
+// (:1122-1155, :1202-1235).  The host has computed every matrix once per call; what differs between the four is chosen by
+// the three switches of OrbfeKeyFrameProjection.
+__global__ __launch_bounds__(kProjThreads) void k_project_keyframe(KfParams P) {
+  __shared__ int firstBad;
+  if (threadIdx.x == 0) firstBad = INT_MAX;
+  __syncthreads();
+  const int i = blockIdx.x * kProjThreads + threadIdx.x;
+  bool valid = false;
+  float u = 0.f, v = 0.f, radius = 0.f;
+  int lvl = 0, row = 0;
+  if (i < P.n) {
+    const unsigned fl = P.flags[i];
+    row = P.rows[i];
+    if (!(fl & (ORBFE_MP_BAD | ORBFE_MP_SKIP))) {          // isBad() / spAlreadyFound, IsInKeyFrame, vbAlreadyMatched, no MapPoint
+      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
+      const float4 a = R[0], b = R[1];
+      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
+      const float Pn[3] = {a.w, b.x, b.y};                  // GetNormal()
+      const float minRaw = b.z, maxRaw = b.w;               // mfMinDistance, mfMaxDistance
+      const OrbfeKeyFrameProjection& C = P.proj;
+      // p3Dc = Rcw*p3Dw+tcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
+      float p[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const float t = C.R[3 * k] * Pw[0] + C.R[3 * k + 1] * Pw[1] + C.R[3 * k + 2] * Pw[2];
+        p[k] = (float)((double)t * 1.0 + (double)C.t[k] * 1.0);
+      }
+      if (C.has_second) {                                   // p3Dc2 = sR21*p3Dc1+t21 (:1124) / p3Dc1 = sR12*p3Dc2+t12 (:1204)
+        float q[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const float t = C.sR[3 * k] * p[0] + C.sR[3 * k + 1] * p[1] + C.sR[3 * k + 2] * p[2];
+          q[k] = (float)((double)t * 1.0 + (double)C.t2[k] * 1.0);
+        }
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+      }
+      if (!(p[2] < 0.0f)) {                                 // depth must be positive
+        // :326 / :840 `1/p3Dc.at<float>(2)` is a float division; :983 / :1130 / :1210 `1.0/...` a double one, rounded to float
+        const float invz = C.invz_in_double ? (float)(1.0 / (double)p[2]) : 1.0f / p[2];
+        const float x = p[0] * invz;
+        const float y = p[1] * invz;
+        u = C.fx * x + C.cx;
+        v = C.fy * y + C.cy;
+        // KeyFrame::IsInImage (src/KeyFrame.cc:678-681), half-open; a NaN or infinite u, v (z = +-0) fails it by itself
+        if (u >= P.minX && u < P.maxX && v >= P.minY && v < P.maxY) {
+          const float maxDistance = 1.2f * maxRaw;          // GetMaxDistanceInvariance (MapPoint.cc:364-368)
+          const float minDistance = 0.8f * minRaw;          // GetMinDistanceInvariance (MapPoint.cc:358-362)
+          float PO[3];
+          if (C.distance_from_camera_point) { PO[0] = p[0]; PO[1] = p[1]; PO[2] = p[2]; }   // cv::norm(p3Dc2) (:1143, :1223)
+          else { PO[0] = Pw[0] - C.Ow[0]; PO[1] = Pw[1] - C.Ow[1]; PO[2] = Pw[2] - C.Ow[2]; }   // PO = p3Dw-Ow
+          double s = 0.0;                                   // cv::norm(PO)
+#pragma unroll
+          for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
+          const float dist3D = (float)sqrt(s);
+          if (!(dist3D < minDistance || dist3D > maxDistance)) {
+            bool angleOk = true;
+            if (C.check_viewing_angle) {                    // PO.dot(Pn)<0.5*dist (:349, :865, :1006)
+              double d = 0.0;
+#pragma unroll
+              for (int k = 0; k < 3; k++) d += (double)PO[k] * (double)Pn[k];
+              angleOk = !(d < 0.5 * (double)dist3D);
+            }
+            if (angleOk) {
+              // PredictScale (MapPoint.cc:370-379), converted to int as the host does (an out-of-range value becomes INT_MIN)
+              const float ratio = maxRaw / dist3D;
+              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
+              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+              valid = true;
+            }
+          }
+        }
+      }
+    }
+    const bool levelOk = lvl >= 0 && lvl < P.nlevels;
+    if (!valid) { u = 0.f; v = 0.f; lvl = 0; }
+    else if (levelOk) radius = P.th * P.sf[lvl];            // th*pKF->mvScaleFactors[nPredictedLevel]
+    if (P.valid) P.valid[i] = valid ? 1 : 0;
+    if (P.uv) { P.uv[2 * i] = u; P.uv[2 * i + 1] = v; }
+    if (P.level) P.level[i] = lvl;
+    if (P.radius) P.radius[i] = radius;
+    if (P.dxy) {
+      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
+      if (valid && !levelOk) atomicMin(&firstBad, i);
+      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
+      P.dlevel[i] = valid && levelOk ? lvl : 0;
+      P.dradius[i] = radius;
+      P.dvalid[i] = valid && levelOk ? 1 : 0;
+      P.drow[i] = valid ? 2 * row : 0;    // descriptor = 32-byte row 2*row of (table + 32)
+    }
+  }
+  const int count = __syncthreads_count(valid ? 1 : 0);
+  if (threadIdx.x == 0) {
+    P.blockInfo[2 * blockIdx.x] = count;
+    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
+    __threadfence_system();
+  }
+}
+
 __global__ void k_debug_logf(const float* __restrict__ x, int n, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = orbfe::logf_glibc(x[i]);
@@ -321,7 +453,7 @@ struct CallArea {
 };
 
 // checks shared by both calls; carves the page-locked area (caller's rows / flags read in place when page-locked)
-int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam, const int32_t* rows, const uint8_t* flags,
+int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const void* cam, const int32_t* rows, const uint8_t* flags,
             int n_mp, CallArea* A) {
   if (!m || !f || !map || !cam || n_mp < 0 || (n_mp && (!rows || !flags))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
   if (map->m != m) { set_err("the local map belongs to another matcher (its uploads are ordered on that matcher's stream)"); return ORBFE_ERR_INVALID; }
@@ -426,6 +558,37 @@ SrcParams source_params(orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map
   float b[4];
   orbfe::frame_bounds(cur, b);
   P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
+  P.blockInfo = A.blockInfo;
+  return P;
+}
+
+}  // namespace
+
+namespace {
+
+// checks shared by the two keyframe-projection calls, then prepare()'s
+int prepare_keyframe(orbfe_matcher* m, orbfe_frame* kf, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj, const int32_t* rows,
+                     const uint8_t* flags, int n, const float* scale_factors, int nlevels, CallArea* A) {
+  if (!scale_factors || nlevels < 1 || nlevels > 32) { set_err("bad argument (scale factors of 1..32 levels are required)"); return ORBFE_ERR_INVALID; }
+  if (proj && proj->check_viewing_angle && proj->distance_from_camera_point) {
+    set_err("the viewing-angle test reads PO = p3Dw-Ow: it needs the distance from the camera centre");
+    return ORBFE_ERR_INVALID;
+  }
+  return prepare(m, kf, map, proj, rows, flags, n, A);
+}
+
+KfParams keyframe_params(orbfe_frame* kf, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj, int n, const float* scale_factors,
+                         int nlevels, float th, const CallArea& A) {
+  KfParams P{};
+  P.table = map->table.p;
+  P.rows = A.rows; P.flags = A.flags; P.n = n;
+  P.proj = *proj;
+  float b[4];
+  orbfe::frame_bounds(kf, b);
+  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
+  P.nlevels = nlevels;
+  P.th = th;
+  for (int l = 0; l < nlevels; l++) P.sf[l] = scale_factors[l];
   P.blockInfo = A.blockInfo;
   return P;
 }
@@ -646,6 +809,74 @@ int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_
   if (bad >= 0) {
     *nmatches = 0;
     set_err("source %d: predicted level outside [0, %d)", bad, nlevels);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
+}
+
+int orbfe_project_keyframe(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj,
+                           const int32_t* rows, const uint8_t* flags, int n, const float* scale_factors, int nlevels, float th,
+                           uint8_t* valid, float* uv, int32_t* level, float* radius, int* n_valid) {
+  CallArea A;
+  int rc = prepare_keyframe(m, kf_frame, map, proj, rows, flags, n, scale_factors, nlevels, &A);
+  if (rc) return rc;
+  if (n_valid) *n_valid = 0;
+  if (n == 0) return ORBFE_OK;
+  KfParams P = keyframe_params(kf_frame, map, proj, n, scale_factors, nlevels, th, A);
+  P.valid = A.inView; P.uv = A.xy; P.level = A.level; P.radius = A.vcos;
+  hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  copy_out(A, n, valid, uv, level, radius);
+  if (n_valid) *n_valid = cnt;
+  return ORBFE_OK;
+}
+
+int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map,
+                                          const OrbfeKeyFrameProjection* proj, const int32_t* rows, const uint8_t* flags, int n,
+                                          const float* scale_factors, int nlevels, float th, const uint8_t* kp_skip, int claim,
+                                          const float* inv_level_sigma2, double chi2, int max_dist, uint8_t* valid, float* uv,
+                                          int32_t* level, int32_t* best_idx, int32_t* best_dist, int* nmatches, int* n_valid) {
+  if (!nmatches || !n_valid || (n > 0 && !best_idx)) { set_err("bad argument (best_idx, nmatches and n_valid are required)"); return ORBFE_ERR_INVALID; }
+  CallArea A;
+  int rc = prepare_keyframe(m, kf_frame, map, proj, rows, flags, n, scale_factors, nlevels, &A);
+  if (rc) return rc;
+  const int nkp = orbfe_frame_size(kf_frame);
+  *nmatches = 0;
+  *n_valid = 0;
+  for (int i = 0; i < n; i++) {
+    best_idx[i] = -1;
+    if (best_dist) best_dist[i] = -1;
+  }
+  if (n == 0) return ORBFE_OK;
+  const size_t c = (size_t)n;
+  const size_t oXY = 0, oL = al(8 * c), oR = oL + al(4 * c), oA = oR + al(4 * c), oV = oA + al(4 * c), total = oV + al(c);
+  if ((rc = map->q.ensure(total))) return rc;
+  uint8_t* D = map->q.p;
+  KfParams P = keyframe_params(kf_frame, map, proj, n, scale_factors, nlevels, th, A);
+  if (valid) P.valid = A.inView;
+  if (uv) P.uv = A.xy;
+  if (level) P.level = A.level;
+  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.drow = (int32_t*)(D + oR); P.dradius = (float*)(D + oA); P.dvalid = D + oV;
+  hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+  HIP_TRY(hipGetLastError());
+  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
+  if ((rc = orbfe::search_projected_frame_device_queries(m, kf_frame, scale_factors, nlevels, th, P.dxy, P.dlevel, P.dradius, P.dvalid,
+                                                         map->table.p + 32, P.drow, n, kp_skip, claim, inv_level_sigma2, chi2,
+                                                         max_dist, best_idx, best_dist, nmatches))) {
+    (void)hipStreamSynchronize(m->stream);
+    return rc;
+  }
+  if (nkp == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  *n_valid = cnt;
+  copy_out(A, n, valid, uv, level, nullptr);
+  if (bad >= 0) {
+    *nmatches = 0;
+    set_err("MapPoint %d: predicted level outside [0, %d)", bad, nlevels);
     return ORBFE_ERR_INVALID;
   }
   return ORBFE_OK;
