@@ -47,6 +47,7 @@ typedef struct OrbfeKeyPoint {
 typedef struct orbfe_extractor orbfe_extractor;
 typedef struct orbfe_matcher orbfe_matcher;
 typedef struct orbfe_vocabulary orbfe_vocabulary;   /* bag-of-words section below */
+typedef struct orbfe_kfdb orbfe_kfdb;               /* keyframe database section below */
 
 const char* orbfe_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). Does not create a context. */
@@ -814,6 +815,45 @@ int orbfe_search_by_bow_batch(orbfe_matcher* m, int n_kf, const uint8_t* const* 
                               const uint8_t* desc2, const float* angle2, const uint8_t* valid2, int n2, const uint32_t* fv2_nodes,
                               const uint32_t* fv2_offsets, const uint32_t* fv2_features, int n_fv2, float nnratio,
                               int check_orientation, int strict_threshold, int32_t* const* matches12, int* nmatches);
+
+/* ---------------------------------------------------------------------------------------------
+ * Keyframe database.  Replaces the inverted file of KeyFrameDatabase (src/KeyFrameDatabase.cc:38-334) and the
+ * mpVoc->score calls around it (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp; src/LoopClosing.cc:125-140): the
+ * BowVectors of the map's keyframes live in HBM, one query compares a BowVector with all of them (one wave per
+ * keyframe).  include/orbfe/KeyFrameDatabase.h is the drop-in class on top of it.
+ *
+ * n_words: the vocabulary's size (word ids are < n_words).  scoring: the vocabulary's DBoW2::ScoringType; 0 L1_NORM,
+ * 1 L2_NORM, 2 CHI_SQUARE and 5 DOT_PRODUCT are built, 3 KL and 4 BHATTACHARYYA are refused HERE with ORBFE_ERR_INVALID
+ * (they need log / a per-word sqrt with the host library's rounding).  capacity_keyframes / capacity_entries: live keyframes
+ * and live (word, value) pairs the pool holds; an add beyond either returns ORBFE_ERR_OVERFLOW and changes nothing.  Erased
+ * keyframes leave tombstones in the pool; an add that does not fit behind the last keyframe first compacts the pool on the
+ * device.  Calls on one handle are serialised by a mutex inside it (like KeyFrameDatabase::mMutex): unlike the other handles
+ * it may be shared by threads.  It depends on no extractor, matcher or vocabulary handle.
+ * ------------------------------------------------------------------------------------------- */
+int orbfe_kfdb_create(int device_id, int n_words, int scoring, int capacity_keyframes, int capacity_entries, orbfe_kfdb** out);
+void orbfe_kfdb_destroy(orbfe_kfdb* db);
+/* void KeyFrameDatabase::add(KeyFrame* pKF)  (:38-44).  key: the caller's name for the keyframe (the pointer, or mnId); a key
+ * that is already in the database is an error (ORBFE_ERR_INVALID).  words ascending (a BowVector's order), n of them (n * 12
+ * bytes are uploaded).  The keyframe goes to the BACK of every word's list, also when the key was there before and erased. */
+int orbfe_kfdb_add(orbfe_kfdb* db, uint64_t key, const uint32_t* words, const double* values, int n);
+/* void KeyFrameDatabase::erase(KeyFrame* pKF)  (:46-65); a key that is not in the database: nothing happens, as there. */
+int orbfe_kfdb_erase(orbfe_kfdb* db, uint64_t key);
+/* void KeyFrameDatabase::clear()  (:67-71) */
+int orbfe_kfdb_clear(orbfe_kfdb* db);
+int orbfe_kfdb_size(orbfe_kfdb* db, int* n_keyframes, int* n_entries);
+/* The inverted-file walk of DetectLoopCandidates (:85-104) / DetectRelocalizationCandidates (:207-222) and the score of every
+ * keyframe it meets: every live keyframe that shares at least one word with the query, in the order of first encounter
+ * (query words ascending, each word's list front to back = ascending by (first common word, add order)); common[i] = number
+ * of shared words, scores[i] = mpVoc->score(query, keyframe) as DBoW2's double, bit for bit (the sum over the common words in
+ * ascending word order); the reference's `float si = ...` is the caller's cast.  No exclusion set and no minCommonWords
+ * filter are applied: both act on this sequence and belong to the caller.  *n_out = number of such keyframes; if it exceeds
+ * cap, the first cap are written and the call returns ORBFE_ERR_OVERFLOW. */
+int orbfe_kfdb_query(orbfe_kfdb* db, const uint32_t* q_words, const double* q_values, int nq, uint64_t* keys, int32_t* common,
+                     double* scores, int cap, int* n_out);
+/* mpVoc->score(query, keyframe keys[i]) for n given keyframes, whether they share a word or not (src/LoopClosing.cc:125-140).
+ * A key that is not in the database fails the call with ORBFE_ERR_INVALID before anything is written. */
+int orbfe_kfdb_score(orbfe_kfdb* db, const uint32_t* q_words, const double* q_values, int nq, const uint64_t* keys, int n,
+                     double* scores);
 
 /* int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t,size_t>>&
  * vMatchedPairs)  (ORBmatcher.cc:652-804, with CheckDistEpipolarLine :135-152), from the epipole onwards: the caller

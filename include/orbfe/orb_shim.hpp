@@ -17,7 +17,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <list>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -1723,5 +1725,292 @@ inline int SearchForTriangulation(MatcherContext& ctx, bool mbCheckOrientation, 
   for (int i = 0; i < nmatches; i++) vMatchedPairs.push_back(std::make_pair((size_t)pairs[2 * i], (size_t)pairs[2 * i + 1]));
   return nmatches;
 }
+
+// KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:38-334) over orbfe_kfdb_*: the inverted file and the
+// mpVoc->score calls are one GPU query (one wave per keyframe of the map); what the reference does with the result -- the
+// member bookkeeping, the 0.8 / 0.75 thresholds, the covisibility accumulation -- is restated here statement for statement.
+// KeyFrameT: mnId, mBowVec, mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore,
+// GetConnectedKeyFrames(), GetBestCovisibilityKeyFrames(int), GetVectorCovisibleKeyFrames(), isBad().  The key of a keyframe
+// is its pointer.  The reference's database has no capacity: this one doubles the device pool when an add does not fit and
+// re-adds the live keyframes in their add order (which is their place in every inverted-file list).
+template <class KeyFrameT>
+class KeyFrameDatabaseT {
+ public:
+  // n_words = voc.size(), scoring = voc.getScoringType().  The device database is created by the first add: the reference
+  // constructs the database before the vocabulary is loaded and calls resizeInvertedFile afterwards (System.cc).
+  KeyFrameDatabaseT(int device, size_t n_words, int scoring, int capacity_keyframes = 4096, int capacity_entries = 4096 * 1024)
+      : device_(device), scoring_(scoring), nWords_(n_words), capK_(capacity_keyframes), capE_(capacity_entries) {}
+  ~KeyFrameDatabaseT() { orbfe_kfdb_destroy(db_); }
+  KeyFrameDatabaseT(const KeyFrameDatabaseT&) = delete;
+  KeyFrameDatabaseT& operator=(const KeyFrameDatabaseT&) = delete;
+
+  // void KeyFrameDatabase::add(KeyFrame *pKF)   KeyFrameDatabase.cc:38-44
+  void add(KeyFrameT* pKF) {
+    std::unique_lock<std::mutex> lock(mMutex);
+    addLocked(pKF);
+  }
+  // void KeyFrameDatabase::erase(KeyFrame* pKF)   :46-65
+  void erase(KeyFrameT* pKF) {
+    std::unique_lock<std::mutex> lock(mMutex);
+    eraseLocked(pKF);
+  }
+  // void KeyFrameDatabase::clear()   :67-71
+  void clear() {
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (db_) check(orbfe_kfdb_clear(db_));
+    seq_.clear();
+  }
+  // void KeyFrameDatabase::resizeInvertedFile(size_t)   :337-339
+  void resizeInvertedFile(size_t n) {
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (n == nWords_) return;
+    nWords_ = n;
+    if (db_) rebuild(capK_, capE_);
+  }
+  size_t size() const { return seq_.size(); }
+
+  // The reference minimum score of LoopClosing::DetectLoop (LoopClosing.cc:125-140): the lowest mpORBVocabulary->score to a
+  // covisible keyframe that is not bad.  A covisible keyframe that the loop closer has not added yet is scored by a visit
+  // (added, scored, erased again: an erased keyframe leaves no trace in any list's order).
+  float MinCovisibleScore(KeyFrameT* mpCurrentKF) {
+    const std::vector<KeyFrameT*> vpConnectedKeyFrames = mpCurrentKF->GetVectorCovisibleKeyFrames();
+    std::unique_lock<std::mutex> lock(mMutex);
+    std::vector<uint64_t> keys;
+    std::vector<KeyFrameT*> visitors;
+    for (size_t i = 0; i < vpConnectedKeyFrames.size(); i++) {
+      KeyFrameT* pKF = vpConnectedKeyFrames[i];
+      if (pKF->isBad()) continue;
+      if (!seq_.count(pKF)) { addLocked(pKF); visitors.push_back(pKF); }
+      keys.push_back(key(pKF));
+    }
+    float minScore = 1;
+    if (!keys.empty()) {
+      flatten(mpCurrentKF->mBowVec);
+      scores_.resize(keys.size());
+      const int rc = orbfe_kfdb_score(db_, qw_.data(), qv_.data(), (int)qw_.size(), keys.data(), (int)keys.size(), scores_.data());
+      for (KeyFrameT* v : visitors) eraseLocked(v);
+      check(rc);
+      for (size_t i = 0; i < keys.size(); i++) {
+        float score = scores_[i];
+        if (score < minScore) minScore = score;
+      }
+    }
+    return minScore;
+  }
+
+  // vector<KeyFrame*> KeyFrameDatabase::DetectLoopCandidates(KeyFrame* pKF, float minScore)   KeyFrameDatabase.cc:74-197
+  std::vector<KeyFrameT*> DetectLoopCandidates(KeyFrameT* pKF, float minScore) {
+    std::set<KeyFrameT*> spConnectedKeyFrames = pKF->GetConnectedKeyFrames();
+    std::list<std::pair<KeyFrameT*, double> > lKFsSharingWords;   // with the score the query computed for each
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      // :85-104.  The walk meets keyframe i of the query's result common_[i] times, for the first time in the result's order.
+      const int n = query(pKF->mBowVec);
+      for (int i = 0; i < n; i++) {
+        KeyFrameT* pKFi = reinterpret_cast<KeyFrameT*>((uintptr_t)keys_[i]);
+        if (pKFi->mnLoopQuery != pKF->mnId) {
+          if (!spConnectedKeyFrames.count(pKFi)) {
+            pKFi->mnLoopWords = common_[i];   // reset at the first encounter, counted at each
+            pKFi->mnLoopQuery = pKF->mnId;
+            lKFsSharingWords.push_back(std::make_pair(pKFi, scores_[i]));
+          } else
+            pKFi->mnLoopWords = 1;            // connected: mnLoopQuery stays, so EVERY encounter resets; the last leaves 1
+        } else
+          pKFi->mnLoopWords += common_[i];    // already carries this query's id: never reset, never listed
+      }
+    }
+    if (lKFsSharingWords.empty()) return std::vector<KeyFrameT*>();
+    std::list<std::pair<float, KeyFrameT*> > lScoreAndMatch;
+    int maxCommonWords = 0;
+    for (auto lit = lKFsSharingWords.begin(), lend = lKFsSharingWords.end(); lit != lend; lit++) {
+      if (lit->first->mnLoopWords > maxCommonWords) maxCommonWords = lit->first->mnLoopWords;
+    }
+    int minCommonWords = maxCommonWords * 0.8f;
+    for (auto lit = lKFsSharingWords.begin(), lend = lKFsSharingWords.end(); lit != lend; lit++) {
+      KeyFrameT* pKFi = lit->first;
+      if (pKFi->mnLoopWords > minCommonWords) {
+        float si = lit->second;   // float si = mpVoc->score(pKF->mBowVec,pKFi->mBowVec);
+        pKFi->mLoopScore = si;
+        if (si >= minScore) lScoreAndMatch.push_back(std::make_pair(si, pKFi));
+      }
+    }
+    if (lScoreAndMatch.empty()) return std::vector<KeyFrameT*>();
+    std::list<std::pair<float, KeyFrameT*> > lAccScoreAndMatch;
+    float bestAccScore = minScore;
+    for (auto it = lScoreAndMatch.begin(), itend = lScoreAndMatch.end(); it != itend; it++) {
+      KeyFrameT* pKFi = it->second;
+      std::vector<KeyFrameT*> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(10);
+      float bestScore = it->first;
+      float accScore = it->first;
+      KeyFrameT* pBestKF = pKFi;
+      for (auto vit = vpNeighs.begin(), vend = vpNeighs.end(); vit != vend; vit++) {
+        KeyFrameT* pKF2 = *vit;
+        if (pKF2->mnLoopQuery == pKF->mnId && pKF2->mnLoopWords > minCommonWords) {
+          accScore += pKF2->mLoopScore;
+          if (pKF2->mLoopScore > bestScore) {
+            pBestKF = pKF2;
+            bestScore = pKF2->mLoopScore;
+          }
+        }
+      }
+      lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+      if (accScore > bestAccScore) bestAccScore = accScore;
+    }
+    float minScoreToRetain = 0.75f * bestAccScore;
+    std::set<KeyFrameT*> spAlreadyAddedKF;
+    std::vector<KeyFrameT*> vpLoopCandidates;
+    vpLoopCandidates.reserve(lAccScoreAndMatch.size());
+    for (auto it = lAccScoreAndMatch.begin(), itend = lAccScoreAndMatch.end(); it != itend; it++) {
+      if (it->first > minScoreToRetain) {
+        KeyFrameT* pKFi = it->second;
+        if (!spAlreadyAddedKF.count(pKFi)) {
+          vpLoopCandidates.push_back(pKFi);
+          spAlreadyAddedKF.insert(pKFi);
+        }
+      }
+    }
+    return vpLoopCandidates;
+  }
+
+  // vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame *F)   KeyFrameDatabase.cc:199-334
+  template <class FrameT>
+  std::vector<KeyFrameT*> DetectRelocalizationCandidates(FrameT* F) {
+    std::list<std::pair<KeyFrameT*, double> > lKFsSharingWords;
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      const int n = query(F->mBowVec);   // :207-222
+      for (int i = 0; i < n; i++) {
+        KeyFrameT* pKFi = reinterpret_cast<KeyFrameT*>((uintptr_t)keys_[i]);
+        if (pKFi->mnRelocQuery != F->mnId) {
+          pKFi->mnRelocWords = common_[i];
+          pKFi->mnRelocQuery = F->mnId;
+          lKFsSharingWords.push_back(std::make_pair(pKFi, scores_[i]));
+        } else
+          pKFi->mnRelocWords += common_[i];
+      }
+    }
+    if (lKFsSharingWords.empty()) return std::vector<KeyFrameT*>();
+    int maxCommonWords = 0;
+    for (auto lit = lKFsSharingWords.begin(), lend = lKFsSharingWords.end(); lit != lend; lit++) {
+      if (lit->first->mnRelocWords > maxCommonWords) maxCommonWords = lit->first->mnRelocWords;
+    }
+    int minCommonWords = maxCommonWords * 0.8f;
+    std::list<std::pair<float, KeyFrameT*> > lScoreAndMatch;
+    for (auto lit = lKFsSharingWords.begin(), lend = lKFsSharingWords.end(); lit != lend; lit++) {
+      KeyFrameT* pKFi = lit->first;
+      if (pKFi->mnRelocWords > minCommonWords) {
+        float si = lit->second;   // float si = mpVoc->score(F->mBowVec,pKFi->mBowVec);
+        pKFi->mRelocScore = si;
+        lScoreAndMatch.push_back(std::make_pair(si, pKFi));
+      }
+    }
+    if (lScoreAndMatch.empty()) return std::vector<KeyFrameT*>();
+    std::list<std::pair<float, KeyFrameT*> > lAccScoreAndMatch;
+    float bestAccScore = 0;
+    for (auto it = lScoreAndMatch.begin(), itend = lScoreAndMatch.end(); it != itend; it++) {
+      KeyFrameT* pKFi = it->second;
+      std::vector<KeyFrameT*> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(10);
+      float bestScore = it->first;
+      float accScore = bestScore;
+      KeyFrameT* pBestKF = pKFi;
+      for (auto vit = vpNeighs.begin(), vend = vpNeighs.end(); vit != vend; vit++) {
+        KeyFrameT* pKF2 = *vit;
+        if (pKF2->mnRelocQuery != F->mnId) continue;
+        accScore += pKF2->mRelocScore;   // (also of a neighbour that this query did not score: its score of an earlier one)
+        if (pKF2->mRelocScore > bestScore) {
+          pBestKF = pKF2;
+          bestScore = pKF2->mRelocScore;
+        }
+      }
+      lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+      if (accScore > bestAccScore) bestAccScore = accScore;
+    }
+    float minScoreToRetain = 0.75f * bestAccScore;
+    std::set<KeyFrameT*> spAlreadyAddedKF;
+    std::vector<KeyFrameT*> vpRelocCandidates;
+    vpRelocCandidates.reserve(lAccScoreAndMatch.size());
+    for (auto it = lAccScoreAndMatch.begin(), itend = lAccScoreAndMatch.end(); it != itend; it++) {
+      const float& si = it->first;
+      if (si > minScoreToRetain) {
+        KeyFrameT* pKFi = it->second;
+        if (!spAlreadyAddedKF.count(pKFi)) {
+          vpRelocCandidates.push_back(pKFi);
+          spAlreadyAddedKF.insert(pKFi);
+        }
+      }
+    }
+    return vpRelocCandidates;
+  }
+
+ private:
+  static uint64_t key(KeyFrameT* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
+  template <class BowVectorT>
+  void flatten(const BowVectorT& v) {
+    qw_.clear(); qv_.clear();
+    for (auto it = v.begin(); it != v.end(); ++it) { qw_.push_back((uint32_t)it->first); qv_.push_back(it->second); }
+  }
+  void create(int capK, int capE) {
+    orbfe_kfdb* nd = nullptr;
+    check(orbfe_kfdb_create(device_, (int)std::max<size_t>(nWords_, 1), scoring_, capK, capE, &nd));
+    orbfe_kfdb_destroy(db_);
+    db_ = nd; capK_ = capK; capE_ = capE;
+  }
+  void rebuild(int capK, int capE) {   // a new pool with the live keyframes in their add order
+    create(capK, capE);
+    std::vector<std::pair<uint64_t, KeyFrameT*> > order;
+    for (auto& e : seq_) order.push_back(std::make_pair(e.second, e.first));
+    std::sort(order.begin(), order.end());
+    for (auto& e : order) {
+      flatten(e.second->mBowVec);
+      check(orbfe_kfdb_add(db_, key(e.second), qw_.data(), qv_.data(), (int)qw_.size()));
+    }
+  }
+  void addLocked(KeyFrameT* pKF) {
+    if (!db_) create(capK_, capE_);
+    if (seq_.count(pKF)) throw std::runtime_error("orbfe: KeyFrameDatabase::add of a keyframe that is already in the database");
+    flatten(pKF->mBowVec);
+    int rc = orbfe_kfdb_add(db_, key(pKF), qw_.data(), qv_.data(), (int)qw_.size());
+    if (rc == ORBFE_ERR_OVERFLOW) {
+      int nk = 0, ne = 0;
+      check(orbfe_kfdb_size(db_, &nk, &ne));
+      const std::vector<uint32_t> w = qw_;
+      const std::vector<double> v = qv_;
+      const long long wantE = (long long)ne + (long long)w.size();
+      long long capE = capE_;
+      while (capE < wantE) capE *= 2;
+      if (capE > 0x7fffffffLL) throw std::runtime_error("orbfe: KeyFrameDatabase: more than 2^31 BowVector entries");
+      rebuild(nk + 1 > capK_ ? capK_ * 2 : capK_, (int)capE);
+      rc = orbfe_kfdb_add(db_, key(pKF), w.data(), v.data(), (int)w.size());
+    }
+    check(rc);
+    seq_[pKF] = next_++;
+  }
+  void eraseLocked(KeyFrameT* pKF) {
+    if (!seq_.erase(pKF)) return;   // not in any list: the reference's loops find nothing
+    check(orbfe_kfdb_erase(db_, key(pKF)));
+  }
+  template <class BowVectorT>
+  int query(const BowVectorT& v) {
+    if (!db_ || seq_.empty()) return 0;
+    flatten(v);
+    const size_t cap = seq_.size();
+    keys_.resize(cap); common_.resize(cap); scores_.resize(cap);
+    int n = 0;
+    check(orbfe_kfdb_query(db_, qw_.data(), qv_.data(), (int)qw_.size(), keys_.data(), common_.data(), scores_.data(), (int)cap, &n));
+    return n;
+  }
+
+  int device_, scoring_;
+  size_t nWords_;
+  int capK_, capE_;
+  orbfe_kfdb* db_ = nullptr;
+  std::mutex mMutex;
+  std::unordered_map<KeyFrameT*, uint64_t> seq_;   // the live keyframes and their add order
+  uint64_t next_ = 0;
+  std::vector<uint32_t> qw_;
+  std::vector<double> qv_, scores_;
+  std::vector<uint64_t> keys_;
+  std::vector<int32_t> common_;
+};
 
 }  // namespace orbfe

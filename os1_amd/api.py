@@ -131,6 +131,15 @@ def load_library():
     L.orbfe_vocabulary_destroy.restype = None
     L.orbfe_vocabulary_info.argtypes = [vp] + [C.POINTER(ci)] * 6
     L.orbfe_bow_transform.argtypes = [vp, vp, ci, ci, ci, vp, vp, C.POINTER(ci), vp, vp, vp, C.POINTER(ci), vp, vp]
+    L.orbfe_kfdb_create.argtypes = [ci, ci, ci, ci, ci, C.POINTER(vp)]
+    L.orbfe_kfdb_destroy.argtypes = [vp]
+    L.orbfe_kfdb_destroy.restype = None
+    L.orbfe_kfdb_add.argtypes = [vp, C.c_uint64, vp, vp, ci]
+    L.orbfe_kfdb_erase.argtypes = [vp, C.c_uint64]
+    L.orbfe_kfdb_clear.argtypes = [vp]
+    L.orbfe_kfdb_size.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    L.orbfe_kfdb_query.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, C.POINTER(ci)]
+    L.orbfe_kfdb_score.argtypes = [vp, vp, vp, ci, vp, ci, vp]
     L.orbfe_search_by_bow.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp,
                                       C.POINTER(ci)]
     L.orbfe_search_by_bow_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp, vp]
@@ -1086,6 +1095,69 @@ class Vocabulary:
     def close(self):
         if getattr(self, 'h', None):
             self.L.orbfe_vocabulary_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeyFrameDatabase:
+    """The map's keyframe BowVectors resident in HBM (KeyFrameDatabase.cc's inverted file and mpVoc->score as one GPU query).
+    scoring: the vocabulary's DBoW2 ScoringType (0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 5 DOT_PRODUCT; KL and BHATTACHARYYA raise)."""
+
+    def __init__(self, n_words, scoring=0, capacity_keyframes=4096, capacity_entries=4096 * 1024, device=0):
+        self.L = load_library()
+        h = C.c_void_p()
+        _check(self.L.orbfe_kfdb_create(device, n_words, scoring, capacity_keyframes, capacity_entries, C.byref(h)))
+        self.h = h
+        self.capacity_keyframes = capacity_keyframes
+
+    def add(self, key, words, values):
+        """KeyFrameDatabase::add: `key` names the keyframe (any 64-bit integer not in the database), words ascending."""
+        words = np.ascontiguousarray(words, np.uint32)
+        values = np.ascontiguousarray(values, np.float64)
+        assert words.shape == values.shape and words.ndim == 1
+        _check(self.L.orbfe_kfdb_add(self.h, key, _p(words), _p(values), len(words)))
+
+    def erase(self, key):
+        _check(self.L.orbfe_kfdb_erase(self.h, key))
+
+    def clear(self):
+        _check(self.L.orbfe_kfdb_clear(self.h))
+
+    def size(self):
+        """-> (live keyframes, live (word, value) entries)"""
+        nk, ne = C.c_int(0), C.c_int(0)
+        _check(self.L.orbfe_kfdb_size(self.h, C.byref(nk), C.byref(ne)))
+        return nk.value, ne.value
+
+    def query(self, words, values):
+        """-> (keys, common, scores): every keyframe sharing a word with the query, in the reference's lKFsSharingWords order."""
+        words = np.ascontiguousarray(words, np.uint32)
+        values = np.ascontiguousarray(values, np.float64)
+        cap = max(self.size()[0], 1)
+        keys = np.zeros(cap, np.uint64)
+        common = np.zeros(cap, np.int32)
+        scores = np.zeros(cap, np.float64)
+        n = C.c_int(0)
+        _check(self.L.orbfe_kfdb_query(self.h, _p(words), _p(values), len(words), _p(keys), _p(common), _p(scores), cap, C.byref(n)))
+        return keys[:n.value], common[:n.value], scores[:n.value]
+
+    def score(self, words, values, keys, out=None):
+        """mpVoc->score(query, keyframe) for the given keys (LoopClosing.cc:125-140); an unknown key raises, `out` untouched."""
+        words = np.ascontiguousarray(words, np.uint32)
+        values = np.ascontiguousarray(values, np.float64)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        scores = np.zeros(max(len(keys), 1), np.float64) if out is None else out
+        _check(self.L.orbfe_kfdb_score(self.h, _p(words), _p(values), len(words), _p(keys), len(keys), _p(scores)))
+        return scores[:len(keys)]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.orbfe_kfdb_destroy(self.h)
             self.h = None
 
     def __del__(self):
