@@ -855,6 +855,42 @@ int orbfe_kfdb_query(orbfe_kfdb* db, const uint32_t* q_words, const double* q_va
 int orbfe_kfdb_score(orbfe_kfdb* db, const uint32_t* q_words, const double* q_values, int nq, const uint64_t* keys, int n,
                      double* scores);
 
+/* ---------------------------------------------------------------------------------------------
+ * Initialiser.  The scoring passes of Initializer::Initialize (src/Initializer.cc:44-121), the consumer of
+ * SearchForInitialization's vnMatches12: CheckHomography (:305-388) and CheckFundamental (:390-468) for all RANSAC
+ * hypotheses in one call, and the keep-the-best rule of FindHomography / FindFundamental (:148-171, :199-222).  The
+ * hypotheses themselves (Normalize, ComputeH21, ComputeF21: cv::SVD) stay with the caller's OpenCV, like ReconstructH / F,
+ * CheckRT and Triangulate.  Scores are the reference's floats bit for bit: the same float expressions without contraction,
+ * `1.0/(float)` as a double division rounded to float, and the sum over the matches taken in match order.
+ *
+ * sigma: mSigma.  H21 / H12 (both or neither) and F21: n_hyp matrices of 9 floats, row-major; a model that is not given is not
+ * scored and its outputs are left as they are.  scores_*: n_hyp floats, currentScore of every iteration.  best_*: the iteration
+ * whose score replaced the running best last, i.e. the first of the largest scores above 0 (a NaN score never wins), or -1 with
+ * best_score_* = 0 and all flags 0 when no score is above 0.  inliers_*: vbMatchesInliers of the winner, one byte per match.
+ * NULL outputs are skipped.  ORBFE_ERR_INVALID (nothing is written): n_hyp < 1, only one of H21 / H12, no model at all, a
+ * matches12 entry outside [-1, n2), frames on another device than m.
+ * ------------------------------------------------------------------------------------------- */
+/* Initializer.cc:305-468 for n_hyp hypotheses at once, plus the selection of :148-171 / :199-222.  pts: n x 4 floats
+ * (u1 v1 u2 v2) in match order.  n = 0 is valid: scores are 0 and best = -1. */
+int orbfe_score_init_hypotheses(orbfe_matcher* m, const float* pts, int n, float sigma, int n_hyp, const float* H21,
+                                const float* H12, const float* F21, float* scores_h, float* scores_f, int32_t* best_h,
+                                int32_t* best_f, float* best_score_h, float* best_score_f, uint8_t* inliers_h /* n */,
+                                uint8_t* inliers_f /* n */);
+/* The same, from two keypoint arrays (mvKeys1, mvKeys2 = mvKeysUn of the two frames) and vnMatches12 (n1 entries, -1 =
+ * unmatched); the matches are compacted in index order as :54-63 does.  *n_matches receives N; inliers_* hold N entries
+ * (n1 bytes always suffice). */
+int orbfe_score_init_hypotheses_kps(orbfe_matcher* m, const OrbfeKeyPoint* kps1_un, int n1, const OrbfeKeyPoint* kps2_un, int n2,
+                                    const int32_t* matches12, float sigma, int n_hyp, const float* H21, const float* H12,
+                                    const float* F21, float* scores_h, float* scores_f, int32_t* best_h, int32_t* best_f,
+                                    float* best_score_h, float* best_score_f, uint8_t* inliers_h, uint8_t* inliers_f,
+                                    int* n_matches);
+/* The same, with both frames resident (orbfe_frame; matches12 has orbfe_frame_size(f1) entries): only matches12 and the
+ * hypotheses cross the link, the gather from the frames' undistorted keypoints happens on the device. */
+int orbfe_score_init_hypotheses_frames(orbfe_matcher* m, orbfe_frame* f1, orbfe_frame* f2, const int32_t* matches12, float sigma,
+                                       int n_hyp, const float* H21, const float* H12, const float* F21, float* scores_h,
+                                       float* scores_f, int32_t* best_h, int32_t* best_f, float* best_score_h,
+                                       float* best_score_f, uint8_t* inliers_h, uint8_t* inliers_f, int* n_matches);
+
 /* int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t,size_t>>&
  * vMatchedPairs)  (ORBmatcher.cc:652-804, with CheckDistEpipolarLine :135-152), from the epipole onwards: the caller
  * computes (ex, ey) (:657-666) and passes F12 row-major.  has_mpX[i] != 0: the keypoint already has a MapPoint and is

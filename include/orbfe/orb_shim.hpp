@@ -578,6 +578,58 @@ inline int SearchForInitialization(MatcherContext& ctx, float mfNNratio, bool mb
   return nmatches;
 }
 
+// What the two RANSAC loops of Initializer::Initialize leave behind (Initializer.cc:99-109): FindHomography's and
+// FindFundamental's outputs, the iteration each of them kept (-1: no score above 0, the reference's H / F stay empty), and
+// currentScore of every iteration.
+struct InitializerScores {
+  std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;
+  float SH = 0.f, SF = 0.f;
+  int bestH = -1, bestF = -1;
+  std::vector<float> scoresH, scoresF;
+};
+
+// float Initializer::CheckHomography / CheckFundamental (Initializer.cc:305-388, :390-468) for every hypothesis, and the
+// keep-the-best rule of FindHomography / FindFundamental (:148-171, :199-222), in one GPU call.  keys1 / keys2 = mvKeys1 /
+// mvKeys2, matches12 = mvMatches12, sigma = mSigma; H21s[it], H12s[it], F21s[it] = H21i, H12i, F21i of iteration `it`
+// (3 x 3, float, read through at<float>(r, c)).  H21s and H12s come together; a model whose vectors are empty is skipped.
+template <class KeyPointT, class MatT>
+inline void ScoreInitializerHypotheses(MatcherContext& ctx, const std::vector<KeyPointT>& keys1, const std::vector<KeyPointT>& keys2,
+                                       const std::vector<std::pair<int, int>>& matches12, float sigma, const std::vector<MatT>& H21s,
+                                       const std::vector<MatT>& H12s, const std::vector<MatT>& F21s, InitializerScores& result) {
+  const int N = (int)matches12.size();
+  const bool hasH = !H21s.empty() || !H12s.empty(), hasF = !F21s.empty();
+  const int K = (int)(hasF ? F21s.size() : H21s.size());
+  if (hasH && (H21s.size() != (size_t)K || H12s.size() != (size_t)K))
+    throw std::runtime_error("orbfe: ScoreInitializerHypotheses needs as many H21 as H12 (and F21) hypotheses");
+  std::vector<float> pts((size_t)N * 4), h21, h12, f21;
+  for (int i = 0; i < N; i++) {   // Initializer.cc:341-347
+    const KeyPointT& kp1 = keys1[matches12[i].first];
+    const KeyPointT& kp2 = keys2[matches12[i].second];
+    pts[4 * (size_t)i] = kp1.pt.x; pts[4 * (size_t)i + 1] = kp1.pt.y; pts[4 * (size_t)i + 2] = kp2.pt.x; pts[4 * (size_t)i + 3] = kp2.pt.y;
+  }
+  auto pack = [K](const std::vector<MatT>& ms, std::vector<float>& out) {
+    out.resize((size_t)K * 9);
+    for (int k = 0; k < K; k++)
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) out[(size_t)k * 9 + 3 * r + c] = ms[k].template at<float>(r, c);
+  };
+  if (hasH) { pack(H21s, h21); pack(H12s, h12); }
+  if (hasF) pack(F21s, f21);
+  std::vector<uint8_t> inH((size_t)N + 1), inF((size_t)N + 1);
+  result = InitializerScores();
+  result.scoresH.assign(hasH ? K : 0, 0.f);
+  result.scoresF.assign(hasF ? K : 0, 0.f);
+  check(orbfe_score_init_hypotheses(ctx.get(), pts.data(), N, sigma, K, hasH ? h21.data() : nullptr, hasH ? h12.data() : nullptr,
+                                    hasF ? f21.data() : nullptr, result.scoresH.data(), result.scoresF.data(), &result.bestH,
+                                    &result.bestF, &result.SH, &result.SF, inH.data(), inF.data()));
+  result.vbMatchesInliersH.assign(N, false);
+  result.vbMatchesInliersF.assign(N, false);
+  for (int i = 0; i < N; i++) {
+    if (hasH) result.vbMatchesInliersH[i] = inH[i] != 0;
+    if (hasF) result.vbMatchesInliersF[i] = inF[i] != 0;
+  }
+}
+
 // int ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float th)
 // (ORBmatcher.cc:45-124).  MapPoint fields are snapshotted through the reference's own accessors
 // (isBad(), GetDescriptor(), Observations() take the MapPoint mutexes, MapPoint.cc:126-129,294-298)

@@ -140,6 +140,10 @@ def load_library():
     L.orbfe_kfdb_size.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.orbfe_kfdb_query.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, C.POINTER(ci)]
     L.orbfe_kfdb_score.argtypes = [vp, vp, vp, ci, vp, ci, vp]
+    tail = [cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]   # sigma, n_hyp, H21, H12, F21, eight outputs
+    L.orbfe_score_init_hypotheses.argtypes = [vp, vp, ci] + tail
+    L.orbfe_score_init_hypotheses_kps.argtypes = [vp, vp, ci, vp, ci, vp] + tail + [C.POINTER(ci)]
+    L.orbfe_score_init_hypotheses_frames.argtypes = [vp, vp, vp, vp] + tail + [C.POINTER(ci)]
     L.orbfe_search_by_bow.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp,
                                       C.POINTER(ci)]
     L.orbfe_search_by_bow_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp, vp]
@@ -554,8 +558,79 @@ class Frame:
             pass
 
 
+class InitScores:
+    """What Matcher.score_init_hypotheses* return: scores_h / scores_f (currentScore per hypothesis), best_h / best_f (winning
+    hypothesis or -1), score_h / score_f (SH, SF), inliers_h / inliers_f (the winner's vbMatchesInliers as bool arrays) and
+    n_matches.  The fields of a model that was not given are None."""
+
+    __slots__ = ('scores_h', 'scores_f', 'best_h', 'best_f', 'score_h', 'score_f', 'inliers_h', 'inliers_f', 'n_matches')
+
+
+class _InitScoreCall:
+    """Argument tail and outputs of one orbfe_score_init_hypotheses* call."""
+
+    def __init__(self, sigma, H21, H12, F21, cap):
+        mats = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 9) for a in (H21, H12, F21)]
+        ks = {len(a) for a in mats if a is not None}
+        if len(ks) > 1:
+            raise ValueError('H21, H12 and F21 must hold the same number of hypotheses')
+        self.K = ks.pop() if ks else 0
+        self.mats = mats
+        self.has_h, self.has_f = mats[0] is not None or mats[1] is not None, mats[2] is not None
+        K = max(self.K, 1)
+        self.scores = np.zeros((2, K), np.float32)
+        self.best = np.full(2, -1, np.int32)
+        self.best_score = np.zeros(2, np.float32)
+        self.inl = np.zeros((2, max(cap, 1)), np.uint8)
+        opt = lambda a: None if a is None else _p(a)
+        self.tail = [float(sigma), self.K, opt(mats[0]), opt(mats[1]), opt(mats[2]), _p(self.scores[0]), _p(self.scores[1]),
+                     _p(self.best[0:]), _p(self.best[1:]), _p(self.best_score[0:]), _p(self.best_score[1:]), _p(self.inl[0]),
+                     _p(self.inl[1])]
+
+    def result(self, n):
+        r = InitScores()
+        r.n_matches = int(n)
+        for i, (has, sfx) in enumerate(((self.has_h, 'h'), (self.has_f, 'f'))):
+            setattr(r, 'scores_' + sfx, self.scores[i, :self.K].copy() if has else None)
+            setattr(r, 'best_' + sfx, int(self.best[i]) if has else None)
+            setattr(r, 'score_' + sfx, np.float32(self.best_score[i]) if has else None)
+            setattr(r, 'inliers_' + sfx, self.inl[i, :n].astype(bool) if has else None)
+        return r
+
+
 class Matcher:
     """Hot subset of ORBmatcher on one GPU."""
+
+    def score_init_hypotheses(self, pts, sigma, H21=None, H12=None, F21=None):
+        """Initializer::CheckHomography / CheckFundamental for every hypothesis and the selection of FindHomography /
+        FindFundamental.  pts: [n][4] = u1 v1 u2 v2 in match order; H21, H12, F21: [K][3][3] or [K][9] float32."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        c = _InitScoreCall(sigma, H21, H12, F21, len(pts))
+        _check(self.L.orbfe_score_init_hypotheses(self.h, _p(pts), len(pts), *c.tail))
+        return c.result(len(pts))
+
+    def score_init_hypotheses_kps(self, kps1_un, kps2_un, matches12, sigma, H21=None, H12=None, F21=None):
+        """The same from mvKeysUn of both frames and vnMatches12 (len(kps1_un) entries, -1 = unmatched)."""
+        kps1_un = np.ascontiguousarray(kps1_un, KP_DTYPE)
+        kps2_un = np.ascontiguousarray(kps2_un, KP_DTYPE)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        if len(m12) != len(kps1_un):
+            raise ValueError('matches12 has one entry per keypoint of frame 1')
+        c = _InitScoreCall(sigma, H21, H12, F21, len(kps1_un))
+        n = C.c_int(0)
+        _check(self.L.orbfe_score_init_hypotheses_kps(self.h, _p(kps1_un), len(kps1_un), _p(kps2_un), len(kps2_un), _p(m12), *c.tail,
+                                                      C.byref(n)))
+        return c.result(n.value)
+
+    def score_init_hypotheses_frames(self, frame1, frame2, matches12, sigma, H21=None, H12=None, F21=None):
+        """The same with both frames resident (Frame): only matches12 and the hypotheses are uploaded."""
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        if len(m12) != len(frame1):
+            raise ValueError('matches12 has one entry per keypoint of frame 1')
+        c = _InitScoreCall(sigma, H21, H12, F21, len(frame1))
+        n = C.c_int(0)
+        _check(self.L.orbfe_score_init_hypotheses_frames(self.h, frame1.h, frame2.h, _p(m12), *c.tail, C.byref(n)))
+        return c.result(n.value)
 
     def frame(self, kps_un, desc, bounds):
         return Frame.from_host(self, kps_un, desc, bounds)

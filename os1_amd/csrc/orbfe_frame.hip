@@ -1503,6 +1503,10 @@ int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, cons
 void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave) {
   *oct = f->D.oct; *angle = f->D.angle; *maxOctave = f->maxOctave;
 }
+// the undistorted keypoint coordinates in keypoint order (the gather of orbfe_initscore.hip)
+void frame_xy(const orbfe_frame* f, const float** x, const float** y) {
+  *x = f->D.x; *y = f->D.y;
+}
 void frame_wait_ready(orbfe_frame* f, hipStream_t st) {
   if (f->ready && hipStreamWaitEvent(st, f->ready, 0) != hipSuccess) (void)hipGetLastError();   // (the recording stream is gone: the build is complete)
 }

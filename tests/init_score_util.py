@@ -1,0 +1,392 @@
+"""Shared by tests/test_init_score.py and tests/test_gpu_init_score.py: the seeded scenes of the initialiser-scoring tests, the
+ctypes binding of the restatement tests/cpp/init_score_ref.cpp (built here with g++ -O2 -ffp-contract=off), a second,
+independent restatement in numpy (np.float32 wherever the reference says float, float64 = Python floats for its `1.0/...`
+divisions, np.add.accumulate for the ordered sum), the crafted hypotheses, and the scene file tests/cpp/init_score_test.cpp reads.
+
+A scene is two views of seeded 3-D points (planar or general), projected with pixel noise, about 30 % of the matches replaced by
+wrong ones.  Hypotheses come from a double-precision 8-point DLT on random minimal sets, cast to float32: they are INPUTS of
+the scoring and need not be what cv::SVD would give."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_SRC = os.path.join(ROOT, 'tests', 'cpp', 'init_score_ref.cpp')
+KERNEL_SRC = os.path.join(ROOT, 'os1_amd', 'csrc', 'orbfe_initscore.hip')
+LDS_CHUNK = 1024        # matches per LDS chunk of k_init_score (os1_amd/csrc/orbfe_initscore.hip kChunk)
+N_MAX = 5000
+K_MAX = 200
+SIGMA = 1.0             # Tracking.cc creates the Initializer with sigma 1.0
+SWEEP_N = (0, 1, 8, 63, 64, 65, 257, LDS_CHUNK - 1, LDS_CHUNK, LDS_CHUNK + 1, N_MAX)
+SWEEP_K = (1, 3, K_MAX)
+f32 = np.float32
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def build_ref(outdir, flags=('-O2', '-ffp-contract=off'), name='init_score_ref.so'):
+    so = os.path.join(str(outdir), name)
+    subprocess.check_call(['g++', '-std=c++17'] + list(flags) + ['-fPIC', '-shared', '-Wall', '-Werror', REF_SRC, '-o', so])
+    L = C.CDLL(so)
+    vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+    L.isr_check_homography.argtypes = [vp, ci, vp, vp, cf, vp]
+    L.isr_check_homography.restype = cf
+    L.isr_check_fundamental.argtypes = [vp, ci, vp, cf, vp]
+    L.isr_check_fundamental.restype = cf
+    L.isr_find.argtypes = [vp, ci, cf, ci] + [vp] * 11
+    L.isr_find.restype = None
+    L.isr_compact.argtypes = [vp, ci, vp, vp, vp]
+    return L
+
+
+class Result:
+    """scores_h/f, best_h/f, score_h/f, inliers_h/f; the fields of an absent model are None."""
+
+    def __init__(self):
+        for k in ('scores_h', 'scores_f', 'best_h', 'best_f', 'score_h', 'score_f', 'inliers_h', 'inliers_f'):
+            setattr(self, k, None)
+
+
+def ref_find(L, pts, sigma, H21=None, H12=None, F21=None):
+    """FindHomography / FindFundamental over the given hypotheses by the C++ restatement."""
+    pts = np.ascontiguousarray(pts, f32).reshape(-1, 4)
+    n = len(pts)
+    mats = [None if a is None else np.ascontiguousarray(a, f32).reshape(-1, 9) for a in (H21, H12, F21)]
+    K = max(len(a) for a in mats if a is not None)
+    sc = np.zeros((2, K), f32)
+    best = np.zeros(2, np.int32)
+    S = np.zeros(2, f32)
+    inl = np.zeros((2, max(n, 1)), np.uint8)
+    L.isr_find(_p(pts), n, sigma, K, _p(mats[0]), _p(mats[1]), _p(mats[2]), _p(sc[0]), _p(sc[1]), _p(best[0:]), _p(best[1:]), _p(S[0:]),
+               _p(S[1:]), _p(inl[0]), _p(inl[1]))
+    r = Result()
+    if mats[0] is not None:
+        r.scores_h, r.best_h, r.score_h, r.inliers_h = sc[0].copy(), int(best[0]), f32(S[0]), inl[0, :n].astype(bool)
+    if mats[2] is not None:
+        r.scores_f, r.best_f, r.score_f, r.inliers_f = sc[1].copy(), int(best[1]), f32(S[1]), inl[1, :n].astype(bool)
+    return r
+
+
+def ref_compact(L, xy1, xy2, m12):
+    xy1 = np.ascontiguousarray(xy1, f32)
+    xy2 = np.ascontiguousarray(xy2, f32)
+    m12 = np.ascontiguousarray(m12, np.int32)
+    pts = np.zeros((max(len(m12), 1), 4), f32)
+    n = L.isr_compact(_p(xy1), len(m12), _p(xy2), _p(m12), _p(pts))
+    return pts[:n].copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The numpy restatement (Initializer.cc:305-388, :390-468): one hypothesis, all matches at once, every operation a float32
+# array operation (numpy rounds each to float32 and fuses nothing).
+# ---------------------------------------------------------------------------------------------------------------------
+def _inv(x):   # `1.0/(float expression)`: the expression widened to double, a double division, the result rounded to float
+    return (1.0 / x.astype(np.float64)).astype(f32)
+
+
+def np_terms_h(pts, H21, H12, sigma):
+    """(c1, c2, inlier flags): the terms CheckHomography adds for every match, +0 where it adds nothing."""
+    with np.errstate(all='ignore'):
+        u1, v1, u2, v2 = (np.ascontiguousarray(pts[:, i], f32) for i in range(4))
+        h = [f32(x) for x in np.asarray(H21, f32).reshape(9)]
+        g = [f32(x) for x in np.asarray(H12, f32).reshape(9)]
+        th = f32(5.991)
+        inv_s2 = f32(1.0 / float(f32(sigma) * f32(sigma)))
+        w = _inv(g[6] * u2 + g[7] * v2 + g[8])
+        uu = (g[0] * u2 + g[1] * v2 + g[2]) * w
+        vv = (g[3] * u2 + g[4] * v2 + g[5]) * w
+        chi1 = ((u1 - uu) * (u1 - uu) + (v1 - vv) * (v1 - vv)) * inv_s2
+        w = _inv(h[6] * u1 + h[7] * v1 + h[8])
+        uu = (h[0] * u1 + h[1] * v1 + h[2]) * w
+        vv = (h[3] * u1 + h[4] * v1 + h[5]) * w
+        chi2 = ((u2 - uu) * (u2 - uu) + (v2 - vv) * (v2 - vv)) * inv_s2
+        r1, r2 = chi1 > th, chi2 > th
+        return np.where(r1, f32(0), th - chi1).astype(f32), np.where(r2, f32(0), th - chi2).astype(f32), ~r1 & ~r2
+
+
+def np_terms_f(pts, F21, sigma, detail=False):
+    with np.errstate(all='ignore'):
+        u1, v1, u2, v2 = (np.ascontiguousarray(pts[:, i], f32) for i in range(4))
+        f = [f32(x) for x in np.asarray(F21, f32).reshape(9)]
+        th, th_score = f32(3.841), f32(5.991)
+        inv_s2 = f32(1.0 / float(f32(sigma) * f32(sigma)))
+        a2 = f[0] * u1 + f[1] * v1 + f[2]
+        b2 = f[3] * u1 + f[4] * v1 + f[5]
+        c2 = f[6] * u1 + f[7] * v1 + f[8]
+        num2 = a2 * u2 + b2 * v2 + c2
+        den2 = a2 * a2 + b2 * b2
+        chi1 = (num2 * num2 / den2) * inv_s2
+        a1 = f[0] * u2 + f[3] * v2 + f[6]
+        b1 = f[1] * u2 + f[4] * v2 + f[7]
+        c1 = f[2] * u2 + f[5] * v2 + f[8]
+        num1 = a1 * u1 + b1 * v1 + c1
+        den1 = a1 * a1 + b1 * b1
+        chi2 = (num1 * num1 / den1) * inv_s2
+        r1, r2 = chi1 > th, chi2 > th
+        out = (np.where(r1, f32(0), th_score - chi1).astype(f32), np.where(r2, f32(0), th_score - chi2).astype(f32), ~r1 & ~r2)
+        return out + (den2, den1) if detail else out
+
+
+def interleave(c1, c2):
+    t = np.empty(2 * len(c1), f32)
+    t[0::2], t[1::2] = c1, c2
+    return t
+
+
+def ordered_sum(terms):
+    """((((0 + t0) + t1) + t2) + ...) in float32."""
+    if len(terms) == 0:
+        return f32(0)
+    with np.errstate(all='ignore'):
+        return f32(np.add.accumulate(terms, dtype=f32)[-1])
+
+
+def np_find(pts, sigma, H21=None, H12=None, F21=None):
+    """FindHomography / FindFundamental by the numpy restatement."""
+    pts = np.ascontiguousarray(pts, f32).reshape(-1, 4)
+    r = Result()
+
+    def loop(K, terms):
+        scores = np.zeros(K, f32)
+        score, best, flags = f32(0), -1, np.zeros(len(pts), bool)
+        for k in range(K):
+            c1, c2, inl = terms(k)
+            scores[k] = ordered_sum(interleave(c1, c2))
+            if scores[k] > score:
+                score, best, flags = scores[k], k, inl
+        return scores, best, score, flags
+
+    if H21 is not None:
+        A, B = np.asarray(H21, f32).reshape(-1, 9), np.asarray(H12, f32).reshape(-1, 9)
+        r.scores_h, r.best_h, r.score_h, r.inliers_h = loop(len(A), lambda k: np_terms_h(pts, A[k], B[k], sigma))
+    if F21 is not None:
+        A = np.asarray(F21, f32).reshape(-1, 9)
+        r.scores_f, r.best_f, r.score_f, r.inliers_f = loop(len(A), lambda k: np_terms_f(pts, A[k], sigma))
+    return r
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def same_scores(a, b):
+    """Bit for bit, NaN by class (isnan on both sides)."""
+    a, b = np.atleast_1d(np.asarray(a, f32)), np.atleast_1d(np.asarray(b, f32))
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and bool((na == nb).all()) and bool((bits(a)[~na] == bits(b)[~nb]).all())
+
+
+def assert_same(got, want, what=''):
+    for sfx in ('h', 'f'):
+        w = getattr(want, 'scores_' + sfx)
+        if w is None:
+            continue
+        assert same_scores(getattr(got, 'scores_' + sfx), w), '%s: scores_%s differ' % (what, sfx)
+        assert getattr(got, 'best_' + sfx) == getattr(want, 'best_' + sfx), '%s: best_%s %r != %r' % (
+            what, sfx, getattr(got, 'best_' + sfx), getattr(want, 'best_' + sfx))
+        assert same_scores(getattr(got, 'score_' + sfx), getattr(want, 'score_' + sfx)), '%s: score_%s differs' % (what, sfx)
+        assert np.array_equal(np.asarray(getattr(got, 'inliers_' + sfx), bool), getattr(want, 'inliers_' + sfx)), \
+            '%s: inliers_%s differ' % (what, sfx)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Scenes
+# ---------------------------------------------------------------------------------------------------------------------
+FX = FY = 500.0
+CX, CY = 320.0, 240.0
+
+
+def _rot(rx, ry, rz):
+    cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+    return (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @
+            np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+
+
+def make_scene(planar, seed, n=N_MAX, noise=0.3, wrong=0.3):
+    rng = np.random.default_rng(seed)
+    uv = np.stack([rng.uniform(20, 620, n), rng.uniform(20, 460, n)], 1)
+    ray = np.stack([(uv[:, 0] - CX) / FX, (uv[:, 1] - CY) / FY, np.ones(n)], 1)
+    if planar:   # a tilted plane n.X = d
+        nrm = np.array([0.15, -0.1, 1.0])
+        depth = 6.0 / (ray @ nrm)
+    else:
+        depth = rng.uniform(3.0, 12.0, n)
+    X = ray * depth[:, None]
+    R, t = _rot(0.02, -0.05, 0.03), np.array([0.4, 0.05, 0.1])
+    X2 = X @ R.T + t
+    uv2 = np.stack([FX * X2[:, 0] / X2[:, 2] + CX, FY * X2[:, 1] / X2[:, 2] + CY], 1)
+    p1 = uv + rng.normal(0, noise, uv.shape)
+    p2 = uv2 + rng.normal(0, noise, uv.shape)
+    bad = rng.random(n) < wrong
+    p2[bad] = np.stack([rng.uniform(0, 640, bad.sum()), rng.uniform(0, 480, bad.sum())], 1)
+    pts = np.ascontiguousarray(np.concatenate([p1, p2], 1), f32)
+    return {'name': 'planar' if planar else 'general', 'pts': pts, 'good': ~bad, 'rng': rng, 'seed': seed}
+
+
+def _normalize(p):
+    m = p.mean(0)
+    d = np.abs(p - m).mean(0)
+    T = np.array([[1 / d[0], 0, -m[0] / d[0]], [0, 1 / d[1], -m[1] / d[1]], [0, 0, 1]])
+    return (p - m) / d, T
+
+
+def dlt_h(p1, p2):
+    """8-point DLT of a homography x2 ~ H21 x1, in double."""
+    q1, T1 = _normalize(p1)
+    q2, T2 = _normalize(p2)
+    A = []
+    for (u1, v1), (u2, v2) in zip(q1, q2):
+        A.append([0, 0, 0, -u1, -v1, -1, v2 * u1, v2 * v1, v2])
+        A.append([u1, v1, 1, 0, 0, 0, -u2 * u1, -u2 * v1, -u2])
+    Hn = np.linalg.svd(np.array(A))[2][-1].reshape(3, 3)
+    return np.linalg.inv(T2) @ Hn @ T1
+
+
+def dlt_f(p1, p2):
+    """8-point DLT of a fundamental matrix x2' F21 x1 = 0 with the rank-2 constraint, in double."""
+    q1, T1 = _normalize(p1)
+    q2, T2 = _normalize(p2)
+    A = [[u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1] for (u1, v1), (u2, v2) in zip(q1, q2)]
+    Fp = np.linalg.svd(np.array(A))[2][-1].reshape(3, 3)
+    u, w, vt = np.linalg.svd(Fp)
+    w[2] = 0
+    return T2.T @ (u @ np.diag(w) @ vt) @ T1
+
+
+def random_hypotheses(scene, K, seed):
+    """K hypotheses per model from random minimal sets of 8 matches (drawn among the first 257, so every prefix of the scene the
+    sweep scores holds most of them)."""
+    rng = np.random.default_rng(seed)
+    P = scene['pts'].astype(np.float64)
+    H21, H12, F21 = (np.zeros((K, 9), f32) for _ in range(3))
+    for k in range(K):
+        idx = rng.choice(257, 8, replace=False)
+        H = dlt_h(P[idx, :2], P[idx, 2:])
+        H21[k] = H.reshape(9)
+        with np.errstate(all='ignore'):
+            H12[k] = np.linalg.inv(H21[k].reshape(3, 3).astype(np.float64)).reshape(9)
+        F21[k] = dlt_f(P[idx, :2], P[idx, 2:]).reshape(9)
+    return H21, H12, F21
+
+
+# Places of the crafted hypotheses in the K_MAX set
+I_TIE_LO, I_BEST, I_TIE_HI = 50, 100, 150
+I_ZERO_H12, I_INF_H21, I_ZERO_F, I_TINY_F, I_DENORM_F = 7, 8, 9, 10, 11
+INF_MATCH = 5           # the match that lies on I_INF_H21's line at infinity
+
+
+def crafted_set(L, scene):
+    """The K_MAX hypotheses of a scene with the crafted ones in their places.  Returns (H21, H12, F21)."""
+    H21, H12, F21 = random_hypotheses(scene, K_MAX, scene['seed'] + 1000)
+    pts = scene['pts']
+    r = ref_find(L, pts, SIGMA, H21, H12, F21)
+    for A in (H21, H12):
+        A[[I_BEST, r.best_h]] = A[[r.best_h, I_BEST]]           # the best one to I_BEST ...
+        A[I_TIE_LO] = A[I_BEST]                                  # ... and exact copies below and above it
+        A[I_TIE_HI] = A[I_BEST]
+    F21[[I_BEST, r.best_f]] = F21[[r.best_f, I_BEST]]
+    F21[I_TIE_LO] = F21[I_BEST]
+    F21[I_TIE_HI] = F21[I_BEST]
+    H12[I_ZERO_H12] = 0                                          # cv::Mat::inv of a singular matrix: 1/0 = inf, 0 * inf = NaN
+    u1 = pts[INF_MATCH, 0]
+    H21[I_INF_H21] = [1, 0, 0, 0, 1, 0, 1, 0, -u1]               # 1 * u1 + 0 * v1 - u1 == 0 exactly for match INF_MATCH
+    H12[I_INF_H21] = H12[I_BEST]
+    F21[I_ZERO_F] = 0                                            # 0 * 0 / (0 + 0)
+    F21[I_TINY_F] = F21[20] * f32(1e-25)                         # (any other hypothesis) a*a + b*b underflows to 0 ...
+    den = np_terms_f(pts, F21[21], SIGMA, detail=True)[3]
+    F21[I_DENORM_F] = F21[21] * f32(np.sqrt(1e-41 / np.median(den.astype(np.float64))))   # ... or lands among the denormals
+    return H21, H12, F21
+
+
+def hypothesis_sets(L, scene):
+    """{name: (H21, H12, F21)}: 'k200' (all crafted cases), 'k3' (NaN, best, copy of best), 'k1' (the best), 'nothing' (no score
+    above 0: every match rejected, or NaN)."""
+    H21, H12, F21 = crafted_set(L, scene)
+    pick = [I_ZERO_H12, I_BEST, I_TIE_HI]
+    pick_f = [I_ZERO_F, I_BEST, I_TIE_HI]
+    far = np.array([1, 0, 1000, 0, 1, 0, 0, 0, 1], f32)         # a shift by 1000 pixels: every term is rejected, the score is 0
+    back = np.array([1, 0, -1000, 0, 1, 0, 0, 0, 1], f32)
+    far_f = np.array([0, 0, 0, 0, 0, 0, 0, 0, 1], f32)          # l = (0, 0, 1): num * num / 0 = inf for every match
+    return {
+        'k200': (H21, H12, F21),
+        'k3': (H21[pick].copy(), H12[pick].copy(), F21[pick_f].copy()),
+        'k1': (H21[[I_BEST]].copy(), H12[[I_BEST]].copy(), F21[[I_BEST]].copy()),
+        'nothing': (np.stack([far, far, H21[I_ZERO_H12]]), np.stack([back, back, H12[I_ZERO_H12]]),
+                    np.stack([far_f, F21[I_ZERO_F], far_f])),
+    }
+
+
+SET_OF_K = {1: 'k1', 3: 'k3', K_MAX: 'k200'}
+SCENE_SEEDS = {'planar': 11, 'general': 12}
+_cache = {}
+
+
+def scenes(L):
+    """[(scene, hypothesis sets)] for the planar and the general scene; built once per process."""
+    if 'scenes' not in _cache:
+        out = []
+        for planar in (True, False):
+            s = make_scene(planar, SCENE_SEEDS['planar' if planar else 'general'])
+            out.append((s, hypothesis_sets(L, s)))
+        _cache['scenes'] = out
+    return _cache['scenes']
+
+
+def keypoint_form(pts, seed, extra=37):
+    """Two keypoint arrays and vnMatches12 (with unmatched entries) whose compaction in index order gives exactly `pts`."""
+    from os1_amd.api import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    n = len(pts)
+    n1, n2 = n + extra, n + extra + 5
+    slots1 = np.sort(rng.choice(n1, n, replace=False))           # match i sits at keypoint slots1[i] of frame 1 (ascending)
+    slots2 = rng.permutation(n2)[:n]
+    k1, k2 = np.zeros(n1, KP_DTYPE), np.zeros(n2, KP_DTYPE)
+    for k, nn in ((k1, n1), (k2, n2)):
+        k['x'], k['y'] = rng.uniform(0, 640, nn).astype(f32), rng.uniform(0, 480, nn).astype(f32)
+        k['size'], k['angle'], k['octave'], k['class_id'] = 31, rng.uniform(0, 360, nn).astype(f32), 0, -1
+    k1['x'][slots1], k1['y'][slots1] = pts[:, 0], pts[:, 1]
+    k2['x'][slots2], k2['y'][slots2] = pts[:, 2], pts[:, 3]
+    m12 = np.full(n1, -1, np.int32)
+    m12[slots1] = slots2
+    return k1, k2, m12
+
+
+def write_scene(path, k1xy, k2xy, pairs, sigma, H21, H12, F21):
+    """The file tests/cpp/init_score_test.cpp reads: sizes, sigma, keypoint positions, mvMatches12, the hypotheses."""
+    K = len(H21 if H21 is not None else F21)
+    with open(path, 'wb') as f:
+        f.write(struct.pack('<6if', len(k1xy), len(k2xy), len(pairs), K, int(H21 is not None), int(F21 is not None), sigma))
+        for a, dt in ((k1xy, f32), (k2xy, f32), (pairs, np.int32), (H21, f32), (H12, f32), (F21, f32)):
+            if a is not None:
+                f.write(np.ascontiguousarray(a, dt).tobytes())
+    return path
+
+
+def kernel_constant(name):
+    """`constexpr int <name> = <value>;` of the kernel source."""
+    import re
+    return int(re.search(r'constexpr int %s = (\d+);' % name, open(KERNEL_SRC).read()).group(1))
+
+
+def compile_facade(out):
+    """tests/cpp/init_score_test.cpp with the restatement, linked against the library."""
+    from os1_amd import api
+    if not os.path.exists(api.lib_path()):
+        api.build_library()
+    cpp = os.path.join(ROOT, 'tests', 'cpp')
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Werror', '-ffp-contract=off', '-I' + os.path.join(ROOT, 'include'),
+                           os.path.join(cpp, 'init_score_test.cpp'), REF_SRC, '-o', out, api.lib_path(),
+                           '-Wl,-rpath,' + os.path.dirname(api.lib_path()), '-Wl,-rpath-link,/opt/rocm/lib'])
+    return out
+
+
+def run_facade(exe, scene_files):
+    r = subprocess.run([exe] + list(scene_files), capture_output=True, text=True, timeout=120)
+    lines = r.stdout.strip().splitlines()
+    assert r.returncode == 0 and lines and lines[-1] == 'PASS', r.stdout[-3000:] + r.stderr[-2000:]
+    return lines
