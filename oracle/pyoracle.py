@@ -3,12 +3,15 @@ importable from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg,
 import ctypes as C
 import os
 import subprocess
+import tempfile
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, 'liborb_oracle.so')
 # the reference's own DBoW2 BowVector.cpp + FeatureVector.cpp, built by oracle/Makefile where /root/reference exists
 DBOW2_REF_SO = os.path.join(_HERE, '_ref', 'libdbow2_vec.so')
+# the reference's own TemplatedVocabulary.h + ScoringObject.cpp (loader, descent, scores), built the same way
+DBOW2_VOC_SO = os.path.join(_HERE, '_ref', 'libdbow2_voc.so')
 
 KP_DTYPE = np.dtype([('x', 'f4'), ('y', 'f4'), ('size', 'f4'), ('angle', 'f4'), ('response', 'f4'),
                      ('octave', 'i4'), ('class_id', 'i4')])
@@ -99,6 +102,13 @@ class Oracle:
         if not self.have_dbow2_ref():
             return False
         return self.L.orc_use_dbow2_ref(DBOW2_REF_SO.encode()) == 0
+
+    def have_dbow2_voc(self):
+        return have_dbow2_voc()
+
+    def dbow2_vocabulary(self, image):
+        """the image loaded by the reference's own vocabulary code, or None where oracle/_ref/libdbow2_voc.so is absent"""
+        return dbow2_vocabulary(image)
 
     def bow_accumulator_is_reference(self):
         return bool(self.L.orc_bow_accumulator_is_reference())
@@ -358,6 +368,99 @@ class OracleVocabulary:
     def __del__(self):
         try:
             self.o.L.orc_vocab_destroy(self.h)
+        except Exception:
+            pass
+
+
+def have_dbow2_voc():
+    return os.path.exists(DBOW2_VOC_SO)
+
+
+_DBOW2_VOC_LIB = None
+# node_of_feature where the reference's single-feature transform never wrote the node id (the feature's word lies above level L - levelsup)
+NID_UNWRITTEN = 0xffffffff
+
+
+def _dbow2_voc_lib():
+    global _DBOW2_VOC_LIB
+    if _DBOW2_VOC_LIB is None:
+        L = C.CDLL(DBOW2_VOC_SO)
+        L.dbow2voc_open.restype = C.c_void_p
+        L.dbow2voc_open.argtypes = [C.c_char_p]
+        L.dbow2voc_close.argtypes = [C.c_void_p]
+        L.dbow2voc_close.restype = None
+        L.dbow2voc_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.dbow2voc_info.restype = None
+        L.dbow2voc_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.POINTER(C.c_int)] + \
+            [C.c_void_p] * 3 + [C.POINTER(C.c_int)] + [C.c_void_p] * 2
+        L.dbow2voc_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.dbow2voc_score.restype = C.c_double
+        _DBOW2_VOC_LIB = L
+    return _DBOW2_VOC_LIB
+
+
+def dbow2_vocabulary(image):
+    """The vocabulary image loaded by the reference's own code (Dbow2Vocabulary), or None where oracle/_ref/libdbow2_voc.so is absent."""
+    return Dbow2Vocabulary(image) if have_dbow2_voc() else None
+
+
+class Dbow2Vocabulary:
+    """The REFERENCE'S OWN DBoW2 vocabulary (oracle/_ref/libdbow2_voc.so <- oracle/dbow2_voc_wrap.cpp): its loadFromBinaryFile reads
+    the image (through a temporary file: it takes a file name, and prints a line to stdout while it loads), its transform and its
+    scoring object answer.  transform() returns what OracleVocabulary.transform returns, with one difference: node_of_feature is
+    NID_UNWRITTEN where the reference's single-feature transform left the node id untouched (a word above level L - levelsup, only in
+    trees with leaves at unequal depths).  For such a feature the reference's batch transform reads an uninitialised variable, so
+    the node it files the feature under in the FeatureVector is indeterminate; the oracle and the product file it under node 0."""
+
+    def __init__(self, image):
+        self.L = _dbow2_voc_lib()
+        fd, path = tempfile.mkstemp(suffix='.bin', prefix='dbow2voc_')
+        try:
+            with os.fdopen(fd, 'wb') as f:
+                f.write(bytes(image))
+            self.h = self.L.dbow2voc_open(path.encode())
+        finally:
+            os.unlink(path)
+        if not self.h:
+            raise ValueError("the reference's loadFromBinaryFile refuses this vocabulary image")
+
+    def info(self):
+        """size(), k, L, scoring and weighting type as the loaded object holds them; n_nodes counts the root"""
+        v = np.zeros(6, np.int32)
+        self.L.dbow2voc_info(self.h, _p(v))
+        return dict(zip(('size', 'k', 'L', 'scoring', 'weighting', 'n_nodes'), (int(x) for x in v)))
+
+    def transform(self, desc, levelsup=4):
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc)
+        ids = np.zeros(max(n, 1), np.uint32)
+        vals = np.zeros(max(n, 1), np.float64)
+        fvn = np.zeros(max(n, 1), np.uint32)
+        fvo = np.zeros(n + 1, np.uint32)
+        fvf = np.zeros(max(n, 1), np.uint32)
+        wof = np.zeros(max(n, 1), np.uint32)
+        nof = np.zeros(max(n, 1), np.uint32)
+        nw, nn = C.c_int(0), C.c_int(0)
+        self.L.dbow2voc_transform(self.h, _p(desc), n, levelsup, _p(ids), _p(vals), C.byref(nw), _p(fvn), _p(fvo), _p(fvf),
+                                  C.byref(nn), _p(wof), _p(nof))
+        nw, nn = nw.value, nn.value
+        return ids[:nw], vals[:nw], (fvn[:nn], fvo[:nn + 1], fvf[:int(fvo[nn])]), wof[:n], nof[:n]
+
+    def score(self, ids1, vals1, ids2, vals2):
+        """score(v1, v2) of two BowVectors given as (ascending ids, values), by the scoring object the loader created"""
+        ids1, ids2 = np.ascontiguousarray(ids1, np.uint32), np.ascontiguousarray(ids2, np.uint32)
+        vals1, vals2 = np.ascontiguousarray(vals1, np.float64), np.ascontiguousarray(vals2, np.float64)
+        assert len(ids1) == len(vals1) and len(ids2) == len(vals2)
+        return float(self.L.dbow2voc_score(self.h, _p(ids1), _p(vals1), len(ids1), _p(ids2), _p(vals2), len(ids2)))
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.dbow2voc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
