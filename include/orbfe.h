@@ -33,6 +33,7 @@ extern "C" {
 #define ORBFE_ERR_TOO_SMALL (-4) /* image too small: some pyramid level has <1 FAST cell column/row
                                     (the reference divides by zero there, ORBextractor.cc:820-823) */
 #define ORBFE_ERR_OVERFLOW (-5)  /* an output capacity was exceeded (outputs truncated)            */
+#define ORBFE_ERR_UNSUPPORTED (-6) /* the request is valid but this library has no bit-exact GPU form of it */
 
 /* Same 28-byte layout as cv::KeyPoint: pt.x, pt.y, size, angle, response, octave, class_id. */
 typedef struct OrbfeKeyPoint {
@@ -207,6 +208,31 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
 int orbfe_extract_batch_collect_matched(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out,
                                         int32_t* matches12, int* nmatches);
 
+/* Frame::UndistortKeyPoints (Frame.cc:284-319) on the GPU: a kernel behind the descriptor kernel restates
+ * cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) in IEEE double, bit for bit what orbfe_undistort_pinhole computes on the
+ * host, on the level-scaled keypoint positions.  dist = k1 k2 p1 p2 [k3 [k4 k5 k6]], ndist <= 8.
+ *   camera_mode 0 with (ndist == 0 or dist[0] == 0): the reference's identity case (Frame.cc:288, whatever the other coefficients
+ *     are): the handle behaves exactly like one without a camera -- nothing is launched or allocated, xy_un equals the keypoints.
+ *   camera_mode 1 (os1's equidistant fisheye): ORBFE_ERR_UNSUPPORTED, the handle stays as it was.  That model needs the host libm's
+ *     double tan bit for bit; undistort those keypoints with orbfe_undistort_equidistant.
+ * With a distorting camera set
+ *   - orbfe_extract_undistorted / orbfe_extract_batch_collect_undistorted also return mvKeysUn: xy_un [nframes][cap][2] floats, row f
+ *     = frame f in keypoint order (matches12 / nmatches of _collect_undistorted: as _collect_matched, or both NULL);
+ *   - orbfe_extract_batch_submit_matched searches on mvKeysUn: PosInGrid, the window's cell range and box test and vbPrevMatched
+ *     (:= F1's mvKeysUn) all take the undistorted float coordinates; `bounds` stays the caller's (orbfe_compute_image_bounds).  A
+ *     chain whose previous batch was matched without the camera (or the other way round) starts over, as after _chain_restart.
+ * May only be called while no batch is submitted.  orbfe_extractor_undistort runs the kernel with the handle's coefficients on n
+ * caller points, in place: the batched form of orbfe_undistort_pinhole.  Like that function it is cv::undistortPoints and NOT
+ * Frame::UndistortKeyPoints: it ignores the dist[0] == 0 short-cut of Frame.cc:288 and applies k2, p1, ... of an "identity" camera,
+ * where the extraction calls of the same handle return xy_un == xy.  A caller that wants the short-cut skips the call. */
+int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, float fy, float cx, float cy, const float* dist,
+                               int ndist);
+int orbfe_extractor_undistort(orbfe_extractor* h, float* xy, int n);
+int orbfe_extract_undistorted(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, size_t stride_bytes, OrbfeKeyPoint* kps,
+                              uint8_t* desc, int cap, int* n_out, float* xy_un);
+int orbfe_extract_batch_collect_undistorted(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, float* xy_un,
+                                            int32_t* matches12, int* nmatches);
+
 /* Stage accessors for the parity tests (state of the LAST extract call, frame index in batch). */
 int orbfe_debug_level_size(const orbfe_extractor* h, int level, int* w, int* hgt);
 int orbfe_debug_level_copy(orbfe_extractor* h, int frame, int level, uint8_t* out /* w*h, tight */);
@@ -311,6 +337,11 @@ int orbfe_stream_set_blur_variant(orbfe_stream* s, int variant);
  * pairs (pointers into the runner's buffers, valid until the next pop; feed them to orbfe_bow_assemble). */
 int orbfe_stream_set_vocabulary(orbfe_stream* s, orbfe_vocabulary* v, int levelsup);
 int orbfe_stream_bow_raw(orbfe_stream* s, int frame, const uint32_t** leaf_node, const uint32_t** level_node, int* n);
+/* orbfe_extractor_set_camera for every handle of the runner (only while no batch is in flight or held; an unsupported model changes
+ * nothing).  Streamed frames are then matched on mvKeysUn, and the frame pushed next has no predecessor.  orbfe_stream_xy_un returns
+ * mvKeysUn of the LAST POPPED batch, [batch][orbfe_stream_capacity][2] floats, valid until the next pop. */
+int orbfe_stream_set_camera(orbfe_stream* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist);
+int orbfe_stream_xy_un(orbfe_stream* s, const float** xy_un);
 /* Per-frame output capacity (keypoints) of the arrays returned by orbfe_stream_pop = their row stride.  It grows when a
  * push brings frames of a geometry that can return more keypoints (orbfe_extractor_max_keypoints_for_size); such a push
  * is only accepted while no batch is in flight or held. */
@@ -483,7 +514,8 @@ int orbfe_frame_create(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint
 /* From frame `frame_index` of the extractor's LAST COLLECTED batch (orbfe_extract / _batch / _collect): keypoints and
  * descriptors are taken where the kernels left them -- nothing is uploaded but, optionally, xy_un: the undistorted
  * coordinates [2 * n] of Frame::UndistortKeyPoints (Frame.cc:286-320; NULL = mvKeysUn = mvKeys, the camera without
- * distortion, :288-292).  Keypoint order = the order the extract call returned.  Must be called before the next
+ * distortion, :288-292 -- or, when the handle has a distorting camera (orbfe_extractor_set_camera), the mvKeysUn the undistortion
+ * kernel left in the arena: no coordinate is sent either way).  Keypoint order = the order the extract call returned.  Must be called before the next
  * submit / extract on that handle (its arena is reused); the frame itself then lives on independently. */
 int orbfe_frame_create_from_extract(orbfe_extractor* h, int frame_index, const float bounds[4], const float* xy_un,
                                     orbfe_frame** out);
@@ -955,6 +987,12 @@ int orbfe_stream_multi_set_blur_variant(orbfe_stream_multi* s, int variant);
 int orbfe_stream_multi_push(orbfe_stream_multi* s, const uint8_t* const* gray, int in_device_memory, int rows, int cols, size_t stride_bytes);
 int orbfe_stream_multi_pop(orbfe_stream_multi* s, const OrbfeKeyPoint** kps, const uint8_t** desc, const int** n_kps, const int32_t** matches12,
                            const int** nmatches);
+/* orbfe_stream_set_camera / orbfe_stream_xy_un for ONE stream over several devices: the camera goes to every runner, the boundary pairs (a batch's first frame against
+ * the last frame of the batch before, popped on another device) are searched on mvKeysUn too, and _xy_un returns mvKeysUn of the
+ * last popped batch, [batch][orbfe_stream_multi_capacity][2] floats, valid until the next pop. */
+int orbfe_stream_multi_set_camera(orbfe_stream_multi* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist,
+                                  int ndist);
+int orbfe_stream_multi_xy_un(orbfe_stream_multi* s, const float** xy_un);
 
 #ifdef __cplusplus
 }

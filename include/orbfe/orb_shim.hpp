@@ -116,10 +116,29 @@ class Extractor {
     check(orbfe_extractor_set_blur_variant(h_, variant));
   }
 
+  // The camera of the Frames built from this extractor's output (Frame.cc:284-319): with a distorting pinhole model the
+  // undistortion runs on the GPU behind the descriptor kernel, extractUndistorted() hands mvKeysUn out with mvKeys, and the
+  // resident frame of such a Frame takes its coordinates from the arena (MatcherContext::resident sends none).  camera_mode 1
+  // (equidistant) throws: orbfe_extractor_set_camera refuses it, Frames of such cameras keep orbfe::UndistortKeyPoints.
+  void SetCamera(int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist) {
+    std::lock_guard<std::mutex> g(mu_);
+    check(orbfe_extractor_set_camera(h_, camera_mode, fx, fy, cx, cy, dist, ndist));
+    camActive_ = ndist > 0 && dist[0] != 0.0f;
+    lastValid_ = false;
+  }
+
   // operator() core: KeyPointT must have cv::KeyPoint's 28-byte layout.
   template <class KeyPointT>
   void extract(const uint8_t* gray, int rows, int cols, size_t step, std::vector<KeyPointT>& keypoints,
                std::vector<uint8_t>& descriptors) {
+    extractUndistorted<KeyPointT>(gray, rows, cols, step, keypoints, nullptr, descriptors);
+  }
+
+  // extract() plus Frame::UndistortKeyPoints: keypointsUn (may be nullptr) = the records with pt replaced by the undistorted
+  // point (Frame.cc:310-316) -- equal to keypoints without a distorting camera (:288-292).
+  template <class KeyPointT>
+  void extractUndistorted(const uint8_t* gray, int rows, int cols, size_t step, std::vector<KeyPointT>& keypoints,
+                          std::vector<KeyPointT>* keypointsUn, std::vector<uint8_t>& descriptors) {
     static_assert(sizeof(KeyPointT) == sizeof(OrbfeKeyPoint), "KeyPointT must match cv::KeyPoint's layout");
     if (!gray || rows == 0 || cols == 0) return;  // reference: silent return, outputs untouched
     std::lock_guard<std::mutex> g(mu_);
@@ -128,10 +147,20 @@ class Extractor {
     kp_.resize(cap_);
     desc_.resize((size_t)cap_ * 32);
     int n = 0;
-    check(orbfe_extract(h_, gray, rows, cols, step, kp_.data(), desc_.data(), cap_, &n));
+    if (camActive_) {
+      xyUn_.resize((size_t)cap_ * 2);
+      check(orbfe_extract_undistorted(h_, gray, rows, cols, step, kp_.data(), desc_.data(), cap_, &n, xyUn_.data()));
+    } else {
+      check(orbfe_extract(h_, gray, rows, cols, step, kp_.data(), desc_.data(), cap_, &n));
+    }
     keypoints.clear();
     keypoints.resize(n);
     if (n) std::memcpy(static_cast<void*>(keypoints.data()), kp_.data(), (size_t)n * sizeof(OrbfeKeyPoint));
+    if (keypointsUn) {
+      *keypointsUn = keypoints;
+      if (camActive_)
+        for (int i = 0; i < n; i++) std::memcpy(static_cast<void*>(&(*keypointsUn)[i]), &xyUn_[2 * (size_t)i], 8);   // pt = the first two floats
+    }
     descriptors.assign(desc_.begin(), desc_.begin() + (size_t)n * 32);
     if (trackLast_ && n > 0) {
       lastN_ = n;
@@ -139,6 +168,10 @@ class Extractor {
       lastDesc_ = detail::Hash128();
       detail::hashBytes(lastKeys_, kp_.data(), (size_t)n * sizeof(OrbfeKeyPoint));
       detail::hashBytes(lastDesc_, desc_.data(), (size_t)n * 32);
+      if (camActive_) {
+        lastUn_ = detail::Hash128();
+        detail::hashBytes(lastUn_, xyUn_.data(), (size_t)n * 8);
+      }
       lastValid_ = true;
     }
   }
@@ -158,15 +191,33 @@ class Extractor {
   // A resident frame straight from the arena of whichever live Extractor on `device` produced exactly these outputs last
   // (n keypoints with fingerprint `keys` of the cv::KeyPoint records as returned, `desc` of the rows); xy_un = the
   // undistorted coordinates [2n] when they differ from the extracted ones, else nullptr.  nullptr if there is none.
+  // *coord_bytes (optional) receives the bytes of coordinates that had to be sent: 0 when the extractor has no distorting camera
+  // and xy_un is nullptr, and 0 when xy_un are the very coordinates its undistortion kernel left in the arena.
   static orbfe_frame* residentFromLastExtract(int device, int n, const detail::Hash128& keys, const detail::Hash128& desc,
-                                              const float bounds[4], const float* xy_un) {
+                                              const float bounds[4], const float* xy_un, size_t* coord_bytes = nullptr) {
     std::lock_guard<std::mutex> g(registryMutex());
     for (Extractor* e : registry()) {
       if (e->device_ != device) continue;
       std::lock_guard<std::mutex> ge(e->mu_);
       if (!e->lastValid_ || e->lastN_ != n || e->lastKeys_ != keys || e->lastDesc_ != desc) continue;
       orbfe_frame* f = nullptr;
-      if (orbfe_frame_create_from_extract(e->h_, 0, bounds, xy_un, &f) == ORBFE_OK && f && orbfe_frame_size(f) == n) return f;
+      const float* send = xy_un;
+      std::vector<float> raw;
+      if (e->camActive_) {
+        if (xy_un) {
+          detail::Hash128 hu;
+          detail::hashBytes(hu, xy_un, (size_t)n * 8);
+          if (hu == e->lastUn_) send = nullptr;   // the arena holds exactly these
+        } else {   // the Frame kept the extracted coordinates although the arena holds undistorted ones: send the extracted ones
+          raw.resize((size_t)n * 2);
+          for (int i = 0; i < n; i++) std::memcpy(&raw[2 * (size_t)i], &e->kp_[(size_t)i], 8);
+          send = raw.data();
+        }
+      }
+      if (orbfe_frame_create_from_extract(e->h_, 0, bounds, send, &f) == ORBFE_OK && f && orbfe_frame_size(f) == n) {
+        if (coord_bytes) *coord_bytes = send ? (size_t)n * 8 : 0;
+        return f;
+      }
       if (f) orbfe_frame_destroy(f);
     }
     return nullptr;
@@ -181,9 +232,10 @@ class Extractor {
   std::vector<OrbfeKeyPoint> kp_;
   std::vector<uint8_t> desc_;
   std::mutex mu_;                       // extract() vs. a search thread taking the arena's content
-  bool trackLast_ = true, lastValid_ = false;
+  bool trackLast_ = true, lastValid_ = false, camActive_ = false;
   int lastN_ = 0;
-  detail::Hash128 lastKeys_, lastDesc_;
+  detail::Hash128 lastKeys_, lastDesc_, lastUn_;
+  std::vector<float> xyUn_;
 };
 
 // One GPU matcher context per thread that runs searches (Tracking constructs ORBmatcher objects on
@@ -247,6 +299,7 @@ class MatcherContext {
   size_t residentUploads() const { return uploads_; }          // frames whose features crossed PCIe (orbfe_frame_create)
   size_t residentFromExtract() const { return fromExtract_; }  // frames taken from an extractor's arena (no upload)
   size_t residentHits() const { return hits_; }
+  size_t residentCoordBytes() const { return coordBytes_; }    // bytes of undistorted coordinates sent for frames taken from an arena
   // drop every cached frame (this context).  Tracking::Reset() / a map load call orbfe_resident_invalidate() instead,
   // which reaches the contexts of all threads.
   void invalidate() {
@@ -458,7 +511,10 @@ class MatcherContext {
                         sizeof(OrbfeKeyPoint) - 8) != 0)
           return nullptr;
     }
-    return Extractor::residentFromLastExtract(device_, n, hraw, hd, b, same ? nullptr : xy.data());
+    size_t sent = 0;
+    orbfe_frame* f = Extractor::residentFromLastExtract(device_, n, hraw, hd, b, same ? nullptr : xy.data(), &sent);
+    if (f) coordBytes_ += sent;
+    return f;
   }
   void trim() {
     const size_t keep = cap_ == 0 ? 0 : std::max<size_t>(cap_, 2);   // a search uses up to two frames: never evict those
@@ -469,7 +525,7 @@ class MatcherContext {
   }
   orbfe_matcher* m_ = nullptr;
   int device_ = 0;
-  size_t cap_ = 48, uploads_ = 0, fromExtract_ = 0, hits_ = 0;
+  size_t cap_ = 48, uploads_ = 0, fromExtract_ = 0, hits_ = 0, coordBytes_ = 0;
   unsigned long long epoch_ = 0;
   std::vector<Entry> cache_;
   struct Scratch { void* p = nullptr; size_t bytes = 0; };

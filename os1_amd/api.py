@@ -124,6 +124,18 @@ def load_library():
     L.orbfe_extractor_set_input_format.argtypes = [vp, ci, ci]
     L.orbfe_stream_set_input_format.argtypes = [vp, ci, ci]
     L.orbfe_extractor_set_blur_variant.argtypes = [vp, ci]
+    L.orbfe_extractor_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
+    L.orbfe_extractor_undistort.argtypes = [vp, vp, ci]
+    L.orbfe_stream_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
+    L.orbfe_stream_xy_un.argtypes = [vp, C.POINTER(vp)]
+    L.orbfe_stream_multi_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
+    L.orbfe_stream_multi_xy_un.argtypes = [vp, C.POINTER(vp)]
+    L.orbfe_sfi_chain_create.argtypes = [vp, C.POINTER(vp)]
+    L.orbfe_sfi_chain_destroy.argtypes = [vp]
+    L.orbfe_sfi_chain_destroy.restype = None
+    L.orbfe_extract_batch_submit_matched.argtypes = [vp, vp, ci, vp, ci, ci, ci, C.c_size_t, vp, ci, cf, ci]
+    L.orbfe_extract_undistorted.argtypes = [vp, vp, ci, ci, C.c_size_t, vp, vp, ci, C.POINTER(ci), vp]
+    L.orbfe_extract_batch_collect_undistorted.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
     L.orbfe_stream_set_blur_variant.argtypes = [vp, ci]
     L.orbfe_vocabulary_create.argtypes = [ci, ci, ci, ci, ci, vp, ci, C.POINTER(vp)]
     L.orbfe_vocabulary_create_from_image.argtypes = [ci, vp, C.c_size_t, C.POINTER(vp)]
@@ -302,6 +314,62 @@ class Extractor:
     def set_input_format(self, fmt='gray', variant=0):
         """Frames of later calls are interleaved 8-bit `fmt` pixels; variant 0 = 15-bit, 1 = 14-bit coefficients."""
         _check(self.L.orbfe_extractor_set_input_format(self.h, self.FORMATS[fmt], variant))
+
+    def set_camera(self, fx, fy, cx, cy, dist=(), mode=0):
+        """Frame::UndistortKeyPoints on the GPU for later calls (mode 0 = pinhole with dist = k1 k2 p1 p2 [k3 [k4 k5 k6]]; mode 1, the
+        equidistant model, raises OrbfeError with code -6)."""
+        d = np.ascontiguousarray(dist, np.float32)
+        _check(self.L.orbfe_extractor_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
+
+    def undistort(self, xy):
+        """The undistortion kernel on (n, 2) float32 points, with the camera of set_camera."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2).copy()
+        _check(self.L.orbfe_extractor_undistort(self.h, _p(xy) if len(xy) else None, len(xy)))
+        return xy
+
+    def extract_undistorted(self, image):
+        """image -> (keypoints, descriptors, xy_un[n, 2]): mvKeys, mDescriptors and mvKeysUn of one frame."""
+        image = np.asarray(image)
+        assert image.dtype == np.uint8 and image.ndim == 2 and image.strides[1] == 1
+        cap = max(self.cap, self.L.orbfe_extractor_max_keypoints_for_size(self.h, image.shape[0], image.shape[1]))
+        kps = np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        xy = np.zeros((cap, 2), np.float32)
+        n = C.c_int(0)
+        _check(self.L.orbfe_extract_undistorted(self.h, _p(image), image.shape[0], image.shape[1], image.strides[0], _p(kps),
+                                                _p(desc), cap, C.byref(n), _p(xy)))
+        return kps[:n.value].copy(), desc[:n.value].copy(), xy[:n.value].copy()
+
+    def collect_undistorted(self, matched=False):
+        """collect() plus xy_un[B, cap, 2]; matched=True (after submit_matched_ptrs): also (matches12[B, cap], nmatches[B])."""
+        B = self._pendingB
+        kps = np.zeros((B, self.cap), KP_DTYPE)
+        desc = np.zeros((B, self.cap, 32), np.uint8)
+        xy = np.zeros((B, self.cap, 2), np.float32)
+        n = np.zeros(B, np.int32)
+        m12 = np.full((B, self.cap), -1, np.int32) if matched else None
+        nm = np.zeros(B, np.int32) if matched else None
+        _check(self.L.orbfe_extract_batch_collect_undistorted(self.h, _p(kps), _p(desc), self.cap, _p(n), _p(xy),
+                                                              _p(m12) if matched else None, _p(nm) if matched else None))
+        return (kps, desc, n, xy, m12, nm) if matched else (kps, desc, n, xy)
+
+    def match_chain(self):
+        """A predecessor chain for submit_matched_ptrs (orbfe_sfi_chain_create); free it with free_match_chain."""
+        c = C.c_void_p()
+        _check(self.L.orbfe_sfi_chain_create(self.h, C.byref(c)))
+        return c
+
+    def free_match_chain(self, chain):
+        self.L.orbfe_sfi_chain_destroy(chain)
+
+    def submit_matched_ptrs(self, chain, ptrs, rows, cols, stride, on_device, bounds, window=100, nnratio=0.9, check_ori=True):
+        """orbfe_extract_batch_submit_matched: the batch, with SearchForInitialization of every frame against its predecessor."""
+        B = len(ptrs)
+        self._pending = (C.c_void_p * B)(*ptrs)
+        self._pendingB = B
+        b = np.asarray(bounds, np.float32)
+        _check(self.L.orbfe_extract_batch_submit_matched(self.h, chain, B, self._pending, int(on_device), rows, cols, stride, _p(b),
+                                                         window, nnratio, int(check_ori)))
 
     def extract_color(self, image):
         """image: (H, W, 3|4) uint8 host array in the format given to set_input_format."""
@@ -1448,6 +1516,17 @@ class Stream:
         self._voc = voc
         _check(self.L.orbfe_stream_set_vocabulary(self.h, voc.h if voc is not None else None, levelsup))
 
+    def set_camera(self, fx, fy, cx, cy, dist=(), mode=0):
+        """orbfe_stream_set_camera: streamed frames are matched on mvKeysUn; only while no batch is in flight."""
+        d = np.ascontiguousarray(dist, np.float32)
+        _check(self.L.orbfe_stream_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
+
+    def xy_un(self):
+        """mvKeysUn [B, cap, 2] of the last popped batch (a copy)."""
+        p = C.c_void_p()
+        _check(self.L.orbfe_stream_xy_un(self.h, C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(self.batch, self.cap, 2)).copy()
+
     def bow_raw(self, frame):
         """(leaf, node) arrays of frame `frame` of the last popped batch (copies)."""
         pl, pn, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
@@ -1534,6 +1613,17 @@ class MultiStream:
 
     def set_blur_variant(self, variant):
         _check(self.L.orbfe_stream_multi_set_blur_variant(self.h, int(variant)))
+
+    def set_camera(self, fx, fy, cx, cy, dist=(), mode=0):
+        """orbfe_stream_multi_set_camera: every runner and the boundary pairs match on mvKeysUn; only while no batch is in flight."""
+        d = np.ascontiguousarray(dist, np.float32)
+        _check(self.L.orbfe_stream_multi_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
+
+    def xy_un(self):
+        """mvKeysUn [B, cap, 2] of the last popped batch (a copy)."""
+        p = C.c_void_p()
+        _check(self.L.orbfe_stream_multi_xy_un(self.h, C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(self.batch, self.cap, 2)).copy()
 
     def device_of_next_push(self):
         return int(self.L.orbfe_stream_multi_device_of_next_push(self.h))

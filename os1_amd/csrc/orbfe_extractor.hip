@@ -54,7 +54,8 @@ int bow_assemble(orbfe_vocabulary* v, const uint2* ln, int n, uint32_t* bow_ids,
                  uint32_t* word_of_feature, uint32_t* node_of_feature);
 int bow_device(const orbfe_vocabulary* v);
 void launch_sfi(const SfiParams& S, int nframes, hipStream_t st);
-void launch_sfi_carry(const SfiParams& S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc, uint32_t* cCount,
+void launch_undistort(const UndistortArgs& A, hipStream_t st);
+void launch_sfi_carry(const SfiParams& S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc, uint32_t* cCount, float* cXyUn,
                       hipStream_t st);
 
 thread_local std::string g_err;
@@ -127,6 +128,9 @@ struct orbfe_sfi_chain {
   DevBuf<SelKp> sel[2];
   DevBuf<float> angle[2];
   DevBuf<uint8_t> desc[2];
+  DevBuf<float> xyUn[2];       // mvKeysUn of the carried level-0 keypoints (allocated by the first batch of a handle with a camera)
+  bool camera = false;         // the last batch was matched on mvKeysUn (a batch of the other kind starts the chain over: its carry lacks them)
+  std::vector<float> hostPrevXyUn;   // host-quadtree route, with a camera
   DevBuf<uint32_t> count;      // [0],[1]: level-0 count of the buffers; [2]: constant 0xffffffff ("none")
   hipEvent_t ready[2] = {};
   long long seq = 0;           // batches submitted so far
@@ -141,7 +145,7 @@ struct orbfe_sfi_chain {
   ~orbfe_sfi_chain() {
     (void)hipSetDevice(device);
     if (hostMatcher) orbfe_matcher_destroy(hostMatcher);
-    for (int i = 0; i < 2; i++) { sel[i].release(); angle[i].release(); desc[i].release(); if (ready[i]) (void)hipEventDestroy(ready[i]); }
+    for (int i = 0; i < 2; i++) { sel[i].release(); angle[i].release(); desc[i].release(); xyUn[i].release(); if (ready[i]) (void)hipEventDestroy(ready[i]); }
     count.release();
   }
 };
@@ -231,6 +235,15 @@ struct orbfe_extractor {
   View<float> d_angle, h_angle;
   View<uint8_t> d_desc, h_desc;
   View<int32_t> d_m12, h_m12, d_nm, h_nm;   // GPU SearchForInitialization outputs ([B][n0cap], [B])
+  // orbfe_extractor_set_camera: Frame::UndistortKeyPoints behind k_describe (k_undistort).  camActive = a distorting pinhole camera:
+  // the arena then carries mvKeysUn, two floats per slot; the identity case of Frame.cc:288 and a handle without a camera carve,
+  // launch and copy nothing new.
+  bool camSet = false, camActive = false;
+  CameraModel cam{};
+  View<float> d_xyUn, h_xyUn;
+  bool lastCam = false, submitCam = false;   // the last collected / submitted batch carries mvKeysUn
+  DevBuf<float> d_unTmp;                     // orbfe_extractor_undistort and the host-quadtree route: points of the caller
+  PinBuf<float> h_unTmp;
   DevBuf<uint16_t> d_sfiOrder;
   DevBuf<int> d_sfiOrderCount;
   DevBuf<uint32_t> d_sfiPool, d_sfiPcount;
@@ -254,6 +267,8 @@ struct orbfe_extractor {
   std::vector<uint8_t> defDesc;
   std::vector<int> defN, defNm;
   std::vector<int32_t> defM12;
+  std::vector<float> defXyUn;   // [frames][deferredCap][2] mvKeysUn, only with a distorting camera (deferredCam)
+  bool deferredCam = false;
   bool lastGpuQt = false, lastZeroCopy = false, submitZeroCopy = false;   // route of the last collected / submitted batch
   bool describe4 = true;         // ORBFE_DESCRIBE_WAVES=1: one wave per keypoint in one- / two-frame calls too
   float stageMs[5] = {0, 0, 0, 0, 0};
@@ -281,7 +296,7 @@ struct orbfe_extractor {
     d_tables.release(); d_coneTab.release(); d_coneTailTab.release(); d_slab.release(); d_in.release(); d_cellCount.release();
     d_sfiOrder.release(); d_sfiOrderCount.release(); d_sfiPool.release(); d_sfiPcount.release();
     d_cells.release(); d_zeros.release(); d_slots.release(); d_cand.release(); d_frame0.release(); d_gray.release(); d_outArena.release(); h_outArena.release();
-    d_f32tmp.release();
+    d_f32tmp.release(); d_unTmp.release(); h_unTmp.release();
     h_frame0.release(); h_cand.release();
     for (auto& es : ev) for (auto& e : es) if (e) (void)hipEventDestroy(e);
     for (auto& e : evS1) if (e) (void)hipEventDestroy(e);
@@ -556,7 +571,8 @@ struct orbfe_extractor {
         const size_t oLs = 0, oSc = oLs + al256(sizeof(uint32_t) * (kMaxLevels + 1) * nframes),
                      oSel = oSc + al256(sizeof(uint32_t) * kMaxLevels * nframes), oAng = oSel + al256(sizeof(SelKp) * maxKp),
                      oDesc = oAng + al256(sizeof(float) * maxKp), oM12 = oDesc + al256(32 * maxKp),
-                     oNm = oM12 + al256(sizeof(int32_t) * (size_t)(selOff[1] - selOff[0]) * nframes), total = oNm + al256(sizeof(int32_t) * nframes);
+                     oNm = oM12 + al256(sizeof(int32_t) * (size_t)(selOff[1] - selOff[0]) * nframes), oXy = oNm + al256(sizeof(int32_t) * nframes),
+                     total = oXy + (camActive ? al256(2 * sizeof(float) * maxKp) : 0);
         if ((rc = d_outArena.ensure(total))) return rc;
         if ((rc = h_outArena.ensure(total))) return rc;
         outArenaBytes = total;
@@ -568,6 +584,7 @@ struct orbfe_extractor {
         d_desc.p = D + oDesc; h_desc.p = Hh + oDesc;
         d_m12.p = (int32_t*)(D + oM12); h_m12.p = (int32_t*)(Hh + oM12);
         d_nm.p = (int32_t*)(D + oNm); h_nm.p = (int32_t*)(Hh + oNm);
+        d_xyUn.p = camActive ? (float*)(D + oXy) : nullptr; h_xyUn.p = camActive ? (float*)(Hh + oXy) : nullptr;
       }
       if (gpuQuadtree) {
         if ((rc = d_own.ensure((size_t)P.candCap * nframes))) return rc;
@@ -655,10 +672,29 @@ struct orbfe_extractor {
   }
 
   int runGpuQt(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, OrbfeKeyPoint* kps,
-               uint8_t* desc, int cap, int* n_out) {
+               uint8_t* desc, int cap, int* n_out, float* xy_un = nullptr) {
     int rc = submitGpuQt(nframes, gray, onDevice, r, c, stride);
     if (rc) return rc;
-    return waitGpuQt(kps, desc, cap, n_out);
+    return waitGpuQt(kps, desc, cap, n_out, nullptr, nullptr, xy_un);
+  }
+
+  // k_undistort on n points of the caller (in place): orbfe_extractor_undistort, and the host-quadtree route, whose keypoints are
+  // assembled on the host.  Runs the stored coefficients whatever they are (the identity case is the CALLERS' to skip).
+  int undistortPoints(float* xy, int n) {
+    if (n <= 0) return ORBFE_OK;
+    int rc;
+    if ((rc = d_unTmp.ensure(2 * (size_t)n)) || (rc = h_unTmp.ensure(2 * (size_t)n))) return rc;
+    hipStream_t st = streams[0];
+    memcpy(h_unTmp.p, xy, 2 * sizeof(float) * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(d_unTmp.p, h_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
+    UndistortArgs U{};
+    U.cam = cam; U.in = d_unTmp.p; U.sel = nullptr; U.selCount = nullptr; U.out = d_unTmp.p; U.n = n;
+    launch_undistort(U, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_unTmp.p, d_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(xy, h_unTmp.p, 2 * sizeof(float) * (size_t)n);
+    return ORBFE_OK;
   }
 
   bool submitProfiled = false, fastTimed = false;
@@ -814,6 +850,18 @@ struct orbfe_extractor {
       HIP_TRY(hipGetLastError());
     }
     const int nslots = nframes * selPerFrame;
+    submitCam = camActive;
+    if (camActive) {   // mvKeysUn of every live slot (Frame.cc:284-319), where the other results go
+      UndistortArgs U{};
+      U.cam = cam; U.in = nullptr; U.sel = d_sel.p; U.selCount = d_selCount.p;
+      U.out = zeroCopy ? h_xyUn.p : d_xyUn.p;
+      U.n = nslots; U.selPerFrame = selPerFrame; U.nlevels = nlevels;
+      for (int l = 0; l <= nlevels; l++) U.selOff[l] = selOff[l];
+      for (int l = 0; l < nlevels; l++) U.sf[l] = sf[l];
+      launch_undistort(U, st);
+      HIP_TRY(hipGetLastError());
+      if (kernelOut) HIP_TRY(hipMemcpyAsync(h_xyUn.p, d_xyUn.p, 2 * sizeof(float) * (size_t)nslots, hipMemcpyDeviceToHost, st));
+    }
     pendingBow = false;
     if (voc) {
       if ((rc = d_bow.ensure(nslots)) || (rc = h_bow.ensure(nslots))) return rc;
@@ -837,6 +885,14 @@ struct orbfe_extractor {
       const int prev = (int)((ch.seq + 1) & 1), cur = (int)(ch.seq & 1);   // buffer written by the previous / this batch
       SP.carrySel = ch.sel[prev].p; SP.carryAngle = ch.angle[prev].p; SP.carryDesc = ch.desc[prev].p;
       const bool iso = ch.isolated;   // every batch stands alone: no carry in, no carry out
+      if (camActive) {
+        for (int i = 0; i < 2; i++)
+          if ((rc = ch.xyUn[i].ensure(2 * (size_t)n0cap))) return rc;
+      }
+      if (ch.camera != camActive && ch.seq > 0) ch.restart = true;   // the carry was written on the other kind of coordinates
+      ch.camera = camActive;
+      SP.xyUn = camActive ? d_xyUn.p : nullptr;
+      SP.carryXyUn = camActive ? ch.xyUn[prev].p : nullptr;
       // (after a restart the carry is not read, but the batch still waits for the one before: it overwrites the buffer that one reads)
       SP.carryCount = ch.count.p + ((ch.seq == 0 || iso || ch.restart) ? 2 : prev);
       ch.restart = false;
@@ -851,7 +907,7 @@ struct orbfe_extractor {
       HIP_TRY(hipGetLastError());
       if (!iso) {
         // hand the last frame's level-0 data to the next batch
-        launch_sfi_carry(SP, nframes - 1, ch.sel[cur].p, ch.angle[cur].p, ch.desc[cur].p, ch.count.p + cur, st);
+        launch_sfi_carry(SP, nframes - 1, ch.sel[cur].p, ch.angle[cur].p, ch.desc[cur].p, ch.count.p + cur, camActive ? ch.xyUn[cur].p : nullptr, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ch.ready[cur], st));
       }
@@ -880,8 +936,9 @@ struct orbfe_extractor {
     return ORBFE_OK;
   }
 
+  // xy_un ([nframes][cap][2], optional): mvKeysUn -- from the arena with a distorting camera, else the keypoints' own coordinates
   int waitGpuQt(OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int32_t* matches12 = nullptr,
-                int* nmatches = nullptr) {
+                int* nmatches = nullptr, float* xy_un = nullptr) {
     if (!pendingFrames) { set_err("no submitted batch to collect"); return ORBFE_ERR_INVALID; }
     HIP_TRY(hipSetDevice(device));
     const int nframes = pendingFrames;
@@ -938,6 +995,11 @@ struct orbfe_extractor {
           ko[n] = kp;
           memcpy(dout + (size_t)n * 32, h_desc.p + (base + i) * 32, 32);
           if (pendingBow) bowKp[f].push_back(h_bow.p[base + i]);
+          if (xy_un) {
+            float* u = xy_un + ((size_t)f * cap + n) * 2;
+            u[0] = submitCam ? h_xyUn.p[2 * (base + i)] : kp.x;
+            u[1] = submitCam ? h_xyUn.p[2 * (base + i) + 1] : kp.y;
+          }
           n++;
         }
       }
@@ -971,6 +1033,7 @@ struct orbfe_extractor {
     lastGpuQt = true;
     lastZeroCopy = submitZeroCopy;
     lastLocalCand = submitLocalCand;
+    lastCam = submitCam;
     return status;
   }
 
@@ -980,7 +1043,7 @@ struct orbfe_extractor {
   //   per s : wait -> D2H candidates -> host quadtrees -> H2D selection -> describe -> D2H (async)
   //   all s : wait, assemble cv::KeyPoint-compatible outputs.
   int run(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, OrbfeKeyPoint* kps,
-          uint8_t* desc, int cap, int* n_out) {
+          uint8_t* desc, int cap, int* n_out, float* xy_un = nullptr) {
     if (pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
     HIP_TRY(hipSetDevice(device));
     int rc;
@@ -1159,6 +1222,18 @@ struct orbfe_extractor {
       }
       if (m > 0) memcpy(desc + (size_t)f * cap * 32, h_desc.p + (size_t)b * 32, (size_t)m * 32);
     }
+    if (xy_un && !camActive) {
+      for (int f = 0; f < nframes; f++)
+        for (int i = 0; i < std::min(frameKpCount[f], cap); i++) { xy_un[((size_t)f * cap + i) * 2] = kps[(size_t)f * cap + i].x; xy_un[((size_t)f * cap + i) * 2 + 1] = kps[(size_t)f * cap + i].y; }
+    } else if (xy_un) {   // mvKeysUn of the assembled keypoints: the same kernel, on one packed list of the whole batch
+      std::vector<float> pts;
+      for (int f = 0; f < nframes; f++)
+        for (int i = 0; i < std::min(frameKpCount[f], cap); i++) { pts.push_back(kps[(size_t)f * cap + i].x); pts.push_back(kps[(size_t)f * cap + i].y); }
+      if ((rc = undistortPoints(pts.data(), (int)(pts.size() / 2)))) return rc;
+      size_t q = 0;
+      for (int f = 0; f < nframes; f++)
+        for (int i = 0; i < std::min(frameKpCount[f], cap); i++, q += 2) { xy_un[((size_t)f * cap + i) * 2] = pts[q]; xy_un[((size_t)f * cap + i) * 2 + 1] = pts[q + 1]; }
+    }
     const double t5 = now_ms();
     stageMs[0] = (float)tWait;          // waiting for stage 1 + candidate D2H
     stageMs[1] = (float)tHostQt;        // host quadtrees + selection packing
@@ -1168,6 +1243,7 @@ struct orbfe_extractor {
     lastFrames = nframes;
     lastGpuQt = false;
     lastLocalCand = false;
+    lastCam = false;
     return status;
   }
 };
@@ -1193,6 +1269,7 @@ int extractor_view(orbfe_extractor* h, int frame, ExtractView* out) {
   out->sel = (z ? h->h_sel.p : h->d_sel.p) + base;
   out->angle = (z ? h->h_angle.p : h->d_angle.p) + base;
   out->desc = (z ? h->h_desc.p : h->d_desc.p) + base * 32;
+  out->xyUn = h->lastCam ? (z ? h->h_xyUn.p : h->d_xyUn.p) + base * 2 : nullptr;
   out->nlevels = h->nlevels;
   out->n = 0;
   for (int l = 0; l <= h->nlevels; l++) out->selOff[l] = h->selOff[l];
@@ -1611,8 +1688,8 @@ int orbfe_extractor_max_keypoints_for_size(const orbfe_extractor* h, int rows, i
   return n;
 }
 
-int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows,
-                        int cols, size_t stride_bytes, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out) {
+static int extract_batch_impl(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows,
+                              int cols, size_t stride_bytes, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, float* xy_un) {
   if (!h || !n_out) { set_err("NULL argument"); return ORBFE_ERR_INVALID; }
   if (nframes <= 0) return ORBFE_OK;
   for (int f = 0; f < nframes; f++) n_out[f] = 0;
@@ -1629,8 +1706,43 @@ int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* g
     if (rc) return rc;
   }
   if (h->gpuQuadtree && h->geomGpuQtOk)
-    return h->runGpuQt(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out);
-  return h->run(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out);
+    return h->runGpuQt(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out, xy_un);
+  return h->run(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out, xy_un);
+}
+
+int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows,
+                        int cols, size_t stride_bytes, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out) {
+  return extract_batch_impl(h, nframes, gray, in_device_memory, rows, cols, stride_bytes, kps, desc, cap, n_out, nullptr);
+}
+
+// Frame::UndistortKeyPoints on the GPU.  camera_mode 0 with (ndist == 0 or dist[0] == 0) is the reference's identity case
+// (Frame.cc:288: mvKeysUn = mvKeys whatever the other coefficients are): the handle then works exactly as one without a camera.
+int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist) {
+  if (!h || ndist < 0 || ndist > 8 || (ndist && !dist) || (camera_mode != 0 && camera_mode != 1)) { set_err("bad camera"); return ORBFE_ERR_INVALID; }
+  if (camera_mode == 1) {
+    set_err("the equidistant model needs the host libm's double tan bit for bit, which no GPU restatement reproduces: "
+            "undistort those keypoints with orbfe_undistort_equidistant on the host");
+    return ORBFE_ERR_UNSUPPORTED;
+  }
+  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  CameraModel C{};
+  for (int i = 0; i < ndist; i++) C.k[i] = dist[i];
+  C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy;
+  C.ifx = 1. / C.fx; C.ify = 1. / C.fy;
+  const bool active = ndist > 0 && dist[0] != 0.0f;
+  if (active != h->camActive) h->batchCap = 0;   // the result arena is carved again, with or without mvKeysUn
+  h->cam = C;
+  h->camSet = true;
+  h->camActive = active;
+  return ORBFE_OK;
+}
+
+int orbfe_extractor_undistort(orbfe_extractor* h, float* xy, int n) {
+  if (!h || n < 0 || (n && !xy)) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (!h->camSet) { set_err("the extractor has no camera (orbfe_extractor_set_camera)"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(h->device));
+  return h->undistortPoints(xy, n);
 }
 
 // The GPU quadtree takes 1..4 root nodes per level and at most 2 044 features per level; outside that (very wide strips,
@@ -1653,8 +1765,10 @@ static int deferred_extract(orbfe_extractor* h, int nframes, const uint8_t* cons
   h->defKps.resize((size_t)nframes * cap);
   h->defDesc.resize((size_t)nframes * cap * 32);
   h->defN.assign(nframes, 0);
-  const int rc = orbfe_extract_batch(h, nframes, gray, in_device_memory, rows, cols, stride_bytes, h->defKps.data(), h->defDesc.data(),
-                                     cap, h->defN.data());
+  if (h->camActive) h->defXyUn.resize((size_t)nframes * cap * 2);   // (without a distorting camera mvKeysUn are the keypoints themselves)
+  const int rc = extract_batch_impl(h, nframes, gray, in_device_memory, rows, cols, stride_bytes, h->defKps.data(), h->defDesc.data(),
+                                    cap, h->defN.data(), h->camActive ? h->defXyUn.data() : nullptr);
+  h->deferredCam = h->camActive;
   if (rc) return rc;
   h->deferredFrames = nframes;
   h->deferredMatched = false;
@@ -1662,7 +1776,7 @@ static int deferred_extract(orbfe_extractor* h, int nframes, const uint8_t* cons
 }
 
 static int deferred_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int32_t* matches12,
-                            int* nmatches) {
+                            int* nmatches, float* xy_un = nullptr) {
   const int nframes = h->deferredFrames, dcap = h->deferredCap;
   h->deferredFrames = 0;
   int status = ORBFE_OK;
@@ -1673,6 +1787,9 @@ static int deferred_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* des
     const int m = std::min(n, cap);
     memcpy(kps + (size_t)f * cap, h->defKps.data() + (size_t)f * dcap, sizeof(OrbfeKeyPoint) * (size_t)m);
     memcpy(desc + (size_t)f * cap * 32, h->defDesc.data() + (size_t)f * dcap * 32, 32 * (size_t)m);
+    if (xy_un && h->deferredCam) memcpy(xy_un + (size_t)f * cap * 2, h->defXyUn.data() + (size_t)f * dcap * 2, 2 * sizeof(float) * (size_t)m);
+    else if (xy_un)
+      for (int i = 0; i < m; i++) { xy_un[((size_t)f * cap + i) * 2] = h->defKps[(size_t)f * dcap + i].x; xy_un[((size_t)f * cap + i) * 2 + 1] = h->defKps[(size_t)f * dcap + i].y; }
     if (matches12 && nmatches) {
       int32_t* row = matches12 + (size_t)f * cap;
       for (int i = 0; i < cap; i++) row[i] = -1;
@@ -1711,6 +1828,13 @@ int orbfe_extract_batch_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t*
   if (!h || !kps || !desc || !n_out || cap <= 0) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   if (h->deferredFrames) return deferred_collect(h, kps, desc, cap, n_out, nullptr, nullptr);
   return h->waitGpuQt(kps, desc, cap, n_out);
+}
+
+int orbfe_extract_batch_collect_undistorted(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, float* xy_un,
+                                            int32_t* matches12, int* nmatches) {
+  if (!h || !kps || !desc || !n_out || !xy_un || cap <= 0 || (!matches12) != (!nmatches)) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  if (h->deferredFrames) return deferred_collect(h, kps, desc, cap, n_out, matches12, nmatches, xy_un);
+  return h->waitGpuQt(kps, desc, cap, n_out, matches12, nmatches, xy_un);
 }
 
 int orbfe_sfi_chain_create(const orbfe_extractor* h, orbfe_sfi_chain** out) {
@@ -1778,20 +1902,37 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
     std::vector<std::vector<float>> pxy;
     std::vector<float*> prev;
     std::vector<int32_t*> m12;
+    // with a distorting camera the searches run on mvKeysUn: the keypoints with their coordinates replaced (Frame.cc:284-319)
+    const bool cam = h->camActive;
+    if (cam != chain->camera) chain->hostPrevValid = false;   // the carry holds the other kind of coordinates
+    chain->camera = cam;
+    std::vector<OrbfeKeyPoint> unKps, unPrev;
+    if (cam) {
+      unKps = h->defKps;
+      for (int f = 0; f < nframes; f++)
+        for (int j = 0; j < h->defN[f]; j++) {
+          unKps[(size_t)f * cap + j].x = h->defXyUn[((size_t)f * cap + j) * 2];
+          unKps[(size_t)f * cap + j].y = h->defXyUn[((size_t)f * cap + j) * 2 + 1];
+        }
+      unPrev = chain->hostPrevKps;
+      if (chain->hostPrevValid)
+        for (size_t j = 0; j < unPrev.size(); j++) { unPrev[j].x = chain->hostPrevXyUn[2 * j]; unPrev[j].y = chain->hostPrevXyUn[2 * j + 1]; }
+    }
+    const OrbfeKeyPoint* curKps = cam ? unKps.data() : h->defKps.data();
     for (int f = 0; f < nframes; f++) {
       const OrbfeKeyPoint* pk;
       const uint8_t* pd;
       int pn;
       if (f == 0) {
         if (!chain->hostPrevValid || chain->isolated || chain->restart) continue;   // very first frame of the stream (or isolated batches): no predecessor
-        pk = chain->hostPrevKps.data(); pd = chain->hostPrevDesc.data(); pn = (int)chain->hostPrevKps.size();
+        pk = cam ? unPrev.data() : chain->hostPrevKps.data(); pd = chain->hostPrevDesc.data(); pn = (int)chain->hostPrevKps.size();
       } else {
-        pk = h->defKps.data() + (size_t)(f - 1) * cap; pd = h->defDesc.data() + (size_t)(f - 1) * cap * 32; pn = h->defN[f - 1];
+        pk = curKps + (size_t)(f - 1) * cap; pd = h->defDesc.data() + (size_t)(f - 1) * cap * 32; pn = h->defN[f - 1];
       }
       pxy.emplace_back((size_t)std::max(pn, 1) * 2);
       for (int j = 0; j < pn; j++) { pxy.back()[2 * j] = pk[j].x; pxy.back()[2 * j + 1] = pk[j].y; }   // vbPrevMatched := F1's keypoints (Tracking.cc:355-357)
       k1.push_back(pk); d1.push_back(pd); n1.push_back(pn);
-      k2.push_back(h->defKps.data() + (size_t)f * cap); d2.push_back(h->defDesc.data() + (size_t)f * cap * 32); n2.push_back(h->defN[f]);
+      k2.push_back(curKps + (size_t)f * cap); d2.push_back(h->defDesc.data() + (size_t)f * cap * 32); n2.push_back(h->defN[f]);
       m12.push_back(h->defM12.data() + (size_t)f * cap);
       frameOf.push_back(f);
     }
@@ -1807,6 +1948,7 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
     const int last = nframes - 1, ln = h->defN[last];
     chain->hostPrevKps.assign(h->defKps.begin() + (size_t)last * cap, h->defKps.begin() + (size_t)last * cap + ln);
     chain->hostPrevDesc.assign(h->defDesc.begin() + (size_t)last * cap * 32, h->defDesc.begin() + ((size_t)last * cap + ln) * 32);
+    if (cam) chain->hostPrevXyUn.assign(h->defXyUn.begin() + (size_t)last * cap * 2, h->defXyUn.begin() + ((size_t)last * cap + ln) * 2);
     chain->hostPrevValid = !chain->isolated;
     chain->restart = false;
     h->deferredMatched = true;
@@ -1836,6 +1978,15 @@ int orbfe_extract(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, s
   if (!gray || rows == 0 || cols == 0) return ORBFE_OK;
   const uint8_t* frames[1] = {gray};
   return orbfe_extract_batch(h, 1, frames, 0, rows, cols, stride_bytes, kps, desc, cap, n_out);
+}
+
+int orbfe_extract_undistorted(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, size_t stride_bytes, OrbfeKeyPoint* kps,
+                              uint8_t* desc, int cap, int* n_out, float* xy_un) {
+  if (!n_out || !xy_un) { set_err("n_out or xy_un is NULL"); return ORBFE_ERR_INVALID; }
+  *n_out = 0;
+  if (!gray || rows == 0 || cols == 0) return ORBFE_OK;
+  const uint8_t* frames[1] = {gray};
+  return extract_batch_impl(h, 1, frames, 0, rows, cols, stride_bytes, kps, desc, cap, n_out, xy_un);
 }
 
 int orbfe_debug_level_size(const orbfe_extractor* h, int level, int* w, int* hgt) {

@@ -66,6 +66,7 @@ __global__ __launch_bounds__(256) void k_frame_from_host(const OrbfeKeyPoint* __
 
 struct ExtractViewDev {
   const orbfe::SelKp* sel; const float* angle; const uint8_t* desc;
+  const float* xyUnSlot;   // mvKeysUn per slot, left in the arena by k_undistort (the handle has a distorting camera), else nullptr
   int selOff[orbfe::kMaxLevels + 1], count[orbfe::kMaxLevels];
   float sf[orbfe::kMaxLevels];
   int nlevels;
@@ -73,7 +74,8 @@ struct ExtractViewDev {
 
 // one frame of an extractor's result arena -> keypoint-order arrays, in the order orbfe_extract returns the keypoints
 // (levels 0..n-1, list order inside a level; ORBextractor.cc:959-967: pt *= mvScaleFactor[level] for level > 0).
-// xyUn != nullptr: the caller's undistorted coordinates (Frame::UndistortKeyPoints, Frame.cc:286-320) replace pt.
+// xyUn != nullptr: the caller's undistorted coordinates (Frame::UndistortKeyPoints, Frame.cc:286-320) replace pt; otherwise the
+// arena's own (V.xyUnSlot) do when the extractor has a distorting camera -- no coordinate crosses the bus.
 __global__ __launch_bounds__(256) void k_frame_from_extract(ExtractViewDev V, const float* __restrict__ xyUn, FrameDev F) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= F.n) return;
@@ -84,6 +86,7 @@ __global__ __launch_bounds__(256) void k_frame_from_extract(ExtractViewDev V, co
   float x = (float)(s.xy & 0xffff), y = (float)(s.xy >> 16);
   if (l != 0) { x *= V.sf[l]; y *= V.sf[l]; }
   if (xyUn) { x = xyUn[2 * i]; y = xyUn[2 * i + 1]; }
+  else if (V.xyUnSlot) { x = V.xyUnSlot[2 * slot]; y = V.xyUnSlot[2 * slot + 1]; }
   F.x[i] = x; F.y[i] = y; F.angle[i] = V.angle[slot]; F.oct[i] = l;
   copy32(F.desc + (size_t)i * 32, V.desc + (size_t)slot * 32);
 }
@@ -1036,7 +1039,7 @@ int orbfe_frame_create_from_extract(orbfe_extractor* h, int frame_index, const f
       dxy = (const float*)f->D.tdesc;
     }
     ExtractViewDev D;
-    D.sel = V.sel; D.angle = V.angle; D.desc = V.desc; D.nlevels = V.nlevels;
+    D.sel = V.sel; D.angle = V.angle; D.desc = V.desc; D.xyUnSlot = V.xyUn; D.nlevels = V.nlevels;
     for (int l = 0; l <= orbfe::kMaxLevels; l++) D.selOff[l] = l <= V.nlevels ? V.selOff[l] : 0;
     for (int l = 0; l < orbfe::kMaxLevels; l++) { D.count[l] = l < V.nlevels ? V.count[l] : 0; D.sf[l] = l < V.nlevels ? V.sf[l] : 1.f; }
     hipLaunchKernelGGL(k_frame_from_extract, dim3((V.n + 255) / 256), dim3(256), 0, st, D, dxy, f->D);

@@ -117,6 +117,7 @@ struct ExtractView {
   const SelKp* sel;            // first slot of the frame
   const float* angle;
   const uint8_t* desc;
+  const float* xyUn;           // mvKeysUn of the frame's slots (two floats per slot) when the handle has a distorting camera, else nullptr
   int selOff[kMaxLevels + 1];  // first slot of every level inside the frame's slot region
   int count[kMaxLevels];       // keypoints per level (host copy of selCount)
   float sf[kMaxLevels];        // mvScaleFactor
@@ -137,6 +138,10 @@ struct SfiParams {
   const float* carryAngle;
   const uint8_t* carryDesc;
   const uint32_t* carryCount;   // device word; > n0cap (0xffffffff) = no predecessor
+  // mvKeysUn of the batch (k_undistort), two floats per slot in the arena's slot order, and of the carried predecessor; nullptr (no
+  // camera on the submitting handle): the kernels take the packed integer positions of `sel`, which ARE mvKeysUn for an ideal pinhole
+  const float* xyUn;
+  const float* carryXyUn;
   float minX, minY, invW, invH; // Frame grid (Frame.cc:98-99)
   float window, nnratio;
   int checkOri;
@@ -148,6 +153,26 @@ struct SfiParams {
   // outputs (inside the result arena)
   int32_t* matches12;           // [nframes][n0cap] vnMatches12 restricted to level-0 queries
   int32_t* nmatches;            // [nframes]
+};
+
+// ---- Frame::UndistortKeyPoints on the GPU (orbfe_undistort.hip) ------------------------------------------
+// K and the distortion coefficients as the doubles cv::undistortPoints works on (float inputs widened; ifx = 1 / fx, ify = 1 / fy).
+struct CameraModel {
+  double fx, fy, cx, cy, ifx, ify;
+  double k[8];   // k1 k2 p1 p2 k3 k4 k5 k6
+};
+// One lane per point.  Slot mode (sel != nullptr): point i is slot i of the result arena -- its level follows from selOff, it is live
+// iff its index inside the level is below selCount, and its distorted position is the level-scaled pt of the collect path
+// (ORBextractor.cc:959-965).  Point mode (sel == nullptr): `in` holds n float pairs.
+struct UndistortArgs {
+  CameraModel cam;
+  const float* in;
+  const SelKp* sel;
+  const uint32_t* selCount;   // [nframes][kMaxLevels]
+  float* out;                 // n float pairs
+  int n, selPerFrame, nlevels;
+  int selOff[kMaxLevels + 1];
+  float sf[kMaxLevels];       // mvScaleFactor
 };
 
 // ---- GPU quadtree (orbfe_quadtree.hip) -------------------------------------------------------------

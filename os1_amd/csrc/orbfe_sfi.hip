@@ -29,6 +29,7 @@ constexpr int kSfiThLow = 50, kSfiHisto = 30;        // TH_LOW, HISTO_LENGTH (OR
 
 // level-0 keypoint data of frame f (or of the carried predecessor)
 struct SfiFrame {
+  const float2* xyUn;   // mvKeysUn of the level-0 keypoints (the submitting handle has a camera), else nullptr
   const SelKp* sel;
   const float* angle;
   const uint8_t* desc;
@@ -39,17 +40,28 @@ __device__ __forceinline__ SfiFrame sfi_frame(const SfiParams& S, int f) {
   SfiFrame F;
   if (f < 0) {
     F.sel = S.carrySel; F.angle = S.carryAngle; F.desc = S.carryDesc;
+    F.xyUn = reinterpret_cast<const float2*>(S.carryXyUn);
     F.n = S.carryCount ? (int)*S.carryCount : -1;
     if (F.n > S.n0cap) F.n = -1;   // 0xffffffff = no predecessor yet
   } else {
     const long long base = (long long)f * S.selPerFrame;   // level 0 is the first region of a frame's slots
     F.sel = S.sel + base; F.angle = S.angle + base; F.desc = S.desc + base * 32;
+    F.xyUn = S.xyUn ? reinterpret_cast<const float2*>(S.xyUn) + base : nullptr;
     F.n = (int)S.selCount[(long long)f * kMaxLevels];
   }
   return F;
 }
 
+// position of level-0 keypoint k: UN = mvKeysUn (float), else the packed integer position (an ideal pinhole's mvKeysUn)
+template <bool UN>
+__device__ __forceinline__ float2 sfi_pos(const SfiFrame& F, int k) {
+  if (UN) return F.xyUn[k];
+  const uint32_t xy = F.sel[k].xy;
+  return make_float2((float)(xy & 0xffff), (float)(xy >> 16));
+}
+
 // ---- per frame: candidate enumeration order -------------------------------------------------------------
+template <bool UN>
 __global__ __launch_bounds__(256) void k_sfi_sort(SfiParams S) {
   // counting sort by grid cell; inside a cell by keypoint index (the order mGrid's vectors were filled in)
   constexpr int kCells = kSfiGridCols * kSfiGridRows, kPer = kCells / 256;
@@ -65,8 +77,8 @@ __global__ __launch_bounds__(256) void k_sfi_sort(SfiParams S) {
   for (int c = tid; c <= kCells; c += 256) start[c] = 0;
   __syncthreads();
   for (int k = tid; k < F.n; k += 256) {
-    const uint32_t xy = F.sel[k].xy;
-    const float x = (float)(xy & 0xffff), y = (float)(xy >> 16);
+    const float2 p = sfi_pos<UN>(F, k);
+    const float x = p.x, y = p.y;
     const int px = (int)roundf((x - S.minX) * S.invW), py = (int)roundf((y - S.minY) * S.invH);   // Frame.cc:266-267
     const int c = (px < 0 || px >= kSfiGridCols || py < 0 || py >= kSfiGridRows) ? -1 : px * kSfiGridRows + py;
     cellOf[k] = c;
@@ -109,6 +121,7 @@ __global__ __launch_bounds__(256) void k_sfi_sort(SfiParams S) {
 }
 
 // ---- per (pair, query): ordered candidate list with distances -------------------------------------------------
+template <bool UN>
 __global__ __launch_bounds__(64) void k_sfi_candidates(SfiParams S) {
   const int i1 = blockIdx.x, fr = blockIdx.y, lane = threadIdx.x;
   const int f = S.frameBase + fr;
@@ -119,8 +132,21 @@ __global__ __launch_bounds__(64) void k_sfi_candidates(SfiParams S) {
     if (lane == 0 && i1 < S.n0cap) *cnt = 0;
     return;
   }
-  const uint32_t qxy = F1.sel[i1].xy;
-  const float x = (float)(qxy & 0xffff), y = (float)(qxy >> 16), r = S.window;
+  const float2 q = sfi_pos<UN>(F1, i1);
+  const float x = q.x, y = q.y, r = S.window;
+  // GetFeaturesInArea's cell range (Frame.cc:214-228).  On integer positions every keypoint inside the box lies in a cell of the
+  // range, so the box test alone decides; on float positions the range is applied as the reference applies it.
+  int cx0 = 0, cx1 = kSfiGridCols - 1, cy0 = 0, cy1 = kSfiGridRows - 1;
+  if (UN) {
+    cx0 = max(0, (int)floorf((x - S.minX - r) * S.invW));
+    cx1 = min(kSfiGridCols - 1, (int)ceilf((x - S.minX + r) * S.invW));
+    cy0 = max(0, (int)floorf((y - S.minY - r) * S.invH));
+    cy1 = min(kSfiGridRows - 1, (int)ceilf((y - S.minY + r) * S.invH));
+    if (cx0 >= kSfiGridCols || cx1 < 0 || cy0 >= kSfiGridRows || cy1 < 0) {   // :216-228: no cell, no candidate
+      if (lane == 0) *cnt = 0;
+      return;
+    }
+  }
   uint32_t qd[8];
   const uint32_t* qp = reinterpret_cast<const uint32_t*>(F1.desc + (long long)i1 * 32);
 #pragma unroll
@@ -136,9 +162,13 @@ __global__ __launch_bounds__(64) void k_sfi_candidates(SfiParams S) {
     int i2 = 0;
     if (e < nin) {
       i2 = order[e];
-      const uint32_t xy = F2.sel[i2].xy;
-      const float dx = (float)(xy & 0xffff) - x, dy = (float)(xy >> 16) - y;
+      const float2 p = sfi_pos<UN>(F2, i2);
+      const float dx = p.x - x, dy = p.y - y;
       ok = fabsf(dx) < r && fabsf(dy) < r;   // Frame.cc:252-256 (levels are 0 by construction)
+      if (UN) {   // the keypoint's own cell (Frame.cc:266-267; it is in the grid, or k_sfi_sort would not list it)
+        const int px = (int)roundf((p.x - S.minX) * S.invW), py = (int)roundf((p.y - S.minY) * S.invH);
+        ok = ok && px >= cx0 && px <= cx1 && py >= cy0 && py <= cy1;
+      }
     }
     const unsigned long long m = __ballot(ok);
     if (ok) {
@@ -429,27 +459,34 @@ int sfi_debug_read(int* out, int capRecords, int reset) {
 
 // Hand the level-0 data of the batch's last frame to the next batch (one small kernel instead of four D2D copies).
 __global__ __launch_bounds__(256) void k_sfi_carry(SfiParams S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc,
-                                                   uint32_t* cCount) {
+                                                   uint32_t* cCount, float2* cXyUn) {
   const long long base = (long long)lastFrame * S.selPerFrame;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < S.n0cap) {
     cSel[i] = S.sel[base + i];
     cAngle[i] = S.angle[base + i];
+    if (cXyUn) cXyUn[i] = reinterpret_cast<const float2*>(S.xyUn)[base + i];   // the predecessor's mvKeysUn go with it
   }
   if (i < S.n0cap * 8)
     reinterpret_cast<uint32_t*>(cDesc)[i] = reinterpret_cast<const uint32_t*>(S.desc + base * 32)[i];
   if (i == 0) *cCount = S.selCount[(long long)lastFrame * kMaxLevels];
 }
 
-void launch_sfi_carry(const SfiParams& S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc, uint32_t* cCount,
+void launch_sfi_carry(const SfiParams& S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc, uint32_t* cCount, float* cXyUn,
                       hipStream_t st) {
-  hipLaunchKernelGGL(k_sfi_carry, dim3((S.n0cap * 8 + 255) / 256), dim3(256), 0, st, S, lastFrame, cSel, cAngle, cDesc, cCount);
+  hipLaunchKernelGGL(k_sfi_carry, dim3((S.n0cap * 8 + 255) / 256), dim3(256), 0, st, S, lastFrame, cSel, cAngle, cDesc, cCount,
+                     S.xyUn ? reinterpret_cast<float2*>(cXyUn) : nullptr);
 }
 
 void launch_sfi(const SfiParams& S, int nframes, hipStream_t st) {
   sfi_debug_setup();
-  hipLaunchKernelGGL(k_sfi_sort, dim3(nframes), dim3(256), sizeof(int) * 3 * S.n0cap, st, S);
-  hipLaunchKernelGGL(k_sfi_candidates, dim3(S.n0cap, nframes), dim3(64), 0, st, S);
+  if (S.xyUn) {   // the submitting handle has a camera: every position is mvKeysUn
+    hipLaunchKernelGGL(k_sfi_sort<true>, dim3(nframes), dim3(256), sizeof(int) * 3 * S.n0cap, st, S);
+    hipLaunchKernelGGL(k_sfi_candidates<true>, dim3(S.n0cap, nframes), dim3(64), 0, st, S);
+  } else {
+    hipLaunchKernelGGL(k_sfi_sort<false>, dim3(nframes), dim3(256), sizeof(int) * 3 * S.n0cap, st, S);
+    hipLaunchKernelGGL(k_sfi_candidates<false>, dim3(S.n0cap, nframes), dim3(64), 0, st, S);
+  }
   const int fixedWords = 6 * S.n0cap + 1 + 32 + 2;
   int ldsPool = (60 * 1024 / 4) - fixedWords;   // candidate entries kept in LDS; longer pools are read from HBM
   if (ldsPool > 8192) ldsPool = 8192;

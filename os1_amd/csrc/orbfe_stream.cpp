@@ -48,6 +48,8 @@ struct Slot {
   std::vector<int> nm;
   std::vector<float> prevxy;   // [cap][2] query centres of row 0 (matchFrame0)
   std::vector<uint32_t> bowLeaf, bowNode;   // [batch][cap], with a vocabulary set
+  std::vector<float> xyUn, prevXyUn;        // [batch][cap][2] mvKeysUn, and the predecessor's, with a camera set
+  bool camera = false;                      // the stream had a camera at push time
   // predecessor of frame 0 (last frame of the previous batch), copied at collect time
   std::vector<OrbfeKeyPoint> prevKps;
   std::vector<uint8_t> prevDesc;
@@ -123,6 +125,8 @@ struct orbfe_stream {
   long long pushSeq = 0, popSeq = 0;
   int channels = 1;   // bytes per pixel of the pushed frames (orbfe_stream_set_input_format)
   bool bow = false;   // orbfe_stream_set_vocabulary
+  bool camera = false;   // orbfe_stream_set_camera
+  std::vector<float> lastXyUn;
 
   // last frame of the previous batch (the predecessor of frame 0 of the next one)
   std::vector<OrbfeKeyPoint> lastKps;
@@ -147,6 +151,13 @@ struct orbfe_stream {
     for (int j = 0; j < s.prevN; j++) { pxy[2 * j] = s.prevKps[j].x; pxy[2 * j + 1] = s.prevKps[j].y; }
     int32_t* row = s.m12.data();
     std::fill(row, row + cap, -1);
+    if (s.camera) {   // the search runs on mvKeysUn of both frames, vbPrevMatched := F1's mvKeysUn (Tracking.cc:355-357)
+      std::vector<OrbfeKeyPoint> k1(s.prevKps.begin(), s.prevKps.begin() + s.prevN), k2(s.kps.begin(), s.kps.begin() + s.n[0]);
+      for (int j = 0; j < s.prevN; j++) { k1[j].x = pxy[2 * j] = s.prevXyUn[2 * j]; k1[j].y = pxy[2 * j + 1] = s.prevXyUn[2 * j + 1]; }
+      for (int j = 0; j < s.n[0]; j++) { k2[j].x = s.xyUn[2 * j]; k2[j].y = s.xyUn[2 * j + 1]; }
+      return orbfe_search_for_initialization(frame0Matcher, k1.data(), s.prevDesc.data(), s.prevN, k2.data(), s.desc.data(), s.n[0],
+                                             s.bounds, pxy, row, s.window, s.nnratio, s.checkOri, &s.nm[0]);
+    }
     return orbfe_search_for_initialization(frame0Matcher, s.prevKps.data(), s.prevDesc.data(), s.prevN, s.kps.data(), s.desc.data(), s.n[0],
                                            s.bounds, pxy, row, s.window, s.nnratio, s.checkOri, &s.nm[0]);
   }
@@ -200,7 +211,12 @@ struct orbfe_stream {
       Slot& s = slots[slot];
       if (s.status == ORBFE_OK) {
         const double ta = nowMs();
-        if (s.window > 0)
+        if (s.camera) {
+          s.xyUn.resize((size_t)batch * cap * 2);
+          const bool m = s.window > 0;
+          s.status = orbfe_extract_batch_collect_undistorted(ext[e], s.kps.data(), s.desc.data(), cap, s.n.data(), s.xyUn.data(),
+                                                             m ? s.m12.data() : nullptr, m ? s.nm.data() : nullptr);
+        } else if (s.window > 0)
           s.status = orbfe_extract_batch_collect_matched(ext[e], s.kps.data(), s.desc.data(), cap, s.n.data(), s.m12.data(),
                                                          s.nm.data());
         else
@@ -221,7 +237,7 @@ struct orbfe_stream {
       }
       if (s.status == ORBFE_OK) {
         s.prevN = isolated ? -1 : lastN;
-        if (s.prevN >= 0) { s.prevKps = lastKps; s.prevDesc = lastDesc; }
+        if (s.prevN >= 0) { s.prevKps = lastKps; s.prevDesc = lastDesc; if (s.camera) s.prevXyUn = lastXyUn; }
         if (s.window <= 0) {   // extraction only: no matches
           std::fill(s.nm.begin(), s.nm.end(), 0);
           std::fill(s.m12.begin(), s.m12.end(), -1);
@@ -232,6 +248,7 @@ struct orbfe_stream {
         lastN = s.n[batch - 1];
         lastKps.assign(s.kps.begin() + (size_t)(batch - 1) * cap, s.kps.begin() + (size_t)(batch - 1) * cap + lastN);
         lastDesc.assign(s.desc.begin() + (size_t)(batch - 1) * cap * 32, s.desc.begin() + ((size_t)(batch - 1) * cap + lastN) * 32);
+        if (s.camera) lastXyUn.assign(s.xyUn.begin() + (size_t)(batch - 1) * cap * 2, s.xyUn.begin() + ((size_t)(batch - 1) * cap + lastN) * 2);
       }
       {
         std::lock_guard<std::mutex> lk(mu);   // matches (if any) came back with the batch: done
@@ -371,6 +388,32 @@ int orbfe_stream_set_blur_variant(orbfe_stream* s, int variant) {
   return ORBFE_OK;
 }
 
+// The camera of every handle of the runner.  The frame pushed next has no predecessor: the one the runner holds was undistorted
+// (or not) by the camera before.
+int orbfe_stream_set_camera(orbfe_stream* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist) {
+  if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
+  for (orbfe_extractor* e : s->ext) {
+    const int rc = orbfe_extractor_set_camera(e, camera_mode, fx, fy, cx, cy, dist, ndist);   // (a refused model is refused by the first handle)
+    if (rc) return rc;
+  }
+  s->camera = true;
+  s->lastN = -1;
+  s->chainRows = s->chainCols = 0;
+  return orbfe_sfi_chain_restart(s->chain);
+}
+
+int orbfe_stream_xy_un(orbfe_stream* s, const float** xy_un) {
+  if (!s || !xy_un) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  if (s->popped < 0 || !s->slots[s->popped].camera || s->slots[s->popped].xyUn.empty()) {
+    set_err("no popped batch with undistorted keypoints (orbfe_stream_set_camera)");
+    return ORBFE_ERR_INVALID;
+  }
+  *xy_un = s->slots[s->popped].xyUn.data();
+  return ORBFE_OK;
+}
+
 int orbfe_stream_set_vocabulary(orbfe_stream* s, orbfe_vocabulary* v, int levelsup) {
   if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
@@ -406,6 +449,12 @@ int orbfe_stream_grow_capacity(orbfe_stream* s, int need) {
   if (!s) { set_err("stream is NULL"); return ORBFE_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(s->mu);
   return s->growCap(need, 0, 0);
+}
+// (orbfe_stream_multi.cpp, not in the header) mvKeysUn of a result held by orbfe_stream_pop_hold; nullptr: pushed without a camera
+const float* orbfe_stream_held_xy_un(orbfe_stream* s, int ticket) {
+  if (!s || ticket < 0 || ticket >= (int)s->slots.size()) return nullptr;
+  const Slot& sl = s->slots[(size_t)ticket];
+  return sl.held && sl.camera && !sl.xyUn.empty() ? sl.xyUn.data() : nullptr;
 }
 int orbfe_stream_batches_in_flight(const orbfe_stream* s) { return s ? s->inFlight : 0; }
 
@@ -445,6 +494,7 @@ int orbfe_stream_push(orbfe_stream* s, const uint8_t* const* gray, int in_device
   {
     std::lock_guard<std::mutex> lk(s->mu);
     sl.window = s->window; sl.checkOri = s->checkOri; sl.nnratio = s->nnratio;
+    sl.camera = s->camera;
     memcpy(sl.bounds, s->bounds, sizeof sl.bounds);
     sl.seq = s->pushSeq++;
     s->extractQ.push_back(slot);

@@ -29,6 +29,7 @@ void set_err(const char* fmt, ...);
 using orbfe::set_err;
 extern "C" int orbfe_stream_capacity_for(const orbfe_stream* s, int rows, int cols);   // orbfe_stream.cpp
 extern "C" int orbfe_stream_grow_capacity(orbfe_stream* s, int need);
+extern "C" const float* orbfe_stream_held_xy_un(orbfe_stream* s, int ticket);
 
 struct orbfe_stream_multi {
   int ndev = 0, batch = 0;
@@ -46,6 +47,7 @@ struct orbfe_stream_multi {
   int window = 100, checkOri = 1;
   float nnratio = 0.9f;
   float bounds[4] = {0, 0, 0, 0};
+  long long noPredSeq = -1;   // orbfe_stream_multi_set_camera: this batch's first frame has no predecessor (it saw another camera)
 
   // what finisher d hands to the consumer (valid from publish(seq) until the consumer lets go of seq)
   struct Done {
@@ -54,6 +56,7 @@ struct orbfe_stream_multi {
     const int* n = nullptr;
     const int32_t* m12 = nullptr;
     const int* nm = nullptr;
+    const float* xyUn = nullptr;   // mvKeysUn [batch][stride][2] when the runners have a camera
     int status = ORBFE_OK;
     int ticket = -1;            // orbfe_stream_pop_hold's: the consumer releases the result slot when it lets go of the batch
     std::string err;
@@ -67,6 +70,7 @@ struct orbfe_stream_multi {
   struct Tail {
     std::vector<OrbfeKeyPoint> kps;
     std::vector<uint8_t> desc;
+    std::vector<float> xyUn;   // the last frame's mvKeysUn (empty without a camera)
     int n = -1;
     long long seq = -1;
   };
@@ -77,21 +81,25 @@ struct orbfe_stream_multi {
   void finish(int d) {
     std::vector<float> prevxy;
     std::vector<int32_t> row;
+    std::vector<OrbfeKeyPoint> cur;
     Tail prev;
     for (long long k = d;; k += ndev) {
       int window_k, checkOri_k;
       float nnratio_k, bounds_k[4];
+      bool noPred_k;
       {
         std::unique_lock<std::mutex> lk(mu);
         cv.wait(lk, [&] { return stop || pushSeq > k; });
         if (pushSeq <= k) return;   // stopped with nothing of ours outstanding
         window_k = window; checkOri_k = checkOri; nnratio_k = nnratio;
         memcpy(bounds_k, bounds, sizeof bounds_k);
+        noPred_k = k == noPredSeq;
       }
       Done r;
       // (held, not "valid until the next pop": this thread goes on to the device's next batch while the consumer still reads this one)
       r.status = orbfe_stream_pop_hold(sub[d], &r.kps, &r.desc, &r.n, &r.m12, &r.nm, &r.ticket);
       if (r.status != ORBFE_OK) r.err = orbfe_last_error();
+      else r.xyUn = orbfe_stream_held_xy_un(sub[d], r.ticket);
       const int stride = orbfe_stream_capacity(sub[d]);   // keypoint slots per frame of the result arrays (grows only while the runner is idle)
       const bool matching = window_k > 0;
       // 1. the next batch's predecessor, before anything else: its finisher may be waiting for it.  Two generations per device: this one
@@ -107,6 +115,8 @@ struct orbfe_stream_multi {
           const int last = batch - 1, ln = r.n[last];
           t.kps.assign(r.kps + (size_t)last * stride, r.kps + (size_t)last * stride + ln);
           t.desc.assign(r.desc + (size_t)last * stride * 32, r.desc + ((size_t)last * stride + ln) * 32);
+          t.xyUn.clear();
+          if (r.xyUn) t.xyUn.assign(r.xyUn + (size_t)last * stride * 2, r.xyUn + ((size_t)last * stride + ln) * 2);
           t.n = ln;
         }
         t.seq = k;
@@ -122,7 +132,7 @@ struct orbfe_stream_multi {
           tailRead[(size_t)((k - 1) % ndev)] = k - 1;
         }
         cv.notify_all();
-        if (matching && r.status == ORBFE_OK && prev.n >= 0) {
+        if (matching && r.status == ORBFE_OK && prev.n >= 0 && !noPred_k && (r.xyUn != nullptr) == (prev.n == 0 || !prev.xyUn.empty())) {
           // the runner owns the slot memory behind the pointers orbfe_stream_pop_hold returned: row 0 of the match vectors is written in place
           int32_t* m12 = const_cast<int32_t*>(r.m12);
           int* nm = const_cast<int*>(r.nm);
@@ -130,7 +140,14 @@ struct orbfe_stream_multi {
           for (int j = 0; j < prev.n; j++) { prevxy[2 * j] = prev.kps[j].x; prevxy[2 * j + 1] = prev.kps[j].y; }   // vbPrevMatched := F1's keypoints (Tracking.cc:355-357)
           row.assign((size_t)(prev.n > 0 ? prev.n : 1), -1);
           int nmatch = 0;
-          const int rc = orbfe_search_for_initialization(matcher[d], prev.kps.data(), prev.desc.data(), prev.n, r.kps, r.desc, r.n[0], bounds_k,
+          const OrbfeKeyPoint* k2 = r.kps;
+          if (r.xyUn) {   // both frames on mvKeysUn, vbPrevMatched := F1's mvKeysUn (what the runners' chains search on)
+            cur.assign(r.kps, r.kps + r.n[0]);
+            for (int j = 0; j < r.n[0]; j++) { cur[(size_t)j].x = r.xyUn[2 * j]; cur[(size_t)j].y = r.xyUn[2 * j + 1]; }
+            for (int j = 0; j < prev.n; j++) { prev.kps[(size_t)j].x = prevxy[2 * j] = prev.xyUn[2 * (size_t)j]; prev.kps[(size_t)j].y = prevxy[2 * j + 1] = prev.xyUn[2 * (size_t)j + 1]; }
+            k2 = cur.data();
+          }
+          const int rc = orbfe_search_for_initialization(matcher[d], prev.kps.data(), prev.desc.data(), prev.n, k2, r.desc, r.n[0], bounds_k,
                                                          prevxy.data(), row.data(), window_k, nnratio_k, checkOri_k, &nmatch);
           if (rc != ORBFE_OK) {
             r.status = rc;
@@ -272,6 +289,39 @@ int orbfe_stream_multi_set_blur_variant(orbfe_stream_multi* s, int variant) {
     const int rc = orbfe_stream_set_blur_variant(q, variant);
     if (rc != ORBFE_OK) return rc;
   }
+  return ORBFE_OK;
+}
+
+// The camera of every runner (orbfe_stream_set_camera), only while no batch is in flight.  The batch pushed next starts without a
+// predecessor, as on the single-device runner.
+int orbfe_stream_multi_set_camera(orbfe_stream_multi* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist,
+                                  int ndist) {
+  if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  long long next;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+    next = s->pushSeq;
+  }
+  release_held_batch(s);
+  for (auto* q : s->sub) {
+    int rc = orbfe_stream_set_camera(q, camera_mode, fx, fy, cx, cy, dist, ndist);   // (a refused model is refused by the first runner)
+    if (rc == ORBFE_OK) rc = orbfe_stream_set_isolated_batches(q, 1);
+    if (rc != ORBFE_OK) return rc;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  s->noPredSeq = next;
+  return ORBFE_OK;
+}
+
+// mvKeysUn of the batch the caller holds (the last popped one): [batch][orbfe_stream_multi_capacity][2]
+int orbfe_stream_multi_xy_un(orbfe_stream_multi* s, const float** xy_un) {
+  if (!s || !xy_un) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  if (s->heldSeq < 0 || !s->doneOf(s->heldSeq).xyUn) {
+    set_err("no popped batch with undistorted keypoints (orbfe_stream_multi_set_camera)");
+    return ORBFE_ERR_INVALID;
+  }
+  *xy_un = s->doneOf(s->heldSeq).xyUn;
   return ORBFE_OK;
 }
 
