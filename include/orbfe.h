@@ -754,6 +754,52 @@ int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_fram
                                           const float* inv_level_sigma2, double chi2, int max_dist, uint8_t* valid, float* uv,
                                           int32_t* level, int32_t* best_idx, int32_t* best_dist, int* nmatches, int* n_valid);
 
+/* void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:227-292) and void MapPoint::UpdateNormalAndDepth()
+ * (:315-356) for a batch of MapPoints, from the RESIDENT keyframes straight into the table's rows: the producer of everything
+ * the projections above read.  MapPoint p, p < n_mp, is row rows[p]; its observations are entries [obs_offsets[p],
+ * obs_offsets[p+1]) of obs_kf / obs_kp / obs_flags in std::map<KeyFrame*,size_t> order: obs_kf = slot of the observing keyframe
+ * in kf_frames / kf_Ow (kf_Ow[3*s..] = its GetCameraCenter()), obs_kp = the keypoint index there, obs_flags (NULL: all 0) carries
+ * ORBFE_OBS_KF_BAD where pKF->isBad().  `what` selects the function(s):
+ *   ORBFE_REFRESH_DESCRIPTOR    the descriptor rows of the observations WITHOUT the bad bit are gathered from the keyframes'
+ *                               resident descriptors; the one with the least median distance to the others (median = sorted[
+ *                               (size_t)(0.5*(N-1)) ], first minimum wins) goes into the row.  An empty list leaves the row's
+ *                               descriptor as it is.
+ *   ORBFE_REFRESH_NORMAL_DEPTH  over ALL observations (bad keyframes included, as the reference): normal = mean of
+ *                               (pos - Ow)/|pos - Ow|; mfMaxDistance = |pos - Ow_ref| * scale_factors[level], level = octave of
+ *                               keypoint ref_kp[p] of the resident keyframe in slot ref_kf[p] (pRefKF, observations[pRefKF]);
+ *                               mfMinDistance = mfMaxDistance / scale_factors[nlevels-1].  pos is read from the row (never
+ *                               written).  A MapPoint without observations keeps its row (its ref_kf / ref_kp are not read).
+ *                               The float chain is restated operation for operation (cv::norm in double, cv::scaleAdd with the
+ *                               product rounded before the sum, convertTo's `+ 0`); INTEGRATION.md section 6 names what an
+ *                               OpenCV built with fused multiply-add would change.
+ * Optional host outputs (NULL: not returned), one entry per MapPoint: best_obs = index of the chosen descriptor's observation
+ * inside the MapPoint's own list as passed (bad entries counted), -1 where nothing was chosen or DESCRIPTOR is not selected;
+ * normal [3*n_mp], min_raw, max_raw = those fields of the row as they stand after the call.
+ * A kf_frames[s] may be NULL if every observation naming slot s carries ORBFE_OBS_KF_BAD and no MapPoint uses it as ref_kf: only
+ * its Ow is read.  The call runs on the matcher's stream, after earlier orbfe_local_map_set_rows and before the next search; the
+ * keyframes' builds are waited for on the stream.  It returns when the requested host outputs are written; with all four NULL
+ * it returns once enqueued (8 bytes per observation went up, nothing comes down) -- unless a keyframe holds an octave >=
+ * nlevels, in which case it waits for the kernel's level report (below).  n_mp == 0: ORBFE_OK.
+ * ORBFE_ERR_INVALID before anything is sent: a row outside [0, capacity) or named twice; obs_offsets not non-decreasing; a slot
+ * outside [0, n_kf); a keypoint index outside its frame's size; a NULL frame named by a non-bad observation or as ref_kf; a frame
+ * on another device; nlevels outside 1..32; a list of more non-bad observations than the LDS budget holds (150 KB / 32 bytes, as
+ * orbfe_distinctive_descriptors).
+ * LEVEL CONTRACT: a MapPoint whose reference keypoint's octave lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID;
+ * the kernel finds it before anything is indexed with that level and leaves that MapPoint's row unwritten (the other rows
+ * of the batch are written, the host outputs are not); the matcher, frames and table stay usable. */
+#define ORBFE_OBS_KF_BAD 1u              /* pKF->isBad(): not in the descriptor list; still in the normal */
+#define ORBFE_REFRESH_DESCRIPTOR   1     /* ComputeDistinctiveDescriptors */
+#define ORBFE_REFRESH_NORMAL_DEPTH 2     /* UpdateNormalAndDepth */
+int orbfe_local_map_refresh_rows(orbfe_matcher* m, orbfe_local_map* map, int what,
+      int n_kf, orbfe_frame* const* kf_frames, const float* kf_Ow /* 3*n_kf */,
+      const float* scale_factors, int nlevels,
+      int n_mp, const int32_t* rows, const int32_t* obs_offsets /* n_mp+1 */,
+      const int32_t* obs_kf /* slot into kf_frames */, const int32_t* obs_kp, const uint8_t* obs_flags,
+      const int32_t* ref_kf, const int32_t* ref_kp,          /* per MapPoint; NORMAL_DEPTH only */
+      int32_t* best_obs, float* normal, float* min_raw, float* max_raw /* optional host outputs */);
+/* test / debug: rows of the table back on the host, 64 bytes each (waits for the matcher's stream first) */
+int orbfe_local_map_download_rows(orbfe_local_map* map, int n, const int32_t* rows, uint8_t* out);
+
 /* Rounds the bookkeeping kernel of the last `_frame` search needed -- the most any chunk of 2 048 consecutive queries took
  * (negative: a chunk hit the bound ORBFE_RESOLVE_MAX_ROUNDS, default 48, and a serial pass on the device finished it). */
 int orbfe_debug_resolve_rounds(const orbfe_matcher* m);

@@ -208,6 +208,8 @@ def load_library():
     L.orbfe_local_map_destroy.restype = None
     L.orbfe_local_map_capacity.argtypes = [vp]
     L.orbfe_local_map_set_rows.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_local_map_refresh_rows.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci] + [vp] * 11
+    L.orbfe_local_map_download_rows.argtypes = [vp, ci, vp, vp]
     L.orbfe_project_local_map.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_search_local_points_frame.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, ci, vp, cf, cf, vp, vp, vp, vp, vp,
                                                   C.POINTER(ci), C.POINTER(ci)]
@@ -525,6 +527,8 @@ class KeyFrameProjection(C.Structure):
 
 
 MP_IN_VIEW, MP_BAD, MP_CANDIDATO, MP_OBSERVED, MP_SKIP = 1, 2, 4, 8, 16
+OBS_KF_BAD = 1
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
 SRC_LAST_FRAME, SRC_KEYFRAME = 0, 1
 
 
@@ -556,6 +560,45 @@ class LocalMap:
         _check(self.L.orbfe_local_map_set_rows(self.h, n, _p(rows), arg(pos, np.float32, (n, 3)), arg(normal, np.float32, (n, 3)),
                                                arg(min_raw, np.float32, (n,)), arg(max_raw, np.float32, (n,)),
                                                arg(desc, np.uint8, (n, 32))))
+
+    def refresh_rows(self, what, kf_frames, kf_Ow, rows, obs_offsets, obs_kf, obs_kp, obs_flags=None, ref_kf=None, ref_kp=None,
+                     scale_factors=None, nlevels=None, outputs=True):
+        """orbfe_local_map_refresh_rows: MapPoint::ComputeDistinctiveDescriptors (REFRESH_DESCRIPTOR) and / or
+        UpdateNormalAndDepth (REFRESH_NORMAL_DEPTH) for the MapPoints in rows `rows`, from the resident keyframes `kf_frames`
+        (api.Frame or None per slot) into the table.  Observations of MapPoint p: entries obs_offsets[p]..obs_offsets[p+1] of
+        obs_kf (slot), obs_kp (keypoint), obs_flags (OBS_KF_BAD).  outputs=True returns (best_obs, normal [n, 3], min_raw,
+        max_raw) as the rows hold them after the call; outputs=False only enqueues the work and returns None."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        n = len(rows)
+        offs = np.ascontiguousarray(obs_offsets, np.int32)
+        okf = np.ascontiguousarray(obs_kf, np.int32)
+        okp = np.ascontiguousarray(obs_kp, np.int32)
+        ofl = None if obs_flags is None else np.ascontiguousarray(obs_flags, np.uint8)
+        rkf = None if ref_kf is None else np.ascontiguousarray(ref_kf, np.int32)
+        rkp = None if ref_kp is None else np.ascontiguousarray(ref_kp, np.int32)
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)
+        if nlevels is None:
+            nlevels = 1 if sf is None else len(sf)
+        Ow = np.ascontiguousarray(kf_Ow, np.float32).reshape(-1, 3)
+        handles = (C.c_void_p * max(len(kf_frames), 1))(*[None if f is None else f.h for f in kf_frames])
+        best = np.zeros(max(n, 1), np.int32)
+        nrm = np.zeros((max(n, 1), 3), np.float32)
+        mn, mx = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        outs = [_p(best), _p(nrm), _p(mn), _p(mx)] if outputs else [None] * 4
+
+        def q(a):
+            return None if a is None else _p(a)
+        _check(self.L.orbfe_local_map_refresh_rows(self.matcher.h, self.h, int(what), len(kf_frames), C.cast(handles, C.c_void_p), _p(Ow),
+                                                   q(sf), int(nlevels), n, _p(rows), _p(offs), _p(okf), _p(okp), q(ofl), q(rkf),
+                                                   q(rkp), *outs))
+        return (best[:n], nrm[:n], mn[:n], mx[:n]) if outputs else None
+
+    def download_rows(self, rows):
+        """Test / debug: the 64-byte rows `rows` of the table as a uint8 array [n, 64]."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        out = np.zeros((max(len(rows), 1), 64), np.uint8)
+        _check(self.L.orbfe_local_map_download_rows(self.h, len(rows), _p(rows), _p(out)))
+        return out[:len(rows)]
 
     def close(self):
         if getattr(self, 'h', None):

@@ -1510,6 +1510,8 @@ void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** an
 void frame_xy(const orbfe_frame* f, const float** x, const float** y) {
   *x = f->D.x; *y = f->D.y;
 }
+// the descriptor rows in keypoint order, without waiting (the gather of orbfe_mprefresh.hip orders itself with frame_wait_ready)
+const uint8_t* frame_descriptor_rows(const orbfe_frame* f) { return f->D.desc; }
 void frame_wait_ready(orbfe_frame* f, hipStream_t st) {
   if (f->ready && hipStreamWaitEvent(st, f->ready, 0) != hipSuccess) (void)hipGetLastError();   // (the recording stream is gone: the build is complete)
 }

@@ -431,6 +431,7 @@ struct orbfe_local_map {
   PinBuf<uint8_t> io;              // per call: copies of ordinary rows / flags arrays, outputs, per-block summary
   DevBuf<uint8_t> q;               // fused call: the search's queries
   std::vector<uint8_t> seen;       // set_rows duplicate check
+  std::shared_ptr<void> refresh;   // scratch of orbfe_local_map_refresh_rows (orbfe_mprefresh.hip); released after the body below
   ~orbfe_local_map() {
     (void)hipSetDevice(m->device);
     if (staged) { (void)hipEventSynchronize(staged); (void)hipEventDestroy(staged); }
@@ -438,6 +439,19 @@ struct orbfe_local_map {
     (void)hipGetLastError();
   }
 };
+
+namespace orbfe {
+// what orbfe_mprefresh.hip needs of a table: its matcher, size, rows, and the slot of its own scratch
+struct LocalMapView {
+  orbfe_matcher* m;
+  int capacity;
+  uint8_t* table;
+  std::shared_ptr<void>* scratch;
+};
+void local_map_view(orbfe_local_map* map, LocalMapView* v) {
+  v->m = map->m; v->capacity = map->capacity; v->table = map->table.p; v->scratch = &map->refresh;
+}
+}  // namespace orbfe
 
 namespace {
 
