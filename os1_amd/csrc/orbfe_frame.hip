@@ -23,11 +23,6 @@
 #include <atomic>
 #include "orbfe_internal.h"
 
-struct orbfe_extractor;
-namespace orbfe {
-int extractor_view(orbfe_extractor* h, int frame, ExtractView* out);
-}
-
 namespace {
 
 constexpr int kCells = kGridCols * kGridRows;   // 3072
@@ -682,9 +677,10 @@ struct RawQ {
   int where[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
-// > 0: the kernels can read p in place (1: page-locked host memory, 2: memory of device `device`); 0: ordinary host memory
-// (the caller copies it into the arena); -1: memory of another device
-int gpu_readable(const void* p, int device) {
+}  // namespace
+
+// the library's one pointer classifier (declared in orbfe_matcher_internal.h)
+int orbfe::gpu_readable(const void* p, int device) {
   hipPointerAttribute_t attr;
   if (p && hipPointerGetAttributes(&attr, p) == hipSuccess) {
     if (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged) return 1;
@@ -694,6 +690,9 @@ int gpu_readable(const void* p, int device) {
   (void)hipGetLastError();
   return 0;
 }
+
+namespace {
+
 // The per-query arrays other than the descriptor rows, and the occupancy bytes, are also READ BY THE HOST (level range,
 // largest radius, the marshalled routes): they must be host memory -- page-locked (then the kernels read them in place) or
 // ordinary.  A device pointer is refused here, before anything dereferences it (include/orbfe.h states the contract).
@@ -992,6 +991,106 @@ int scratch_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps, const uint8_t* des
   return rc;
 }
 
+// ---- What the host-array form of a search and its device-query twin (the fused calls of orbfe_localmap.hip) share, per kind:
+// the result initialisation, the arena plan with the kind's raw queries, and the submission with the result copy.  The device
+// form differs in where the queries live (queries_on_device) and in its window bound (the largest of ALL scale factors: the
+// host reads no level).
+
+// kp_assigned[n] = -1, no match; true: nothing to search
+bool nothing_to_assign(const orbfe_frame* f, int nq, int32_t* kp_assigned, int* nmatches) {
+  *nmatches = 0;
+  for (int i = 0; i < f->n; i++) kp_assigned[i] = -1;
+  return nq == 0 || f->n == 0;
+}
+// best_idx[nq] = best_dist[nq] = -1, no match; true: nothing to search
+bool nothing_to_project(const orbfe_frame* f, int nq, int32_t* best_idx, int32_t* best_dist, int* nmatches) {
+  *nmatches = 0;
+  for (int i = 0; i < nq; i++) {
+    best_idx[i] = -1;
+    if (best_dist) best_dist[i] = -1;
+  }
+  return nq == 0 || f->n == 0;
+}
+
+// kind 1, SearchByProjection(F, MapPoints, th): the arena and the raw queries.  *rmaxRaw: the widest window per unit scale factor
+int mappoint_queries(orbfe_matcher* m, const orbfe_frame* f, double tEntry, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                     const float* xy, const int32_t* level, const float* viewcos, const uint8_t* flags, int n_mp, float th, SearchPlan* P,
+                     RawQ* Q, float* rmaxRaw) {
+  m->tEntry = tEntry;
+  const int rc = plan_search(m, f, kModeMapPoints, n_mp, true, 0, P);
+  if (rc) return rc;
+  const bool bFactor = th != 1.0;
+  Q->kind = 1; Q->xy = xy; Q->level = level; Q->aux = viewcos; Q->flags = flags;
+  Q->claimSrc = flags; Q->claimMask = ORBFE_MP_OBSERVED;
+  Q->occ = kp_occupied; Q->sf = scale_factors; Q->nlevels = nlevels; Q->th = th; Q->factor = bFactor ? 1 : 0;
+  *rmaxRaw = 4.0f;
+  if (bFactor) *rmaxRaw *= th;
+  return ORBFE_OK;
+}
+// kind 2, SearchByProjection(F, LastFrame / KeyFrame) from the projection on
+int uv_queries(orbfe_matcher* m, const orbfe_frame* f, double tEntry, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+               const float* xy, const int32_t* level, const float* angle, const uint8_t* valid, const uint8_t* claim, int n_src, float th,
+               SearchPlan* P, RawQ* Q) {
+  m->tEntry = tEntry;
+  const int rc = plan_search(m, f, kModeUv, n_src, true, 0, P);
+  if (rc) return rc;
+  Q->kind = 2; Q->xy = xy; Q->level = level; Q->flags = valid; Q->angle = angle;
+  Q->claimSrc = claim; Q->claimMask = ORBFE_MP_OBSERVED;
+  Q->occ = kp_occupied; Q->sf = scale_factors; Q->nlevels = nlevels; Q->th = th;
+  return ORBFE_OK;
+}
+// (kind 2, skip_any_occupied: every source claims; the claim bytes are not read)
+void claim_always(RawQ* Q) { Q->claimSrc = nullptr; Q->claimMask = 0xff; Q->claimConst = 1; }
+// kind 3, the projected loops (radius given); the chi-square gate's table travels in the arena
+int projected_queries(orbfe_matcher* m, const orbfe_frame* f, double tEntry, const float* xy, const int32_t* level, const float* radius,
+                      const uint8_t* valid, int n_src, const uint8_t* kp_skip, int claim, const float* inv_level_sigma2, int nlevels,
+                      SearchPlan* P, RawQ* Q) {
+  if (inv_level_sigma2 && f->maxOctave >= nlevels) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
+  m->tEntry = tEntry;
+  const int rc = plan_search(m, f, kModeProjected, n_src, kp_skip != nullptr, inv_level_sigma2 ? nlevels : 0, P);
+  if (rc) return rc;
+  Q->kind = 3; Q->xy = xy; Q->level = level; Q->aux = radius; Q->flags = valid;
+  Q->claimConst = claim ? 1 : 0;
+  Q->occ = kp_skip;
+  return ORBFE_OK;
+}
+// the device form: every per-query array and the descriptor row indices are in the frame's device memory already; only the
+// occupancy / skip bytes (`what`) are a host array
+int queries_on_device(const orbfe_matcher* m, RawQ* Q, const int32_t* d_desc_row, const char* what) {
+  Q->descRow = d_desc_row; Q->descRowWhere = 2;
+  Q->device = true;
+  for (int k = 0; k < 6; k++) Q->where[k] = 2;
+  Q->where[6] = Q->occ ? gpu_readable(Q->occ, m->device) : 0;
+  if (Q->where[6] == 2) { set_err("the %s bytes must be host memory", what); return ORBFE_ERR_INVALID; }
+  return ORBFE_OK;
+}
+float largest_scale_factor(const float* scale_factors, int nlevels) {
+  float maxSf = 0.f;
+  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
+  return maxSf;
+}
+
+// submit and copy the result out.  raw == nullptr: the marshalled route
+int search_assigned(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const RawQ* raw, const uint8_t* desc, float rmax, float nnratio,
+                    int maxDist, int checkOri, int32_t* kp_assigned, int* nmatches) {
+  const int* out = nullptr;
+  const int rc = run_search(m, f, P, desc, rmax, nnratio, maxDist, 0.0, checkOri, &out, nmatches, raw);
+  if (rc) return rc;
+  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)f->n);
+  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
+  return ORBFE_OK;
+}
+int search_best(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const RawQ* raw, const uint8_t* desc, float rmax, const float* inv_level_sigma2,
+                int nlevels, double chi2, int maxDist, int32_t* best_idx, int32_t* best_dist, int* nmatches) {
+  if (inv_level_sigma2) memcpy(P.invSigma2, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
+  const int* out = nullptr;
+  const int rc = run_search(m, f, P, desc, rmax, 0.f, maxDist, chi2, 0, &out, nmatches, raw);
+  if (rc) return rc;
+  memcpy(best_idx, out, sizeof(int32_t) * (size_t)P.nq);
+  if (best_dist) memcpy(best_dist, out + P.nq, sizeof(int32_t) * (size_t)P.nq);
+  return ORBFE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1125,33 +1224,21 @@ static int sbp_frame_impl(orbfe_matcher* m, orbfe_frame* f, const float* scale_f
     return sbp_frame_impl(m, f, scale_factors, nlevels, kp_occupied, mp_proj_xy, mp_level, mp_viewcos, mp_flags, rows.data(), nullptr,
                           nullptr, n_mp, th, nnratio, kp_assigned, nmatches);
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_mp == 0 || n == 0) return ORBFE_OK;
-  m->tEntry = tEntry;
+  if (nothing_to_assign(f, n_mp, kp_assigned, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeMapPoints, n_mp, true, 0, &P);
-  if (rc) return rc;
-  const bool bFactor = th != 1.0;
-  const int* out = nullptr;
   RawQ Q;
-  Q.kind = 1; Q.xy = mp_proj_xy; Q.level = mp_level; Q.aux = mp_viewcos; Q.flags = mp_flags;
-  Q.claimSrc = mp_flags; Q.claimMask = ORBFE_MP_OBSERVED;
-  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th; Q.factor = bFactor ? 1 : 0;
+  float rmaxRaw;
+  int rc = mappoint_queries(m, f, tEntry, scale_factors, nlevels, kp_occupied, mp_proj_xy, mp_level, mp_viewcos, mp_flags, n_mp, th, &P, &Q, &rmaxRaw);
+  if (rc) return rc;
   Q.descRow = mp_desc_row; Q.descHost = desc_host;
   if ((rc = classify_host_arrays(m, &Q))) return rc;
   if (frame_zero_copy() && nlevels <= 32) {   // no loop over the MapPoints here: the window kernel reads the caller's arrays
     float maxSf = 0.f;
     if ((rc = check_levels(mp_level, mp_flags, ORBFE_MP_IN_VIEW | ORBFE_MP_BAD, ORBFE_MP_IN_VIEW, n_mp, scale_factors, nlevels, &maxSf, "MapPoint")))
       return rc;
-    float rmaxRaw = 4.0f;
-    if (bFactor) rmaxRaw *= th;
-    if ((rc = run_search(m, f, P, mp_desc, rmaxRaw * maxSf, nnratio, TH_HIGH, 0.0, 0, &out, nmatches, &Q))) return rc;
-    memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-    m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-    return ORBFE_OK;
+    return search_assigned(m, f, P, &Q, mp_desc, rmaxRaw * maxSf, nnratio, TH_HIGH, 0, kp_assigned, nmatches);
   }
+  const bool bFactor = Q.factor != 0;
   float rmax = 0.f;
   for (int i = 0; i < n_mp; i++) {
     const uint8_t fl = mp_flags[i];
@@ -1169,11 +1256,8 @@ static int sbp_frame_impl(orbfe_matcher* m, orbfe_frame* f, const float* scale_f
     P.qr[i] = r * scale_factors[lvl];
     rmax = std::max(rmax, P.qr[i]);
   }
-  memcpy(P.occ0, kp_occupied, (size_t)n);
-  if ((rc = run_search(m, f, P, mp_desc, rmax, nnratio, TH_HIGH, 0.0, 0, &out, nmatches))) return rc;
-  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-  return ORBFE_OK;
+  memcpy(P.occ0, kp_occupied, (size_t)f->n);
+  return search_assigned(m, f, P, nullptr, mp_desc, rmax, nnratio, TH_HIGH, 0, kp_assigned, nmatches);
 }
 
 int orbfe_search_by_projection_frame(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels,
@@ -1219,28 +1303,17 @@ int orbfe_search_by_projection_uv_frame(orbfe_matcher* m, orbfe_frame* f, const 
     set_err("bad argument");
     return ORBFE_ERR_INVALID;
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_src == 0 || n == 0) return ORBFE_OK;
-  m->tEntry = tEntry;
+  if (nothing_to_assign(f, n_src, kp_assigned, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeUv, n_src, true, 0, &P);
-  if (rc) return rc;
-  const int* out = nullptr;
   RawQ Q;
-  Q.kind = 2; Q.xy = src_uv; Q.level = src_level; Q.flags = src_valid; Q.angle = src_angle;
-  Q.claimSrc = src_flags; Q.claimMask = ORBFE_MP_OBSERVED;
-  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th;
+  int rc = uv_queries(m, f, tEntry, scale_factors, nlevels, kp_occupied, src_uv, src_level, src_angle, src_valid, src_flags, n_src, th, &P, &Q);
+  if (rc) return rc;
   if ((rc = classify_host_arrays(m, &Q))) return rc;
-  if (skip_any_occupied) { Q.claimSrc = nullptr; Q.claimMask = 0xff; Q.claimConst = 1; }
+  if (skip_any_occupied) claim_always(&Q);
   if (frame_zero_copy() && nlevels <= 32) {
     float maxSf = 0.f;
     if ((rc = check_levels(src_level, src_valid, 0, 0, n_src, scale_factors, nlevels, &maxSf, "source"))) return rc;
-    if ((rc = run_search(m, f, P, src_desc, th * maxSf, 0.f, max_dist, 0.0, check_orientation, &out, nmatches, &Q))) return rc;
-    memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-    m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-    return ORBFE_OK;
+    return search_assigned(m, f, P, &Q, src_desc, th * maxSf, 0.f, max_dist, check_orientation, kp_assigned, nmatches);
   }
   float rmax = 0.f;
   for (int i = 0; i < n_src; i++) {
@@ -1256,11 +1329,8 @@ int orbfe_search_by_projection_uv_frame(orbfe_matcher* m, orbfe_frame* f, const 
     P.qr[i] = th * scale_factors[lvl];
     rmax = std::max(rmax, P.qr[i]);
   }
-  memcpy(P.occ0, kp_occupied, (size_t)n);
-  if ((rc = run_search(m, f, P, src_desc, rmax, 0.f, max_dist, 0.0, check_orientation, &out, nmatches))) return rc;
-  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-  return ORBFE_OK;
+  memcpy(P.occ0, kp_occupied, (size_t)f->n);
+  return search_assigned(m, f, P, nullptr, src_desc, rmax, 0.f, max_dist, check_orientation, kp_assigned, nmatches);
 }
 
 // the projected best-match loop of SearchByProjection(KeyFrame*, Scw, ...), Fuse x2 and SearchBySim3
@@ -1276,32 +1346,16 @@ int orbfe_search_projected_frame(orbfe_matcher* m, orbfe_frame* f, int n_src, co
     set_err("bad argument");
     return ORBFE_ERR_INVALID;
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n_src; i++) {
-    best_idx[i] = -1;
-    if (best_dist) best_dist[i] = -1;
-  }
-  if (n_src == 0 || n == 0) return ORBFE_OK;
-  if (inv_level_sigma2 && f->maxOctave >= nlevels) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
-  m->tEntry = tEntry;
+  if (nothing_to_project(f, n_src, best_idx, best_dist, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeProjected, n_src, kp_skip != nullptr, inv_level_sigma2 ? nlevels : 0, &P);
-  if (rc) return rc;
-  const int* out = nullptr;
   RawQ Q;
-  Q.kind = 3; Q.xy = src_uv; Q.level = src_level; Q.aux = src_radius; Q.flags = src_valid;
-  Q.claimConst = claim ? 1 : 0;
-  Q.occ = kp_skip;
+  int rc = projected_queries(m, f, tEntry, src_uv, src_level, src_radius, src_valid, n_src, kp_skip, claim, inv_level_sigma2, nlevels, &P, &Q);
+  if (rc) return rc;
   if ((rc = classify_host_arrays(m, &Q))) return rc;
   if (frame_zero_copy()) {
     float rmaxRaw = 0.f;
     for (int i = 0; i < n_src; i++) rmaxRaw = std::max(rmaxRaw, src_radius[i]);   // (of all sources: an upper bound)
-    if (inv_level_sigma2) memcpy(P.invSigma2, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
-    if ((rc = run_search(m, f, P, src_desc, rmaxRaw, 0.f, max_dist, chi2, 0, &out, nmatches, &Q))) return rc;
-    memcpy(best_idx, out, sizeof(int32_t) * (size_t)n_src);
-    if (best_dist) memcpy(best_dist, out + n_src, sizeof(int32_t) * (size_t)n_src);
-    return ORBFE_OK;
+    return search_best(m, f, P, &Q, src_desc, rmaxRaw, inv_level_sigma2, nlevels, chi2, max_dist, best_idx, best_dist, nmatches);
   }
   float rmax = 0.f;
   for (int i = 0; i < n_src; i++) {
@@ -1314,12 +1368,8 @@ int orbfe_search_projected_frame(orbfe_matcher* m, orbfe_frame* f, int n_src, co
     P.qr[i] = (src_valid[i] && src_level[i] >= 0) ? src_radius[i] : -1.f;   // no octave lies in [level-1, level] for level < 0
     rmax = std::max(rmax, P.qr[i]);
   }
-  if (kp_skip) memcpy(P.occ0, kp_skip, (size_t)n);
-  if (inv_level_sigma2) memcpy(P.invSigma2, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
-  if ((rc = run_search(m, f, P, src_desc, rmax, 0.f, max_dist, chi2, 0, &out, nmatches))) return rc;
-  memcpy(best_idx, out, sizeof(int32_t) * (size_t)n_src);
-  if (best_dist) memcpy(best_dist, out + n_src, sizeof(int32_t) * (size_t)n_src);
-  return ORBFE_OK;
+  if (kp_skip) memcpy(P.occ0, kp_skip, (size_t)f->n);
+  return search_best(m, f, P, nullptr, src_desc, rmax, inv_level_sigma2, nlevels, chi2, max_dist, best_idx, best_dist, nmatches);
 }
 
 }  // extern "C"
@@ -1377,33 +1427,14 @@ int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scal
     set_err("bad argument");
     return ORBFE_ERR_INVALID;
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_mp == 0 || n == 0) return ORBFE_OK;
-  if (gpu_readable(kp_occupied, m->device) == 2) { set_err("the occupancy bytes must be host memory"); return ORBFE_ERR_INVALID; }
-  m->tEntry = tEntry;
+  if (nothing_to_assign(f, n_mp, kp_assigned, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeMapPoints, n_mp, true, 0, &P);
-  if (rc) return rc;
-  const bool bFactor = th != 1.0;
   RawQ Q;
-  Q.kind = 1; Q.xy = d_xy; Q.level = d_level; Q.aux = d_viewcos; Q.flags = d_flags;
-  Q.claimSrc = d_flags; Q.claimMask = ORBFE_MP_OBSERVED;
-  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th; Q.factor = bFactor ? 1 : 0;
-  Q.descRow = d_desc_row; Q.descRowWhere = 2;
-  Q.device = true;
-  for (int k = 0; k < 5; k++) Q.where[k] = 2;
-  Q.where[6] = gpu_readable(kp_occupied, m->device);
-  float maxSf = 0.f;
-  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
-  float rmaxRaw = 4.0f;
-  if (bFactor) rmaxRaw *= th;
-  const int* out = nullptr;
-  if ((rc = run_search(m, f, P, d_desc, rmaxRaw * maxSf, nnratio, TH_HIGH, 0.0, 0, &out, nmatches, &Q))) return rc;
-  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-  return ORBFE_OK;
+  float rmaxRaw;
+  int rc = mappoint_queries(m, f, tEntry, scale_factors, nlevels, kp_occupied, d_xy, d_level, d_viewcos, d_flags, n_mp, th, &P, &Q, &rmaxRaw);
+  if (rc) return rc;
+  if ((rc = queries_on_device(m, &Q, d_desc_row, "occupancy"))) return rc;
+  return search_assigned(m, f, P, &Q, d_desc, rmaxRaw * largest_scale_factor(scale_factors, nlevels), nnratio, TH_HIGH, 0, kp_assigned, nmatches);
 }
 }  // namespace orbfe
 
@@ -1426,31 +1457,15 @@ int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* s
     set_err("bad argument");
     return ORBFE_ERR_INVALID;
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n; i++) kp_assigned[i] = -1;
-  if (n_src == 0 || n == 0) return ORBFE_OK;
-  if (gpu_readable(kp_occupied, m->device) == 2) { set_err("the occupancy bytes must be host memory"); return ORBFE_ERR_INVALID; }
-  m->tEntry = tEntry;
+  if (nothing_to_assign(f, n_src, kp_assigned, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeUv, n_src, true, 0, &P);
-  if (rc) return rc;
   RawQ Q;
-  Q.kind = 2; Q.xy = d_xy; Q.level = d_level; Q.flags = d_valid; Q.angle = d_angle;
-  Q.claimSrc = d_claim; Q.claimMask = ORBFE_MP_OBSERVED;
-  if (skip_any_occupied) { Q.claimSrc = nullptr; Q.claimMask = 0xff; Q.claimConst = 1; }
-  Q.occ = kp_occupied; Q.sf = scale_factors; Q.nlevels = nlevels; Q.th = th;
-  Q.descRow = d_desc_row; Q.descRowWhere = 2;
-  Q.device = true;
-  for (int k = 0; k < 6; k++) Q.where[k] = 2;
-  Q.where[6] = gpu_readable(kp_occupied, m->device);
-  float maxSf = 0.f;
-  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
-  const int* out = nullptr;
-  if ((rc = run_search(m, f, P, d_desc, th * maxSf, 0.f, max_dist, 0.0, check_orientation, &out, nmatches, &Q))) return rc;
-  memcpy(kp_assigned, out, sizeof(int32_t) * (size_t)n);
-  m->stageMs[2] = orbfe_matcher::nowMs() - m->tSynced;
-  return ORBFE_OK;
+  int rc = uv_queries(m, f, tEntry, scale_factors, nlevels, kp_occupied, d_xy, d_level, d_angle, d_valid, d_claim, n_src, th, &P, &Q);
+  if (rc) return rc;
+  if (skip_any_occupied) claim_always(&Q);
+  if ((rc = queries_on_device(m, &Q, d_desc_row, "occupancy"))) return rc;
+  return search_assigned(m, f, P, &Q, d_desc, th * largest_scale_factor(scale_factors, nlevels), 0.f, max_dist, check_orientation, kp_assigned,
+                         nmatches);
 }
 
 // The projected best-match loop (orbfe_search_projected_frame's search) on sources that are already in device memory
@@ -1470,35 +1485,14 @@ int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, cons
     set_err("bad argument");
     return ORBFE_ERR_INVALID;
   }
-  const int n = f->n;
-  *nmatches = 0;
-  for (int i = 0; i < n_src; i++) {
-    best_idx[i] = -1;
-    if (best_dist) best_dist[i] = -1;
-  }
-  if (n_src == 0 || n == 0) return ORBFE_OK;
-  if (inv_level_sigma2 && f->maxOctave >= nlevels) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
-  if (kp_skip && gpu_readable(kp_skip, m->device) == 2) { set_err("the skip bytes must be host memory"); return ORBFE_ERR_INVALID; }
-  m->tEntry = tEntry;
+  if (nothing_to_project(f, n_src, best_idx, best_dist, nmatches)) return ORBFE_OK;
   SearchPlan P;
-  int rc = plan_search(m, f, kModeProjected, n_src, kp_skip != nullptr, inv_level_sigma2 ? nlevels : 0, &P);
-  if (rc) return rc;
   RawQ Q;
-  Q.kind = 3; Q.xy = d_xy; Q.level = d_level; Q.aux = d_radius; Q.flags = d_valid;
-  Q.claimConst = claim ? 1 : 0;
-  Q.occ = kp_skip;
-  Q.descRow = d_desc_row; Q.descRowWhere = 2;
-  Q.device = true;
-  for (int k = 0; k < 4; k++) Q.where[k] = 2;
-  Q.where[6] = kp_skip ? gpu_readable(kp_skip, m->device) : 0;
-  float maxSf = 0.f;
-  for (int l = 0; l < nlevels; l++) maxSf = std::max(maxSf, scale_factors[l]);
-  if (inv_level_sigma2) memcpy(P.invSigma2, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
-  const int* out = nullptr;
-  if ((rc = run_search(m, f, P, d_desc, th * maxSf, 0.f, max_dist, chi2, 0, &out, nmatches, &Q))) return rc;
-  memcpy(best_idx, out, sizeof(int32_t) * (size_t)n_src);
-  if (best_dist) memcpy(best_dist, out + n_src, sizeof(int32_t) * (size_t)n_src);
-  return ORBFE_OK;
+  int rc = projected_queries(m, f, tEntry, d_xy, d_level, d_radius, d_valid, n_src, kp_skip, claim, inv_level_sigma2, nlevels, &P, &Q);
+  if (rc) return rc;
+  if ((rc = queries_on_device(m, &Q, d_desc_row, "skip"))) return rc;
+  return search_best(m, f, P, &Q, d_desc, th * largest_scale_factor(scale_factors, nlevels), inv_level_sigma2, nlevels, chi2, max_dist, best_idx,
+                     best_dist, nmatches);
 }
 
 // what the projection of a SOURCE frame's keypoints reads of its resident copy (k_project_sources): octaves and angles in

@@ -14,11 +14,6 @@
 // `currentScore > score` is false for it.
 #include "orbfe_matcher_internal.h"
 
-namespace orbfe {
-void frame_xy(const orbfe_frame* f, const float** x, const float** y);
-void frame_wait_ready(orbfe_frame* f, hipStream_t st);
-}  // namespace orbfe
-
 namespace {
 
 constexpr int kThreads = 256;

@@ -10,34 +10,18 @@
 // its results in device memory where the resident frame's window search (orbfe_frame.hip) reads them: one submission of
 // three kernels on the matcher's stream, no copy command in between.
 //
-// The arithmetic is the reference's cv::Mat float arithmetic as the oracle pins it (oracle/orb_oracle.cpp cvGemm3, cvNorm3,
-// cvDot3, predictScale; include/orbfe/orb_shim.hpp RestatedOps): Rcw*P+tcw is a float dot in source order with a double
-// epilogue, cv::norm and Mat::dot accumulate in double, and PredictScale's log is glibc logf (glibc_logf.h).  The library is
-// built with -ffp-contract=off, so every float operation rounds on its own as in the reference.
+// One projection core, three kernels.  The arithmetic is the reference's cv::Mat float arithmetic as the oracle pins it
+// (oracle/orb_oracle.cpp cvGemm3, cvNorm3, cvDot3, predictScale; include/orbfe/orb_shim.hpp RestatedOps), and every piece of
+// it is stated ONCE below: load_row, transform3 (Rcw*P+tcw as cv::gemm computes it), norm3 and dot3 (cv::norm, Mat::dot: double
+// accumulation), distance_in_range (the 0.8f / 1.2f invariance), predict_level (PredictScale: glibc logf, glibc_logf.h).  So is
+// the framing every kernel shares: ProjCommon, block_begin, write_common (host outputs, the search's common query fields, the
+// level rule) and block_summary.  A kernel keeps what is its own: the culling order of its reference loop, its bounds test,
+// its 1/z, its extra outputs.  The library is built with -ffp-contract=off, so every float operation rounds on its own as in
+// the reference; the order of operations and the operand types of these expressions are the correctness contract of this file.
 #include "orbfe_matcher_internal.h"
 #include "glibc_logf.h"
 
 #include <atomic>
-
-struct orbfe_frame;
-namespace orbfe {
-void frame_bounds(const orbfe_frame* f, float out[4]);
-int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
-                             const float* d_xy, const int32_t* d_level, const float* d_viewcos, const uint8_t* d_flags,
-                             const uint8_t* d_desc, const int32_t* d_desc_row, int n_mp, float th, float nnratio,
-                             int32_t* kp_assigned, int* nmatches);
-int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
-                                const float* d_xy, const int32_t* d_level, const float* d_angle, const uint8_t* d_valid,
-                                const uint8_t* d_claim, const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, float th,
-                                int max_dist, int skip_any_occupied, int check_orientation, int32_t* kp_assigned, int* nmatches);
-int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, float th,
-                                          const float* d_xy, const int32_t* d_level, const float* d_radius, const uint8_t* d_valid,
-                                          const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, const uint8_t* kp_skip, int claim,
-                                          const float* inv_level_sigma2, double chi2, int max_dist, int32_t* best_idx, int32_t* best_dist,
-                                          int* nmatches);
-void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
-void frame_wait_ready(orbfe_frame* f, hipStream_t st);
-}  // namespace orbfe
 
 namespace {
 
@@ -66,132 +50,164 @@ __global__ __launch_bounds__(256) void k_local_map_scatter(const uint8_t* __rest
     d4[1] = s4[1];
   }
 }
+// ---- the projection core ---------------------------------------------------------------------------------------------
+struct Row {
+  float pos[3];      // GetWorldPos()
+  float normal[3];   // GetNormal()
+  float minRaw, maxRaw;   // mfMinDistance, mfMaxDistance
+};
+__device__ __forceinline__ Row load_row(const uint8_t* __restrict__ table, int row) {
+  const float4* R = reinterpret_cast<const float4*>(table + (size_t)row * kRowBytes);
+  const float4 a = R[0], b = R[1];
+  return Row{{a.x, a.y, a.z}, {a.w, b.x, b.y}, b.z, b.w};
+}
+// out = R*P+t as cv::gemm computes it: float dot in source order, double epilogue (alpha = beta = 1).  out must not alias P.
+__device__ __forceinline__ void transform3(const float R[9], const float t[3], const float P[3], float out[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float d = R[3 * k] * P[0] + R[3 * k + 1] * P[1] + R[3 * k + 2] * P[2];
+    out[k] = (float)((double)d * 1.0 + (double)t[k] * 1.0);
+  }
+}
+// (float)cv::norm(v): double accumulation in index order
+__device__ __forceinline__ float norm3(const float v[3]) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
+  return (float)sqrt(s);
+}
+// a.dot(b): double accumulation in index order; the caller rounds or compares
+__device__ __forceinline__ double dot3(const float a[3], const float b[3]) {
+  double d = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) d += (double)a[k] * (double)b[k];
+  return d;
+}
+// !(dist < GetMinDistanceInvariance() || dist > GetMaxDistanceInvariance())  (MapPoint.cc:358-368)
+__device__ __forceinline__ bool distance_in_range(float dist, float minRaw, float maxRaw) {
+  const float maxDistance = 1.2f * maxRaw;
+  const float minDistance = 0.8f * minRaw;
+  return !(dist < minDistance || dist > maxDistance);
+}
+// PredictScale (MapPoint.cc:370-379): ceil(log(ratio)/logScaleFactor) with float ratio, converted to int as the host does (an
+// out-of-range value becomes INT_MIN)
+__device__ __forceinline__ int predict_level(float maxRaw, float dist, float logScaleFactor) {
+  const float ratio = maxRaw / dist;
+  const float c = ceilf(orbfe::logf_glibc(ratio) / logScaleFactor);
+  return (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+}
 
-struct ProjParams {
+// what the three kernels' parameter blocks have in common
+struct ProjCommon {
   const uint8_t* table;
   const int32_t* rows;         // [n] (page-locked host memory)
   const uint8_t* flags;        // [n]
   int n;
-  OrbfeCamera cam;
-  float minX, maxX, minY, maxY;
-  float cosLimit;
+  float minX, maxX, minY, maxY;   // bounds of the frame projected INTO
   int nlevels;                 // fused call: levels outside [0, nlevels) are taken out of the search and reported
   // outputs in page-locked host memory (any may be null)
-  uint8_t* inView;
+  uint8_t* valid;
   float* xy;
   int32_t* level;
-  float* vcos;
   // fused call: the search's queries in device memory (null: projection only)
   float* dxy;
   int32_t* dlevel;
-  float* dvcos;
-  uint8_t* dflags;
   int32_t* drow;
-  int* blockInfo;              // [2 * blocks] page-locked: MapPoints in view, first MapPoint with an out-of-range level (-1)
+  int* blockInfo;              // [2 * blocks] page-locked: items valid, first valid item with an out-of-range level (-1)
+};
+
+// Every lane of the block calls block_begin and block_summary (lanes with i >= n too): both hold a barrier.
+__device__ __forceinline__ void block_begin(int* firstBad) {
+  if (threadIdx.x == 0) *firstBad = INT_MAX;
+  __syncthreads();
+}
+// Item i after the kernel's own tests: the common host outputs and the search's common query fields (an item that is not
+// valid is written as zeros).  Returns whether the search may use the item: a level outside [0, nlevels) is never handed to
+// it (the call fails instead, naming the first such item).
+__device__ __forceinline__ bool write_common(const ProjCommon& P, int i, bool valid, float u, float v, int lvl, int row, int* firstBad) {
+  if (!valid) { u = 0.f; v = 0.f; lvl = 0; }
+  if (P.valid) P.valid[i] = valid ? 1 : 0;
+  if (P.xy) { P.xy[2 * i] = u; P.xy[2 * i + 1] = v; }
+  if (P.level) P.level[i] = lvl;
+  const bool levelOk = lvl >= 0 && lvl < P.nlevels;
+  if (P.dxy) {
+    if (valid && !levelOk) atomicMin(firstBad, i);
+    reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
+    P.dlevel[i] = levelOk ? lvl : 0;
+    P.drow[i] = valid ? 2 * row : 0;      // descriptor = 32-byte row 2*row of (table + 32)
+  }
+  return valid && levelOk;
+}
+__device__ __forceinline__ void block_summary(const ProjCommon& P, bool valid, const int* firstBad) {
+  const int count = __syncthreads_count(valid ? 1 : 0);
+  if (threadIdx.x == 0) {
+    P.blockInfo[2 * blockIdx.x] = count;
+    P.blockInfo[2 * blockIdx.x + 1] = *firstBad == INT_MAX ? -1 : *firstBad;
+    __threadfence_system();
+  }
+}
+
+struct ProjParams {
+  ProjCommon c;
+  OrbfeCamera cam;
+  float cosLimit;
+  float* vcos;                 // page-locked host output (may be null)
+  float* dvcos;                // fused call
+  uint8_t* dflags;
 };
 
 // bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit)  (src/Frame.cc:151-207), one lane per listed MapPoint
 __global__ __launch_bounds__(kProjThreads) void k_project_local_map(ProjParams P) {
   __shared__ int firstBad;
-  if (threadIdx.x == 0) firstBad = INT_MAX;
-  __syncthreads();
+  block_begin(&firstBad);
   const int i = blockIdx.x * kProjThreads + threadIdx.x;
   bool inView = false;
-  float u = 0.f, v = 0.f, viewCos = 0.f;
-  int lvl = 0, row = 0;
-  unsigned fl = 0;
-  if (i < P.n) {
-    fl = P.flags[i];
-    row = P.rows[i];
+  if (i < P.c.n) {
+    float u = 0.f, v = 0.f, viewCos = 0.f;
+    int lvl = 0;
+    const unsigned fl = P.c.flags[i];
+    const int row = P.c.rows[i];
     // Tracking.cc:804-807: mnLastFrameSeen == mCurrentFrame.mnId, isBad()
     if (!(fl & (ORBFE_MP_BAD | ORBFE_MP_SKIP))) {
-      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
-      const float4 a = R[0], b = R[1];
-      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
-      const float Pn[3] = {a.w, b.x, b.y};                  // GetNormal()
-      const float minRaw = b.z, maxRaw = b.w;               // mfMinDistance, mfMaxDistance
+      const Row r = load_row(P.c.table, row);
       const OrbfeCamera& C = P.cam;
-      // Pc = mRcw*P+mtcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
       float Pc[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const float t = C.Rcw[3 * k] * Pw[0] + C.Rcw[3 * k + 1] * Pw[1] + C.Rcw[3 * k + 2] * Pw[2];
-        Pc[k] = (float)((double)t * 1.0 + (double)C.tcw[k] * 1.0);
-      }
+      transform3(C.Rcw, C.tcw, r.pos, Pc);                  // Pc = mRcw*P+mtcw
       if (!(Pc[2] < 0.0f)) {                                // Frame.cc:166-167
         const float invz = 1.0f / Pc[2];
         u = C.fx * Pc[0] * invz + C.cx;
         v = C.fy * Pc[1] * invz + C.cy;
-        if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {   // Frame.cc:173-176
-          const float maxDistance = 1.2f * maxRaw;          // GetMaxDistanceInvariance (MapPoint.cc:364-368)
-          const float minDistance = 0.8f * minRaw;          // GetMinDistanceInvariance (MapPoint.cc:358-362)
-          const float PO[3] = {Pw[0] - C.Ow[0], Pw[1] - C.Ow[1], Pw[2] - C.Ow[2]};
-          double s = 0.0;                                   // cv::norm(PO)
-#pragma unroll
-          for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
-          const float dist = (float)sqrt(s);
-          if (!(dist < minDistance || dist > maxDistance)) {
-            double d = 0.0;                                 // PO.dot(Pn)
-#pragma unroll
-            for (int k = 0; k < 3; k++) d += (double)PO[k] * (double)Pn[k];
-            viewCos = (float)(d / (double)dist);
+        if (!(u < P.c.minX || u > P.c.maxX) && !(v < P.c.minY || v > P.c.maxY)) {   // Frame.cc:173-176
+          const float PO[3] = {r.pos[0] - C.Ow[0], r.pos[1] - C.Ow[1], r.pos[2] - C.Ow[2]};
+          const float dist = norm3(PO);
+          if (distance_in_range(dist, r.minRaw, r.maxRaw)) {   // Frame.cc:179-186
+            viewCos = (float)(dot3(PO, r.normal) / (double)dist);   // PO.dot(Pn)/dist
             if (!(viewCos < P.cosLimit)) {
-              // PredictScale (MapPoint.cc:370-379): ceil(log(ratio)/logScaleFactor) with float ratio, converted to int as
-              // the host does (an out-of-range value becomes INT_MIN)
-              const float ratio = maxRaw / dist;
-              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
-              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+              lvl = predict_level(r.maxRaw, dist, C.logScaleFactor);
               inView = true;
             }
           }
         }
       }
     }
-    if (!inView) { u = 0.f; v = 0.f; viewCos = 0.f; lvl = 0; }
-    if (P.inView) P.inView[i] = inView ? 1 : 0;
-    if (P.xy) { P.xy[2 * i] = u; P.xy[2 * i + 1] = v; }
-    if (P.level) P.level[i] = lvl;
+    if (!inView) viewCos = 0.f;
+    const bool searched = write_common(P.c, i, inView, u, v, lvl, row, &firstBad);
     if (P.vcos) P.vcos[i] = viewCos;
-    if (P.dxy) {
-      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
-      const bool levelOk = lvl >= 0 && lvl < P.nlevels;
-      if (inView && !levelOk) atomicMin(&firstBad, i);
-      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
-      P.dlevel[i] = levelOk ? lvl : 0;
+    if (P.c.dxy) {
       P.dvcos[i] = viewCos;
-      P.dflags[i] = (uint8_t)((inView && levelOk ? ORBFE_MP_IN_VIEW : 0u) | (fl & (ORBFE_MP_CANDIDATO | ORBFE_MP_OBSERVED)));
-      P.drow[i] = inView ? 2 * row : 0;   // descriptor = 32-byte row 2*row of (table + 32)
+      P.dflags[i] = (uint8_t)((searched ? ORBFE_MP_IN_VIEW : 0u) | (fl & (ORBFE_MP_CANDIDATO | ORBFE_MP_OBSERVED)));
     }
   }
-  const int count = __syncthreads_count(inView ? 1 : 0);
-  if (threadIdx.x == 0) {
-    P.blockInfo[2 * blockIdx.x] = count;
-    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
-    __threadfence_system();
-  }
+  block_summary(P.c, inView, &firstBad);
 }
 
 struct SrcParams {
-  const uint8_t* table;
-  const int32_t* rows;         // [n] (page-locked host memory)
-  const uint8_t* flags;        // [n]
+  ProjCommon c;                // (bounds: the CURRENT frame's)
   const int* srcOct;           // [n] the SOURCE frame's resident octaves (mvKeys[i].octave)
-  int n;
   int mode;                    // ORBFE_SRC_LAST_FRAME / ORBFE_SRC_KEYFRAME
   OrbfeCamera cam;
-  float minX, maxX, minY, maxY;   // the CURRENT frame's bounds
-  int nlevels;                 // fused call: levels outside [0, nlevels) are taken out of the search and reported
-  // outputs in page-locked host memory (any may be null)
-  uint8_t* valid;
-  float* uv;
-  int32_t* level;
-  // fused call: the search's queries in device memory (null: projection only)
-  float* dxy;
-  int32_t* dlevel;
-  uint8_t* dvalid;
+  uint8_t* dvalid;             // fused call
   uint8_t* dclaim;
-  int32_t* drow;
-  int* blockInfo;              // [2 * blocks] page-locked: sources valid, first valid source with an out-of-range level (-1)
 };
 
 // The projection loops of ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th)
@@ -200,48 +216,30 @@ struct SrcParams {
 // check, :1386 / :1515) is not touched here: the search reads it from the source frame's resident copy.
 __global__ __launch_bounds__(kProjThreads) void k_project_sources(SrcParams P) {
   __shared__ int firstBad;
-  if (threadIdx.x == 0) firstBad = INT_MAX;
-  __syncthreads();
+  block_begin(&firstBad);
   const int i = blockIdx.x * kProjThreads + threadIdx.x;
   bool valid = false;
-  float u = 0.f, v = 0.f;
-  int lvl = 0, row = 0;
-  unsigned fl = 0;
-  if (i < P.n) {
-    fl = P.flags[i];
-    row = P.rows[i];
+  if (i < P.c.n) {
+    float u = 0.f, v = 0.f;
+    int lvl = 0;
+    const unsigned fl = P.c.flags[i];
+    const int row = P.c.rows[i];
     // :1318-1321 no MapPoint / mvbOutlier[i] (isBad() is not asked); :1445-1447 no MapPoint / isBad() / in sAlreadyFound
     if (!(fl & (P.mode == ORBFE_SRC_KEYFRAME ? (ORBFE_MP_BAD | ORBFE_MP_SKIP) : ORBFE_MP_SKIP))) {
-      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
-      const float4 a = R[0], b = R[1];
-      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
-      const float maxRaw = b.w, minRaw = b.z;               // mfMaxDistance, mfMinDistance
+      const Row r = load_row(P.c.table, row);
       const OrbfeCamera& C = P.cam;
-      // x3Dc = Rcw*x3Dw+tcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
       float Pc[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const float t = C.Rcw[3 * k] * Pw[0] + C.Rcw[3 * k + 1] * Pw[1] + C.Rcw[3 * k + 2] * Pw[2];
-        Pc[k] = (float)((double)t * 1.0 + (double)C.tcw[k] * 1.0);
-      }
+      transform3(C.Rcw, C.tcw, r.pos, Pc);                  // x3Dc = Rcw*x3Dw+tcw
       const float invzc = (float)(1.0 / (double)Pc[2]);     // :1329 / :1455: a DOUBLE division, rounded to float
       if (P.mode == ORBFE_SRC_KEYFRAME || !(invzc < 0)) {   // :1332-1333 (the KeyFrame form has no such test)
         u = C.fx * Pc[0] * invzc + C.cx;
         v = C.fy * Pc[1] * invzc + C.cy;
-        if (!(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {   // :1339-1342 / :1460-1463
+        if (!(u < P.c.minX || u > P.c.maxX) && !(v < P.c.minY || v > P.c.maxY)) {   // :1339-1342 / :1460-1463
           if (P.mode == ORBFE_SRC_KEYFRAME) {
-            const float PO[3] = {Pw[0] - C.Ow[0], Pw[1] - C.Ow[1], Pw[2] - C.Ow[2]};   // :1466
-            double s = 0.0;                                 // cv::norm(PO)
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
-            const float dist3D = (float)sqrt(s);
-            const float maxDistance = 1.2f * maxRaw;        // GetMaxDistanceInvariance (MapPoint.cc:364-368)
-            const float minDistance = 0.8f * minRaw;        // GetMinDistanceInvariance (MapPoint.cc:358-362)
-            if (!(dist3D < minDistance || dist3D > maxDistance)) {   // :1473-1474
-              // PredictScale (MapPoint.cc:370-379), converted to int as the host does (an out-of-range value becomes INT_MIN)
-              const float ratio = maxRaw / dist3D;
-              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
-              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+            const float PO[3] = {r.pos[0] - C.Ow[0], r.pos[1] - C.Ow[1], r.pos[2] - C.Ow[2]};   // :1466
+            const float dist3D = norm3(PO);
+            if (distance_in_range(dist3D, r.minRaw, r.maxRaw)) {   // :1473-1474
+              lvl = predict_level(r.maxRaw, dist3D, C.logScaleFactor);
               valid = true;
             }
           } else {
@@ -255,51 +253,23 @@ __global__ __launch_bounds__(kProjThreads) void k_project_sources(SrcParams P) {
         }
       }
     }
-    if (!valid) { u = 0.f; v = 0.f; lvl = 0; }
-    if (P.valid) P.valid[i] = valid ? 1 : 0;
-    if (P.uv) { P.uv[2 * i] = u; P.uv[2 * i + 1] = v; }
-    if (P.level) P.level[i] = lvl;
-    if (P.dxy) {
-      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
-      const bool levelOk = lvl >= 0 && lvl < P.nlevels;
-      if (valid && !levelOk) atomicMin(&firstBad, i);
-      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
-      P.dlevel[i] = levelOk ? lvl : 0;
-      P.dvalid[i] = valid && levelOk ? 1 : 0;
+    const bool searched = write_common(P.c, i, valid, u, v, lvl, row, &firstBad);
+    if (P.c.dxy) {
+      P.dvalid[i] = searched ? 1 : 0;
       P.dclaim[i] = (uint8_t)(fl & ORBFE_MP_OBSERVED);
-      P.drow[i] = valid ? 2 * row : 0;    // descriptor = 32-byte row 2*row of (table + 32)
     }
   }
-  const int count = __syncthreads_count(valid ? 1 : 0);
-  if (threadIdx.x == 0) {
-    P.blockInfo[2 * blockIdx.x] = count;
-    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
-    __threadfence_system();
-  }
+  block_summary(P.c, valid, &firstBad);
 }
 
 struct KfParams {
-  const uint8_t* table;
-  const int32_t* rows;         // [n] (page-locked host memory)
-  const uint8_t* flags;        // [n]
-  int n;
+  ProjCommon c;                // (bounds: the TARGET keyframe's; nlevels is set in both call forms: the radius reads it)
   OrbfeKeyFrameProjection proj;
-  float minX, maxX, minY, maxY;   // the TARGET keyframe's bounds
-  int nlevels;
   float th;
   float sf[32];                // the target keyframe's mvScaleFactors
-  // outputs in page-locked host memory (any may be null)
-  uint8_t* valid;
-  float* uv;
-  int32_t* level;
-  float* radius;
-  // fused call: the search's queries in device memory (null: projection only)
-  float* dxy;
-  int32_t* dlevel;
-  float* dradius;
+  float* radius;               // page-locked host output (may be null)
+  float* dradius;              // fused call
   uint8_t* dvalid;
-  int32_t* drow;
-  int* blockInfo;              // [2 * blocks] page-locked: points valid, first valid point with an out-of-range level (-1)
 };
 
 // The projection loops of the keyframe-side searches, one lane per listed MapPoint: everything between GetWorldPos() and
@@ -309,36 +279,22 @@ struct KfParams {
 // the three switches of OrbfeKeyFrameProjection.
 __global__ __launch_bounds__(kProjThreads) void k_project_keyframe(KfParams P) {
   __shared__ int firstBad;
-  if (threadIdx.x == 0) firstBad = INT_MAX;
-  __syncthreads();
+  block_begin(&firstBad);
   const int i = blockIdx.x * kProjThreads + threadIdx.x;
   bool valid = false;
-  float u = 0.f, v = 0.f, radius = 0.f;
-  int lvl = 0, row = 0;
-  if (i < P.n) {
-    const unsigned fl = P.flags[i];
-    row = P.rows[i];
+  if (i < P.c.n) {
+    float u = 0.f, v = 0.f, radius = 0.f;
+    int lvl = 0;
+    const unsigned fl = P.c.flags[i];
+    const int row = P.c.rows[i];
     if (!(fl & (ORBFE_MP_BAD | ORBFE_MP_SKIP))) {          // isBad() / spAlreadyFound, IsInKeyFrame, vbAlreadyMatched, no MapPoint
-      const float4* R = reinterpret_cast<const float4*>(P.table + (size_t)row * kRowBytes);
-      const float4 a = R[0], b = R[1];
-      const float Pw[3] = {a.x, a.y, a.z};                  // GetWorldPos()
-      const float Pn[3] = {a.w, b.x, b.y};                  // GetNormal()
-      const float minRaw = b.z, maxRaw = b.w;               // mfMinDistance, mfMaxDistance
+      const Row r = load_row(P.c.table, row);
       const OrbfeKeyFrameProjection& C = P.proj;
-      // p3Dc = Rcw*p3Dw+tcw: gemm, float dot in source order, double epilogue (alpha = beta = 1)
       float p[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const float t = C.R[3 * k] * Pw[0] + C.R[3 * k + 1] * Pw[1] + C.R[3 * k + 2] * Pw[2];
-        p[k] = (float)((double)t * 1.0 + (double)C.t[k] * 1.0);
-      }
+      transform3(C.R, C.t, r.pos, p);                       // p3Dc = Rcw*p3Dw+tcw
       if (C.has_second) {                                   // p3Dc2 = sR21*p3Dc1+t21 (:1124) / p3Dc1 = sR12*p3Dc2+t12 (:1204)
         float q[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const float t = C.sR[3 * k] * p[0] + C.sR[3 * k + 1] * p[1] + C.sR[3 * k + 2] * p[2];
-          q[k] = (float)((double)t * 1.0 + (double)C.t2[k] * 1.0);
-        }
+        transform3(C.sR, C.t2, p, q);
         p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
       }
       if (!(p[2] < 0.0f)) {                                 // depth must be positive
@@ -349,75 +305,35 @@ __global__ __launch_bounds__(kProjThreads) void k_project_keyframe(KfParams P) {
         u = C.fx * x + C.cx;
         v = C.fy * y + C.cy;
         // KeyFrame::IsInImage (src/KeyFrame.cc:678-681), half-open; a NaN or infinite u, v (z = +-0) fails it by itself
-        if (u >= P.minX && u < P.maxX && v >= P.minY && v < P.maxY) {
-          const float maxDistance = 1.2f * maxRaw;          // GetMaxDistanceInvariance (MapPoint.cc:364-368)
-          const float minDistance = 0.8f * minRaw;          // GetMinDistanceInvariance (MapPoint.cc:358-362)
+        if (u >= P.c.minX && u < P.c.maxX && v >= P.c.minY && v < P.c.maxY) {
           float PO[3];
           if (C.distance_from_camera_point) { PO[0] = p[0]; PO[1] = p[1]; PO[2] = p[2]; }   // cv::norm(p3Dc2) (:1143, :1223)
-          else { PO[0] = Pw[0] - C.Ow[0]; PO[1] = Pw[1] - C.Ow[1]; PO[2] = Pw[2] - C.Ow[2]; }   // PO = p3Dw-Ow
-          double s = 0.0;                                   // cv::norm(PO)
-#pragma unroll
-          for (int k = 0; k < 3; k++) s += (double)PO[k] * (double)PO[k];
-          const float dist3D = (float)sqrt(s);
-          if (!(dist3D < minDistance || dist3D > maxDistance)) {
-            bool angleOk = true;
-            if (C.check_viewing_angle) {                    // PO.dot(Pn)<0.5*dist (:349, :865, :1006)
-              double d = 0.0;
-#pragma unroll
-              for (int k = 0; k < 3; k++) d += (double)PO[k] * (double)Pn[k];
-              angleOk = !(d < 0.5 * (double)dist3D);
-            }
-            if (angleOk) {
-              // PredictScale (MapPoint.cc:370-379), converted to int as the host does (an out-of-range value becomes INT_MIN)
-              const float ratio = maxRaw / dist3D;
-              const float c = ceilf(orbfe::logf_glibc(ratio) / C.logScaleFactor);
-              lvl = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+          else { PO[0] = r.pos[0] - C.Ow[0]; PO[1] = r.pos[1] - C.Ow[1]; PO[2] = r.pos[2] - C.Ow[2]; }   // PO = p3Dw-Ow
+          const float dist3D = norm3(PO);
+          if (distance_in_range(dist3D, r.minRaw, r.maxRaw)) {
+            // PO.dot(Pn)<0.5*dist (:349, :865, :1006)
+            if (!C.check_viewing_angle || !(dot3(PO, r.normal) < 0.5 * (double)dist3D)) {
+              lvl = predict_level(r.maxRaw, dist3D, C.logScaleFactor);
               valid = true;
             }
           }
         }
       }
     }
-    const bool levelOk = lvl >= 0 && lvl < P.nlevels;
-    if (!valid) { u = 0.f; v = 0.f; lvl = 0; }
-    else if (levelOk) radius = P.th * P.sf[lvl];            // th*pKF->mvScaleFactors[nPredictedLevel]
-    if (P.valid) P.valid[i] = valid ? 1 : 0;
-    if (P.uv) { P.uv[2 * i] = u; P.uv[2 * i + 1] = v; }
-    if (P.level) P.level[i] = lvl;
+    const bool searched = write_common(P.c, i, valid, u, v, lvl, row, &firstBad);
+    if (searched) radius = P.th * P.sf[lvl];                // th*pKF->mvScaleFactors[nPredictedLevel]
     if (P.radius) P.radius[i] = radius;
-    if (P.dxy) {
-      // the search reads these: a level outside [0, nlevels) is never handed to it (the call fails instead)
-      if (valid && !levelOk) atomicMin(&firstBad, i);
-      reinterpret_cast<float2*>(P.dxy)[i] = make_float2(u, v);
-      P.dlevel[i] = valid && levelOk ? lvl : 0;
+    if (P.c.dxy) {
       P.dradius[i] = radius;
-      P.dvalid[i] = valid && levelOk ? 1 : 0;
-      P.drow[i] = valid ? 2 * row : 0;    // descriptor = 32-byte row 2*row of (table + 32)
+      P.dvalid[i] = searched ? 1 : 0;
     }
   }
-  const int count = __syncthreads_count(valid ? 1 : 0);
-  if (threadIdx.x == 0) {
-    P.blockInfo[2 * blockIdx.x] = count;
-    P.blockInfo[2 * blockIdx.x + 1] = firstBad == INT_MAX ? -1 : firstBad;
-    __threadfence_system();
-  }
+  block_summary(P.c, valid, &firstBad);
 }
 
 __global__ void k_debug_logf(const float* __restrict__ x, int n, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = orbfe::logf_glibc(x[i]);
-}
-
-// > 0: page-locked host memory (read by the kernel in place); 0: ordinary host memory; -1: device memory
-int host_readable(const void* p) {
-  hipPointerAttribute_t attr;
-  if (p && hipPointerGetAttributes(&attr, p) == hipSuccess) {
-    if (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged) return 1;
-    if (attr.type == hipMemoryTypeDevice) return -1;
-    return 0;
-  }
-  (void)hipGetLastError();
-  return 0;
 }
 
 }  // namespace
@@ -439,15 +355,7 @@ struct orbfe_local_map {
     (void)hipGetLastError();
   }
 };
-
 namespace orbfe {
-// what orbfe_mprefresh.hip needs of a table: its matcher, size, rows, and the slot of its own scratch
-struct LocalMapView {
-  orbfe_matcher* m;
-  int capacity;
-  uint8_t* table;
-  std::shared_ptr<void>* scratch;
-};
 void local_map_view(orbfe_local_map* map, LocalMapView* v) {
   v->m = map->m; v->capacity = map->capacity; v->table = map->table.p; v->scratch = &map->refresh;
 }
@@ -466,7 +374,7 @@ struct CallArea {
   int blocks;
 };
 
-// checks shared by both calls; carves the page-locked area (caller's rows / flags read in place when page-locked)
+// checks shared by all six calls; carves the page-locked area (caller's rows / flags read in place when page-locked)
 int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const void* cam, const int32_t* rows, const uint8_t* flags,
             int n_mp, CallArea* A) {
   if (!m || !f || !map || !cam || n_mp < 0 || (n_mp && (!rows || !flags))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
@@ -474,8 +382,9 @@ int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const void* 
   if (orbfe_frame_device(f) != m->device) { set_err("frame and matcher live on different devices"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(m->device));
   (void)hipGetLastError();
-  const int wr = host_readable(rows), wf = host_readable(flags);
-  if (n_mp && (wr < 0 || wf < 0)) { set_err("rows and flags must be host memory"); return ORBFE_ERR_INVALID; }
+  // 0: ordinary host memory (copied below), 1: page-locked (read in place); anything else is some device's memory
+  const int wr = orbfe::gpu_readable(rows, m->device), wf = orbfe::gpu_readable(flags, m->device);
+  if (n_mp && ((unsigned)wr > 1u || (unsigned)wf > 1u)) { set_err("rows and flags must be host memory"); return ORBFE_ERR_INVALID; }
   // a row is an address: one branch-free sweep, and only if it finds a row outside the table a second one over the MapPoints
   // that are projected (skipped and bad ones may carry anything)
   unsigned hi = 0;
@@ -503,43 +412,6 @@ int prepare(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const void* 
   return ORBFE_OK;
 }
 
-ProjParams params(orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam, float cosLimit, int n_mp, const CallArea& A) {
-  ProjParams P{};
-  P.table = map->table.p;
-  P.rows = A.rows; P.flags = A.flags; P.n = n_mp;
-  P.cam = *cam;
-  float b[4];
-  orbfe::frame_bounds(f, b);
-  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
-  P.cosLimit = cosLimit;
-  P.blockInfo = A.blockInfo;
-  return P;
-}
-
-// after the stream has passed the kernel: MapPoints in view, first MapPoint whose level is outside the search's range
-void summary(const CallArea& A, int* nInView, int* firstBad) {
-  std::atomic_thread_fence(std::memory_order_acquire);
-  const volatile int* B = A.blockInfo;
-  int cnt = 0, bad = -1;
-  for (int b = 0; b < A.blocks; b++) {
-    cnt += B[2 * b];
-    if (bad < 0 && B[2 * b + 1] >= 0) bad = B[2 * b + 1];
-  }
-  *nInView = cnt;
-  *firstBad = bad;
-}
-
-void copy_out(const CallArea& A, int n_mp, uint8_t* in_view, float* proj_xy, int32_t* level, float* view_cos) {
-  if (in_view) memcpy(in_view, A.inView, (size_t)n_mp);
-  if (proj_xy) memcpy(proj_xy, A.xy, 8 * (size_t)n_mp);
-  if (level) memcpy(level, A.level, 4 * (size_t)n_mp);
-  if (view_cos) memcpy(view_cos, A.vcos, 4 * (size_t)n_mp);
-}
-
-}  // namespace
-
-namespace {
-
 // checks shared by the two source-projection calls, then prepare()'s
 int prepare_sources(orbfe_matcher* m, orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map, const OrbfeCamera* cam, int mode,
                     const int32_t* rows, const uint8_t* flags, int n_src, CallArea* A) {
@@ -562,24 +434,6 @@ int prepare_sources(orbfe_matcher* m, orbfe_frame* cur, orbfe_frame* src, orbfe_
   return ORBFE_OK;
 }
 
-SrcParams source_params(orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map, const OrbfeCamera* cam, int mode, int n_src,
-                        const CallArea& A) {
-  SrcParams P{};
-  P.table = map->table.p;
-  P.rows = A.rows; P.flags = A.flags; P.n = n_src;
-  P.mode = mode;
-  P.cam = *cam;
-  float b[4];
-  orbfe::frame_bounds(cur, b);
-  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
-  P.blockInfo = A.blockInfo;
-  return P;
-}
-
-}  // namespace
-
-namespace {
-
 // checks shared by the two keyframe-projection calls, then prepare()'s
 int prepare_keyframe(orbfe_matcher* m, orbfe_frame* kf, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj, const int32_t* rows,
                      const uint8_t* flags, int n, const float* scale_factors, int nlevels, CallArea* A) {
@@ -591,20 +445,128 @@ int prepare_keyframe(orbfe_matcher* m, orbfe_frame* kf, orbfe_local_map* map, co
   return prepare(m, kf, map, proj, rows, flags, n, A);
 }
 
+// the common parameter part of a call that projects n items into frame f, every host output switched on
+ProjCommon common_params(orbfe_frame* f, orbfe_local_map* map, int n, const CallArea& A) {
+  ProjCommon c{};
+  c.table = map->table.p;
+  c.rows = A.rows; c.flags = A.flags; c.n = n;
+  float b[4];
+  orbfe::frame_bounds(f, b);
+  c.minX = b[0]; c.maxX = b[1]; c.minY = b[2]; c.maxY = b[3];
+  c.valid = A.inView; c.xy = A.xy; c.level = A.level;
+  c.blockInfo = A.blockInfo;
+  return c;
+}
+
+// the source frame's part of a source projection: its resident octaves (and angles, largest octave), ordered behind its build
+SrcParams source_params(orbfe_frame* cur, orbfe_frame* src, orbfe_local_map* map, const OrbfeCamera* cam, int mode, int n_src,
+                        const CallArea& A, const float** srcAngle, int* maxOctave) {
+  SrcParams P{};
+  P.c = common_params(cur, map, n_src, A);
+  P.mode = mode;
+  P.cam = *cam;
+  orbfe::frame_source_arrays(src, &P.srcOct, srcAngle, maxOctave);
+  return P;
+}
+
 KfParams keyframe_params(orbfe_frame* kf, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj, int n, const float* scale_factors,
                          int nlevels, float th, const CallArea& A) {
   KfParams P{};
-  P.table = map->table.p;
-  P.rows = A.rows; P.flags = A.flags; P.n = n;
+  P.c = common_params(kf, map, n, A);
+  P.c.nlevels = nlevels;
   P.proj = *proj;
-  float b[4];
-  orbfe::frame_bounds(kf, b);
-  P.minX = b[0]; P.maxX = b[1]; P.minY = b[2]; P.maxY = b[3];
-  P.nlevels = nlevels;
   P.th = th;
   for (int l = 0; l < nlevels; l++) P.sf[l] = scale_factors[l];
-  P.blockInfo = A.blockInfo;
+  P.radius = A.vcos;
   return P;
+}
+
+// Fused call: the kernel writes only the host outputs the caller asked for, and the search's queries into map->q -- the
+// common three arrays, then the kernel's own two (aBytes / bBytes per item).
+int fused_params(orbfe_local_map* map, int nlevels, const void* valid, const void* xy, const void* level, ProjCommon* c, size_t aBytes,
+                 void** a, size_t bBytes, void** b) {
+  if (!valid) c->valid = nullptr;
+  if (!xy) c->xy = nullptr;
+  if (!level) c->level = nullptr;
+  c->nlevels = nlevels;
+  const size_t n = (size_t)c->n;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  const size_t oXY = take(8 * n), oL = take(4 * n), oR = take(4 * n), oA = take(aBytes * n), oB = take(bBytes * n);
+  const int rc = map->q.ensure(o);
+  if (rc) return rc;
+  uint8_t* D = map->q.p;
+  c->dxy = (float*)(D + oXY); c->dlevel = (int32_t*)(D + oL); c->drow = (int32_t*)(D + oR);
+  *a = D + oA; *b = D + oB;
+  return ORBFE_OK;
+}
+
+// after the stream has passed the kernel: items valid, first valid item whose level is outside the search's range
+void summary(const CallArea& A, int* nValid, int* firstBad) {
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const volatile int* B = A.blockInfo;
+  int cnt = 0, bad = -1;
+  for (int b = 0; b < A.blocks; b++) {
+    cnt += B[2 * b];
+    if (bad < 0 && B[2 * b + 1] >= 0) bad = B[2 * b + 1];
+  }
+  *nValid = cnt;
+  *firstBad = bad;
+}
+
+// the caller's output arrays (any may be null); aux: viewing cosines / radii
+struct Outputs {
+  uint8_t* valid;
+  float* xy;
+  int32_t* level;
+  float* aux;
+};
+void copy_out(const CallArea& A, int n, const Outputs& O) {
+  if (O.valid) memcpy(O.valid, A.inView, (size_t)n);
+  if (O.xy) memcpy(O.xy, A.xy, 8 * (size_t)n);
+  if (O.level) memcpy(O.level, A.level, 4 * (size_t)n);
+  if (O.aux) memcpy(O.aux, A.vcos, 4 * (size_t)n);
+}
+
+// A projection-only call after prepare(): launch, wait, count, copy out.
+template <class Launch>
+int run_projection(orbfe_matcher* m, const CallArea& A, int n, Launch launch, const Outputs& O, int* count) {
+  if (count) *count = 0;
+  if (n == 0) return ORBFE_OK;
+  launch();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  copy_out(A, n, O);
+  if (count) *count = cnt;
+  return ORBFE_OK;
+}
+
+// A fused call once its parameters stand: the projection kernel, then the window search and the bookkeeping on the same
+// stream (search() returns when its result is back; `searched` says whether it submitted anything, i.e. the frame has
+// keypoints).  `what` names an item in the error text.
+template <class Launch, class Search>
+int run_fused(orbfe_matcher* m, const CallArea& A, int n, int nlevels, bool searched, const char* what, Launch launch, Search search,
+              const Outputs& O, int* nmatches, int* count) {
+  launch();
+  HIP_TRY(hipGetLastError());
+  const int rc = search();
+  if (rc) {
+    (void)hipStreamSynchronize(m->stream);
+    return rc;
+  }
+  if (!searched) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
+  int cnt = 0, bad = -1;
+  summary(A, &cnt, &bad);
+  *count = cnt;
+  copy_out(A, n, O);
+  if (bad >= 0) {
+    *nmatches = 0;
+    set_err("%s %d: predicted level outside [0, %d)", what, bad, nlevels);
+    return ORBFE_ERR_INVALID;
+  }
+  return ORBFE_OK;
 }
 
 }  // namespace
@@ -669,25 +631,17 @@ int orbfe_local_map_set_rows(orbfe_local_map* map, int n, const int32_t* rows, c
   HIP_TRY(hipEventRecord(map->staged, m->stream));
   return ORBFE_OK;
 }
-
 int orbfe_project_local_map(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
                             float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp, uint8_t* in_view,
                             float* proj_xy, int32_t* level, float* view_cos, int* n_in_view) {
   CallArea A;
-  int rc = prepare(m, f, map, cam, rows, flags, n_mp, &A);
+  const int rc = prepare(m, f, map, cam, rows, flags, n_mp, &A);
   if (rc) return rc;
-  if (n_in_view) *n_in_view = 0;
-  if (n_mp == 0) return ORBFE_OK;
-  ProjParams P = params(f, map, cam, view_cos_limit, n_mp, A);
-  P.inView = A.inView; P.xy = A.xy; P.level = A.level; P.vcos = A.vcos;
-  hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  copy_out(A, n_mp, in_view, proj_xy, level, view_cos);
-  if (n_in_view) *n_in_view = cnt;
-  return ORBFE_OK;
+  ProjParams P{};
+  P.c = common_params(f, map, n_mp, A);
+  P.cam = *cam; P.cosLimit = view_cos_limit; P.vcos = A.vcos;
+  return run_projection(m, A, n_mp, [&] { hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P); },
+                        Outputs{in_view, proj_xy, level, view_cos}, n_in_view);
 }
 
 int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
@@ -710,60 +664,35 @@ int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_loca
     for (int i = 0; i < n; i++) kp_assigned[i] = -1;
     return ORBFE_OK;
   }
-  const size_t c = (size_t)n_mp;
-  const size_t oXY = 0, oL = al(8 * c), oV = oL + al(4 * c), oF = oV + al(4 * c), oR = oF + al(c), total = oR + al(4 * c);
-  if ((rc = map->q.ensure(total))) return rc;
-  uint8_t* D = map->q.p;
-  ProjParams P = params(f, map, cam, view_cos_limit, n_mp, A);
-  if (in_view) P.inView = A.inView;
-  if (proj_xy) P.xy = A.xy;
-  if (level) P.level = A.level;
-  if (view_cos) P.vcos = A.vcos;
-  P.nlevels = nlevels;
-  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.dvcos = (float*)(D + oV); P.dflags = D + oF; P.drow = (int32_t*)(D + oR);
-  hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
-  if ((rc = orbfe::sbp_frame_device_queries(m, f, scale_factors, nlevels, kp_occupied, P.dxy, P.dlevel, P.dvcos, P.dflags,
-                                            map->table.p + 32, P.drow, n_mp, th, nnratio, kp_assigned, nmatches))) {
-    (void)hipStreamSynchronize(m->stream);
-    return rc;
-  }
-  if (n == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  *n_in_view = cnt;
-  copy_out(A, n_mp, in_view, proj_xy, level, view_cos);
-  if (bad >= 0) {
-    *nmatches = 0;
-    set_err("MapPoint %d: predicted level outside [0, %d)", bad, nlevels);
-    return ORBFE_ERR_INVALID;
-  }
-  return ORBFE_OK;
+  ProjParams P{};
+  P.c = common_params(f, map, n_mp, A);
+  P.cam = *cam; P.cosLimit = view_cos_limit; P.vcos = view_cos ? A.vcos : nullptr;
+  if ((rc = fused_params(map, nlevels, in_view, proj_xy, level, &P.c, 4, (void**)&P.dvcos, 1, (void**)&P.dflags))) return rc;
+  return run_fused(
+      m, A, n_mp, nlevels, n != 0, "MapPoint",
+      [&] { hipLaunchKernelGGL(k_project_local_map, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P); },
+      [&] {
+        return orbfe::sbp_frame_device_queries(m, f, scale_factors, nlevels, kp_occupied, P.c.dxy, P.c.dlevel, P.dvcos, P.dflags,
+                                               map->table.p + 32, P.c.drow, n_mp, th, nnratio, kp_assigned, nmatches);
+      },
+      Outputs{in_view, proj_xy, level, view_cos}, nmatches, n_in_view);
 }
 
 int orbfe_project_sources(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame, orbfe_local_map* map,
                           const OrbfeCamera* cam, int mode, const int32_t* rows, const uint8_t* flags, int n_src, uint8_t* valid,
                           float* uv, int32_t* level, int* n_valid) {
   CallArea A;
-  int rc = prepare_sources(m, cur_frame, src_frame, map, cam, mode, rows, flags, n_src, &A);
+  const int rc = prepare_sources(m, cur_frame, src_frame, map, cam, mode, rows, flags, n_src, &A);
   if (rc) return rc;
-  if (n_valid) *n_valid = 0;
-  if (n_src == 0) return ORBFE_OK;
-  SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A);
   const float* srcAngle = nullptr;
   int maxOctave = 0;
-  orbfe::frame_source_arrays(src_frame, &P.srcOct, &srcAngle, &maxOctave);
-  P.valid = A.inView; P.uv = A.xy; P.level = A.level;
-  orbfe::frame_wait_ready(src_frame, m->stream);
-  hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  copy_out(A, n_src, valid, uv, level, nullptr);
-  if (n_valid) *n_valid = cnt;
-  return ORBFE_OK;
+  const SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A, &srcAngle, &maxOctave);
+  return run_projection(m, A, n_src,
+                        [&] {
+                          orbfe::frame_wait_ready(src_frame, m->stream);
+                          hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+                        },
+                        Outputs{valid, uv, level, nullptr}, n_valid);
 }
 
 int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame,
@@ -787,65 +716,38 @@ int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_
     for (int i = 0; i < n; i++) kp_assigned[i] = -1;
     return ORBFE_OK;
   }
-  SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A);
   const float* srcAngle = nullptr;
   int maxOctave = 0;
-  orbfe::frame_source_arrays(src_frame, &P.srcOct, &srcAngle, &maxOctave);
+  SrcParams P = source_params(cur_frame, src_frame, map, cam, mode, n_src, A, &srcAngle, &maxOctave);
   // nLastOctave indexes mvScaleFactors (:1347): refused up front from the source frame's largest octave
   if (mode == ORBFE_SRC_LAST_FRAME && maxOctave >= nlevels) {
     set_err("the source frame holds a keypoint of octave %d: outside [0, %d)", maxOctave, nlevels);
     return ORBFE_ERR_INVALID;
   }
-  const size_t c = (size_t)n_src;
-  const size_t oXY = 0, oL = al(8 * c), oR = oL + al(4 * c), oV = oR + al(4 * c), oC = oV + al(c), total = oC + al(c);
-  if ((rc = map->q.ensure(total))) return rc;
-  uint8_t* D = map->q.p;
-  if (valid) P.valid = A.inView;
-  if (uv) P.uv = A.xy;
-  if (level) P.level = A.level;
-  P.nlevels = nlevels;
-  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.drow = (int32_t*)(D + oR); P.dvalid = D + oV; P.dclaim = D + oC;
-  orbfe::frame_wait_ready(src_frame, m->stream);
-  hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
-  if ((rc = orbfe::sbp_uv_frame_device_queries(m, cur_frame, scale_factors, nlevels, kp_occupied, P.dxy, P.dlevel, srcAngle, P.dvalid,
-                                               P.dclaim, map->table.p + 32, P.drow, n_src, th, max_dist,
-                                               mode == ORBFE_SRC_KEYFRAME ? 1 : 0, check_orientation, kp_assigned, nmatches))) {
-    (void)hipStreamSynchronize(m->stream);
-    return rc;
-  }
-  if (n == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  *n_valid = cnt;
-  copy_out(A, n_src, valid, uv, level, nullptr);
-  if (bad >= 0) {
-    *nmatches = 0;
-    set_err("source %d: predicted level outside [0, %d)", bad, nlevels);
-    return ORBFE_ERR_INVALID;
-  }
-  return ORBFE_OK;
+  if ((rc = fused_params(map, nlevels, valid, uv, level, &P.c, 1, (void**)&P.dvalid, 1, (void**)&P.dclaim))) return rc;
+  return run_fused(
+      m, A, n_src, nlevels, n != 0, "source",
+      [&] {
+        orbfe::frame_wait_ready(src_frame, m->stream);
+        hipLaunchKernelGGL(k_project_sources, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
+      },
+      [&] {
+        return orbfe::sbp_uv_frame_device_queries(m, cur_frame, scale_factors, nlevels, kp_occupied, P.c.dxy, P.c.dlevel, srcAngle, P.dvalid,
+                                                  P.dclaim, map->table.p + 32, P.c.drow, n_src, th, max_dist,
+                                                  mode == ORBFE_SRC_KEYFRAME ? 1 : 0, check_orientation, kp_assigned, nmatches);
+      },
+      Outputs{valid, uv, level, nullptr}, nmatches, n_valid);
 }
 
 int orbfe_project_keyframe(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map, const OrbfeKeyFrameProjection* proj,
                            const int32_t* rows, const uint8_t* flags, int n, const float* scale_factors, int nlevels, float th,
                            uint8_t* valid, float* uv, int32_t* level, float* radius, int* n_valid) {
   CallArea A;
-  int rc = prepare_keyframe(m, kf_frame, map, proj, rows, flags, n, scale_factors, nlevels, &A);
+  const int rc = prepare_keyframe(m, kf_frame, map, proj, rows, flags, n, scale_factors, nlevels, &A);
   if (rc) return rc;
-  if (n_valid) *n_valid = 0;
-  if (n == 0) return ORBFE_OK;
-  KfParams P = keyframe_params(kf_frame, map, proj, n, scale_factors, nlevels, th, A);
-  P.valid = A.inView; P.uv = A.xy; P.level = A.level; P.radius = A.vcos;
-  hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  copy_out(A, n, valid, uv, level, radius);
-  if (n_valid) *n_valid = cnt;
-  return ORBFE_OK;
+  const KfParams P = keyframe_params(kf_frame, map, proj, n, scale_factors, nlevels, th, A);
+  return run_projection(m, A, n, [&] { hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P); },
+                        Outputs{valid, uv, level, radius}, n_valid);
 }
 
 int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map,
@@ -857,7 +759,6 @@ int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_fram
   CallArea A;
   int rc = prepare_keyframe(m, kf_frame, map, proj, rows, flags, n, scale_factors, nlevels, &A);
   if (rc) return rc;
-  const int nkp = orbfe_frame_size(kf_frame);
   *nmatches = 0;
   *n_valid = 0;
   for (int i = 0; i < n; i++) {
@@ -865,35 +766,18 @@ int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_fram
     if (best_dist) best_dist[i] = -1;
   }
   if (n == 0) return ORBFE_OK;
-  const size_t c = (size_t)n;
-  const size_t oXY = 0, oL = al(8 * c), oR = oL + al(4 * c), oA = oR + al(4 * c), oV = oA + al(4 * c), total = oV + al(c);
-  if ((rc = map->q.ensure(total))) return rc;
-  uint8_t* D = map->q.p;
   KfParams P = keyframe_params(kf_frame, map, proj, n, scale_factors, nlevels, th, A);
-  if (valid) P.valid = A.inView;
-  if (uv) P.uv = A.xy;
-  if (level) P.level = A.level;
-  P.dxy = (float*)(D + oXY); P.dlevel = (int32_t*)(D + oL); P.drow = (int32_t*)(D + oR); P.dradius = (float*)(D + oA); P.dvalid = D + oV;
-  hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P);
-  HIP_TRY(hipGetLastError());
-  // the window search and the bookkeeping follow on the same stream; the search returns when its result is back
-  if ((rc = orbfe::search_projected_frame_device_queries(m, kf_frame, scale_factors, nlevels, th, P.dxy, P.dlevel, P.dradius, P.dvalid,
-                                                         map->table.p + 32, P.drow, n, kp_skip, claim, inv_level_sigma2, chi2,
-                                                         max_dist, best_idx, best_dist, nmatches))) {
-    (void)hipStreamSynchronize(m->stream);
-    return rc;
-  }
-  if (nkp == 0) HIP_TRY(hipStreamSynchronize(m->stream));   // (no search was submitted: wait for the projection alone)
-  int cnt = 0, bad = -1;
-  summary(A, &cnt, &bad);
-  *n_valid = cnt;
-  copy_out(A, n, valid, uv, level, nullptr);
-  if (bad >= 0) {
-    *nmatches = 0;
-    set_err("MapPoint %d: predicted level outside [0, %d)", bad, nlevels);
-    return ORBFE_ERR_INVALID;
-  }
-  return ORBFE_OK;
+  P.radius = nullptr;
+  if ((rc = fused_params(map, nlevels, valid, uv, level, &P.c, 4, (void**)&P.dradius, 1, (void**)&P.dvalid))) return rc;
+  return run_fused(
+      m, A, n, nlevels, orbfe_frame_size(kf_frame) != 0, "MapPoint",
+      [&] { hipLaunchKernelGGL(k_project_keyframe, dim3(A.blocks), dim3(kProjThreads), 0, m->stream, P); },
+      [&] {
+        return orbfe::search_projected_frame_device_queries(m, kf_frame, scale_factors, nlevels, th, P.c.dxy, P.c.dlevel, P.dradius, P.dvalid,
+                                                            map->table.p + 32, P.c.drow, n, kp_skip, claim, inv_level_sigma2, chi2,
+                                                            max_dist, best_idx, best_dist, nmatches);
+      },
+      Outputs{valid, uv, level, nullptr}, nmatches, n_valid);
 }
 
 int orbfe_debug_logf(orbfe_matcher* m, const float* x, int n, float* out) {

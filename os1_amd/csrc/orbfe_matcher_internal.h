@@ -1,6 +1,6 @@
 // orbfe_matcher_internal.h -- shared by orbfe_matcher.hip (host-array searches), orbfe_frame.hip (device-resident frames
 // + GPU-side match bookkeeping) and orbfe_bow.hip: the window kernel, its parameter block, buffer helpers and the matcher
-// handle.  Reference semantics: Frame::GetFeaturesInArea (src/Frame.cc:209-262) over Frame::AssignFeaturesToGrid's
+// handle; and the declarations of what the matcher-side files ask of each other.  Reference semantics: Frame::GetFeaturesInArea (src/Frame.cc:209-262) over Frame::AssignFeaturesToGrid's
 // 64x48 grid (Frame.cc:114-129, 264-274), ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1605-1621).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -470,6 +470,53 @@ inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 using namespace orbfe_match;
 
 struct orbfe_frame;
+struct orbfe_matcher;
+struct orbfe_local_map;
+struct orbfe_extractor;
+
+// ---- what the library's files ask of each other (each is defined once, in the file named) -------------------------------
+namespace orbfe {
+// orbfe_extractor.hip: one frame of the handle's last collected batch
+int extractor_view(orbfe_extractor* h, int frame, ExtractView* out);
+
+// orbfe_frame.hip.  > 0: the kernels can read p in place (1: page-locked host memory, 2: memory of device `device`); 0: ordinary
+// host memory (the caller copies it into a page-locked arena); -1: memory of another device
+int gpu_readable(const void* p, int device);
+// a resident frame's mnMinX, mnMaxX, mnMinY, mnMaxY; its octaves and angles in keypoint order and its largest octave; its
+// undistorted coordinates in keypoint order; its descriptor rows in keypoint order (none of these waits) -- and the stream
+// order behind the frame's build, for the kernels that read them
+void frame_bounds(const orbfe_frame* f, float out[4]);
+void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
+void frame_xy(const orbfe_frame* f, const float** x, const float** y);
+const uint8_t* frame_descriptor_rows(const orbfe_frame* f);
+void frame_wait_ready(orbfe_frame* f, hipStream_t st);
+// the three searches on queries that a projection kernel of orbfe_localmap.hip has left in device memory, earlier on the
+// matcher's stream (the host reads none of the d_ arrays)
+int sbp_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                             const float* d_xy, const int32_t* d_level, const float* d_viewcos, const uint8_t* d_flags,
+                             const uint8_t* d_desc, const int32_t* d_desc_row, int n_mp, float th, float nnratio,
+                             int32_t* kp_assigned, int* nmatches);
+int sbp_uv_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, const uint8_t* kp_occupied,
+                                const float* d_xy, const int32_t* d_level, const float* d_angle, const uint8_t* d_valid,
+                                const uint8_t* d_claim, const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, float th,
+                                int max_dist, int skip_any_occupied, int check_orientation, int32_t* kp_assigned, int* nmatches);
+int search_projected_frame_device_queries(orbfe_matcher* m, orbfe_frame* f, const float* scale_factors, int nlevels, float th,
+                                          const float* d_xy, const int32_t* d_level, const float* d_radius, const uint8_t* d_valid,
+                                          const uint8_t* d_desc, const int32_t* d_desc_row, int n_src, const uint8_t* kp_skip, int claim,
+                                          const float* inv_level_sigma2, double chi2, int max_dist, int32_t* best_idx, int32_t* best_dist,
+                                          int* nmatches);
+
+// orbfe_localmap.hip: what orbfe_mprefresh.hip needs of a table -- its matcher, size, rows, and the slot of its own scratch
+struct LocalMapView {
+  orbfe_matcher* m;
+  int capacity;
+  uint8_t* table;
+  std::shared_ptr<void>* scratch;   // owned by the map, released with it (its device is current then)
+};
+void local_map_view(orbfe_local_map* map, LocalMapView* v);
+}  // namespace orbfe
+using orbfe::gpu_readable;
+
 struct orbfe_matcher {
   int device = 0;
   hipStream_t stream = nullptr;

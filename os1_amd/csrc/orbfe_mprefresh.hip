@@ -30,19 +30,6 @@
 
 #include <atomic>
 
-namespace orbfe {
-struct LocalMapView {
-  orbfe_matcher* m;
-  int capacity;
-  uint8_t* table;
-  std::shared_ptr<void>* scratch;   // owned by the map, released with it (its device is current then)
-};
-void local_map_view(orbfe_local_map* map, LocalMapView* v);
-void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
-const uint8_t* frame_descriptor_rows(const orbfe_frame* f);
-void frame_wait_ready(orbfe_frame* f, hipStream_t st);
-}  // namespace orbfe
-
 namespace {
 
 constexpr int kRowBytes = 64;                    // pos[3], normal[3], mfMinDistance, mfMaxDistance, descriptor[32]

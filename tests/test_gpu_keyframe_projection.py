@@ -265,6 +265,49 @@ def test_errors_leave_everything_usable(api, ref, oracle):
     matcher.close()
 
 
+def test_out_of_range_level_in_the_second_block(api, matcher, ref, oracle):
+    """Fuse on the 500-feature frames: two 256-lane blocks, the second one partial.  Two valid points of the second block
+    predict a level >= nlevels (mfMaxDistance = dist * 1.2^9): the fused call fails naming the lower of them, the projection
+    alone reports both as they are, and with the two flagged ORBFE_MP_SKIP the fused call equals the oracle."""
+    W, H = 640, 480
+    kA, dA, kB, dB, sf = _frames(api, W, H, 500)
+    fn, th = K.FUSE, 3.0
+    sc = K.scene(kA, dA, kB, dB, sf, W, H, seed=K.case_seed(fn, th, W))
+    d = K.make_case(ref, fn, sc, th)['dirs'][0]
+    rows, flags = d['rows'], d['flags']
+    n = len(rows)
+    assert 256 < n <= 512
+    proj = K.ref_project(ref, sc['tab'], rows, flags, d['pr'], sc['bounds'], sf, th)
+    named_once = np.array([(rows == r).sum() == 1 for r in rows])
+    cand = np.flatnonzero((proj['valid'] == 1) & named_once & (np.arange(n) >= 256))
+    assert len(cand) >= 4
+    lo, hi = int(cand[1]), int(cand[3])
+    for s in (hi, lo):
+        row = int(rows[s])
+        dist = K.U._norm((sc['tab']['pos'][row] - d['pr']['Ow'])[None].astype(np.float32))[0]
+        sc['tab']['min'][row], sc['tab']['max'][row] = 0.0, dist * np.float32(1.2 ** 9)
+    frames = dict(B=matcher.frame(kB, dB, sc['bounds']))
+    lm = _table(api, matcher, sc['tab'])
+    want = K.ref_project(ref, sc['tab'], rows, flags, d['pr'], sc['bounds'], sf, th)
+    outside = (want['valid'] == 1) & ((want['level'] < 0) | (want['level'] >= len(sf)))
+    assert np.flatnonzero(outside).tolist() == [lo, hi]
+    with pytest.raises(api.OrbfeError) as e:
+        _fused(api, matcher, frames, lm, d, sf, th)
+    assert e.value.code == -1
+    assert 'MapPoint %d: predicted level outside [0, %d)' % (lo, len(sf)) in str(e.value)
+    K.check_projection(matcher.project_keyframe(frames['B'], lm, K.api_projection(api, d['pr']), rows, flags, sf, float(th)), want)
+    d2 = dict(d)
+    d2['flags'] = flags.copy()
+    d2['flags'][[lo, hi]] |= K.MP_SKIP
+    want = K.ref_project(ref, sc['tab'], rows, d2['flags'], d['pr'], sc['bounds'], sf, th)
+    nm, bi, bd = K.cpu_search(oracle, d2, want, sc, kB, dB, sf)
+    got = _fused(api, matcher, frames, lm, d2, sf, th)
+    K.check_projection(got, want)
+    assert got['nmatches'] == nm and nm > 0 and (got['best_idx'] == bi).all() and (got['best_dist'] == bd).all()
+    lm.close()
+    frames['B'].close()
+
+
 def test_facade_sequence(api, tmp_path):
     """tests/cpp/keyframe_projection_test.cpp: the four new shim templates on facade_pose_test's mock model, every call equal to
     the oracle's whole function and to the host-projection template it stands in for"""

@@ -257,6 +257,45 @@ def test_edges(api, matcher, ref, oracle):
     frame.close()
 
 
+def test_out_of_range_level_in_the_second_block(api, matcher, ref, oracle):
+    """500 MapPoints are two 256-lane blocks, the second one partial.  MapPoints 300 and 270 predict a level >= nlevels
+    (mfMaxDistance = dist * 1.2^9): the fused call fails naming the lowest of them, the projection alone reports both as they
+    are, and with the two skipped the fused call equals the oracle."""
+    W, H = 1920, 1080
+    kA, dA, kB, dB, sf = _pair(api, W, H, 2000)
+    camA = U.camera(W, H)
+    mp = U.triangulate(kA, dA, sf, 500, camA, seed=51)
+    for i in (300, 270):
+        d = U._norm((mp['pos'][i] - camA['Ow'])[None])[0]
+        mp['min'][i] = 0.0
+        mp['max'][i] = d * np.float32(1.2 ** 9)
+    bounds = (0.0, float(W), 0.0, float(H))
+    frame = matcher.frame(kB, dB, bounds)
+    lm = _table(api, matcher, mp)
+    occ = np.zeros(len(kB), np.uint8)
+    acam = U.api_camera(api, camA)
+    rows = np.arange(500, dtype=np.int32)
+    flags = np.zeros(500, np.uint8)
+    want = U.ref_project(ref, mp, rows, flags, camA, bounds)
+    outside = (want['in_view'] == 1) & ((want['level'] < 0) | (want['level'] >= len(sf)))
+    assert np.flatnonzero(outside).tolist() == [270, 300]
+    with pytest.raises(api.OrbfeError) as e:
+        matcher.search_local_points(frame, lm, acam, rows, flags, occ, sf, 1.0)
+    assert e.value.code == -1
+    assert 'MapPoint 270: predicted level outside [0, %d)' % len(sf) in str(e.value)
+    _check_projection(matcher.project_local_map(frame, lm, acam, rows, flags), want)
+    fl2 = flags.copy()
+    fl2[[270, 300]] = 16
+    want = U.ref_project(ref, mp, rows, fl2, camA, bounds)
+    got = matcher.search_local_points(frame, lm, acam, rows, fl2, occ, sf, 1.0)
+    _check_projection(got, want)
+    on, oa = oracle.search_by_projection(kB, dB, bounds, sf, occ, want['proj_xy'], want['level'], want['view_cos'],
+                                         U.oracle_flags(want, fl2), mp['desc'][rows], 1.0, 0.8)
+    assert got['nmatches'] == on and on > 0 and (got['kp_assigned'] == oa).all()
+    lm.close()
+    frame.close()
+
+
 def test_search_local_points_facade_sequence(api, tmp_path, ref, oracle):
     """tests/cpp/local_map_test.cpp: a tracking-shaped sequence through orb_shim.hpp's SearchLocalPoints"""
     import local_map_facade as F

@@ -234,6 +234,48 @@ def test_errors_leave_everything_usable(api, ref, oracle):
     matcher.close()
 
 
+def test_out_of_range_level_in_the_second_block(api, matcher, ref, oracle):
+    """KEYFRAME mode on the 500-feature frame: two 256-lane blocks, the second one partial.  Two valid sources of the second
+    block predict a level >= nlevels (mfMaxDistance = dist * 1.2^9): the fused call fails naming the lower of them, the
+    projection alone reports both as they are, and with the two taken out (no MapPoint: ORBFE_MP_SKIP) the fused call equals
+    the oracle.  (In LAST_FRAME mode the level is the source's octave, refused up front.)"""
+    W, H = 640, 480
+    kA, dA, kB, dB, sf = _frames(api, W, H, 500)
+    mode = S.KEYFRAME
+    th, max_dist = S.CASES[mode][0]
+    sc = S.scene(kA, dA, kB, sf, W, H, seed=S.case_seed(mode, th, W))
+    n = sc['n']
+    assert 256 < n <= 512
+    flags = S.flags_of(sc, mode)
+    proj = S.ref_project(ref, sc['tab'], sc['rows'], flags, kA['octave'], sc['cam'], sc['bounds'], mode)
+    named_once = np.bincount(sc['rows'], minlength=n)[sc['rows']] == 1
+    cand = np.flatnonzero((proj['valid'] == 1) & named_once & (np.arange(n) >= 256))
+    assert len(cand) >= 4
+    lo, hi = int(cand[1]), int(cand[3])
+    for s in (hi, lo):
+        row = int(sc['rows'][s])
+        d = U._norm((sc['tab']['pos'][row] - sc['cam']['Ow'])[None].astype(np.float32))[0]
+        sc['tab']['min'][row], sc['tab']['max'][row] = 0.0, d * np.float32(1.2 ** 9)
+    src = matcher.frame(kA, dA, sc['bounds'])
+    cur = matcher.frame(kB, dB, sc['bounds'])
+    lm = _table(api, matcher, sc['tab'])
+    acam = U.api_camera(api, sc['cam'])
+    want = S.ref_project(ref, sc['tab'], sc['rows'], flags, kA['octave'], sc['cam'], sc['bounds'], mode)
+    outside = (want['valid'] == 1) & ((want['level'] < 0) | (want['level'] >= len(sf)))
+    assert np.flatnonzero(outside).tolist() == [lo, hi]
+    with pytest.raises(api.OrbfeError) as e:
+        matcher.search_by_projection_sources(cur, src, lm, acam, mode, sc['rows'], flags, sc['st']['occ'], sf, th, max_dist)
+    assert e.value.code == -1
+    assert 'source %d: predicted level outside [0, %d)' % (lo, len(sf)) in str(e.value)
+    S.check_projection(matcher.project_sources(cur, src, lm, acam, mode, sc['rows'], flags), want)
+    sc['st']['absent'][[lo, hi]] = 1
+    assert (S.flags_of(sc, mode)[[lo, hi]] & S.MP_SKIP).all()
+    _check_fused(api, matcher, ref, oracle, cur, src, lm, sc, mode, kA, kB, dB, sf, th, max_dist, True, W, dict(pruned=0))
+    lm.close()
+    cur.close()
+    src.close()
+
+
 def test_facade_sequence(api, tmp_path):
     """tests/cpp/source_projection_test.cpp: a tracking-shaped sequence through orb_shim.hpp's SearchByProjectionLastFrame /
     SearchByProjectionKeyFrame, every call equal to orc_sbp_frame / orc_sbp_keyframe, rows sent only for changed MapPoints,
