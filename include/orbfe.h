@@ -848,6 +848,19 @@ int orbfe_bow_transform(orbfe_vocabulary* v, const uint8_t* desc, int n, int in_
                         uint32_t* bow_ids, double* bow_values, int* n_words, uint32_t* fv_nodes, uint32_t* fv_offsets,
                         uint32_t* fv_features, int* n_fv_nodes, uint32_t* word_of_feature, uint32_t* node_of_feature);
 
+/* orbfe_bow_transform for n_sets descriptor sets in ONE submission and ONE wait: the KeyFrame::ComputeBoW loop of a map load
+ * (src/Osmap.cpp, Osmap::rebuild).  Set s has n[s] rows (0 is allowed) at desc[s]; WHERE THE ROWS LIE is decided per set:
+ * ordinary host memory (copied into one upload), page-locked host memory or 16-byte aligned rows in the memory of the
+ * vocabulary's device (orbfe_frame_descriptors_device) -- both read in place.  Every output is an array of n_sets per-set
+ * pointers (n_words, n_fv_nodes: n_sets ints), each in the layout and with the bytes orbfe_bow_transform gives for that set
+ * alone; word_of_feature / node_of_feature may be NULL, or hold NULL for a set.  capacity[s]: entries the outputs of set s
+ * hold (fv_offsets[s]: capacity[s] + 1); capacity[s] < n[s] fails the call with ORBFE_ERR_OVERFLOW, the message names the
+ * set, and nothing is written for any set.  One grid covers every (set, feature) pair; at most 2^30 descriptors per call. */
+int orbfe_bow_transform_batch(orbfe_vocabulary* v, int levelsup, int n_sets, const uint8_t* const* desc, const int* n,
+                              const int* capacity, uint32_t* const* bow_ids, double* const* bow_values, int* n_words,
+                              uint32_t* const* fv_nodes, uint32_t* const* fv_offsets, uint32_t* const* fv_features,
+                              int* n_fv_nodes, uint32_t* const* word_of_feature, uint32_t* const* node_of_feature);
+
 /* Frame::ComputeBoW fused into the extractor: with a vocabulary set, every extract call also runs the tree descent on
  * the descriptors while they are still in HBM (right behind the descriptor kernel, same stream) and keeps the per-
  * keypoint (word, node) pairs of the last collected batch.  orbfe_extract_bow then returns frame `frame` of that batch
@@ -914,6 +927,14 @@ void orbfe_kfdb_destroy(orbfe_kfdb* db);
  * that is already in the database is an error (ORBFE_ERR_INVALID).  words ascending (a BowVector's order), n of them (n * 12
  * bytes are uploaded).  The keyframe goes to the BACK of every word's list, also when the key was there before and erased. */
 int orbfe_kfdb_add(orbfe_kfdb* db, uint64_t key, const uint32_t* words, const double* values, int n);
+/* orbfe_kfdb_add for n keyframes (the add loop of a map load): keyframe j has key keys[j] and n_words[j] (word, value) pairs
+ * at words[j] / values[j].  The database afterwards is the database after n single adds in index order (pool order, tombstones,
+ * compaction), so every later query returns the same bytes; the mutex is taken once, the entries go up as one staging image.
+ * All n keyframes are checked before anything is sent: words not ascending, a key already present or named twice
+ * (ORBFE_ERR_INVALID), a capacity exceeded (ORBFE_ERR_OVERFLOW) at entry j fail the whole call -- the message names j -- and
+ * change nothing. */
+int orbfe_kfdb_add_batch(orbfe_kfdb* db, int n, const uint64_t* keys, const uint32_t* const* words, const double* const* values,
+                         const int* n_words);
 /* void KeyFrameDatabase::erase(KeyFrame* pKF)  (:46-65); a key that is not in the database: nothing happens, as there. */
 int orbfe_kfdb_erase(orbfe_kfdb* db, uint64_t key);
 /* void KeyFrameDatabase::clear()  (:67-71) */

@@ -26,6 +26,8 @@ class KeyFrameDatabase {
       : mpVoc(&voc), mDb(orbfe::detail::defaultDevice(), voc.size(), (int)voc.getScoringType()) {}   // ORBFE_DEVICE, as the matcher
 
   void add(KeyFrame* pKF) { mDb.add(pKF); }
+  // Not in the reference: add(pKF) for every keyframe of a loaded map in one call (the add loop of Osmap::rebuild, src/Osmap.cpp)
+  void add(const std::vector<KeyFrame*>& vpKFs) { mDb.add(vpKFs); }
   void erase(KeyFrame* pKF) { mDb.erase(pKF); }
   void clear() { mDb.clear(); }
 

@@ -22,6 +22,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -352,6 +353,20 @@ class MatcherContext {
     cache_.insert(cache_.begin(), e);
     trim();
     return cache_.front().frame;
+  }
+
+  // the resident copy of F if the context HOLDS one (nothing is created, the cache's order stays); nullptr otherwise
+  template <class FrameLike>
+  orbfe_frame* residentIfHeld(const FrameLike& F) {
+    if (cap_ == 0 || cache_.empty() || orbfe_resident_epoch() != epoch_) return nullptr;
+    const int n = (int)F.mvKeysUn.size();
+    const float b[4] = {(float)F.mnMinX, (float)F.mnMaxX, (float)F.mnMinY, (float)F.mnMaxY};
+    detail::Hash128 hk, hd;
+    detail::hashBytes(hk, F.mvKeysUn.data(), (size_t)n * sizeof(OrbfeKeyPoint));
+    detail::hashDescriptorRows(hd, F.mDescriptors, n);
+    for (auto it = cache_.begin(); it != cache_.end(); ++it)
+      if (it->n == n && it->keys == hk && it->desc == hd && std::memcmp(it->bounds, b, sizeof b) == 0) return it->frame;
+    return nullptr;
   }
 
   // ---- the local map's descriptors on the device.  Tracking::SearchLocalPoints (Tracking.cc:818-824) sends the same few
@@ -1655,6 +1670,41 @@ class Vocabulary {
     }
   }
 
+  // transform() for several descriptor sets in one submission (orbfe_bow_transform_batch): rows[s] = the n[s] packed 32-byte
+  // rows of set s (host, page-locked or device memory), bow[s] / fv[s] = where its vectors go.  Each pair of vectors is what
+  // transform() gives for that set alone.
+  template <class BowVectorT, class FeatureVectorT>
+  void transformBatch(const std::vector<const uint8_t*>& rows, const std::vector<int>& n, const std::vector<BowVectorT*>& bow,
+                      const std::vector<FeatureVectorT*>& fv, int levelsup) {
+    const size_t ns = rows.size();
+    for (size_t s = 0; s < ns; s++) { bow[s]->clear(); fv[s]->clear(); }
+    if (!v_ || ns == 0) return;
+    size_t total = 0;
+    for (size_t s = 0; s < ns; s++) total += (size_t)n[s];
+    // one block per output array, set s at its prefix (fv_offsets: one entry more per set)
+    ids_.resize(total + 1); vals_.resize(total + 1); nodes_.resize(total + 1); offs_.resize(total + ns); feats_.resize(total + 1);
+    std::vector<uint32_t*> pi(ns), pn(ns), po(ns), pf(ns);
+    std::vector<double*> pv(ns);
+    std::vector<int> nw(ns, 0), nn(ns, 0);
+    size_t at = 0;
+    for (size_t s = 0; s < ns; s++) {
+      pi[s] = ids_.data() + at; pv[s] = vals_.data() + at; pn[s] = nodes_.data() + at; pf[s] = feats_.data() + at;
+      po[s] = offs_.data() + at + s;
+      at += (size_t)n[s];
+    }
+    check(orbfe_bow_transform_batch(v_, levelsup, (int)ns, rows.data(), n.data(), n.data(), pi.data(), pv.data(), nw.data(), pn.data(),
+                                    po.data(), pf.data(), nn.data(), nullptr, nullptr));
+    for (size_t s = 0; s < ns; s++) {
+      BowVectorT& v = *bow[s];
+      FeatureVectorT& f = *fv[s];
+      for (int i = 0; i < nw[s]; i++) v.insert(v.end(), typename BowVectorT::value_type(pi[s][i], pv[s][i]));
+      for (int i = 0; i < nn[s]; i++) {
+        auto it = f.insert(f.end(), typename FeatureVectorT::value_type(pn[s][i], typename FeatureVectorT::mapped_type()));
+        it->second.assign(pf[s] + po[s][i], pf[s] + po[s][i + 1]);
+      }
+    }
+  }
+
  private:
   int device_;
   orbfe_vocabulary* v_ = nullptr;
@@ -1666,6 +1716,46 @@ class Vocabulary {
 template <class FrameT>
 inline void ComputeBoW(Vocabulary& voc, FrameT& F) {
   if (F.mBowVec.empty()) voc.transform(F.mDescriptors, (int)F.mDescriptors.rows, F.mBowVec, F.mFeatVec, 4);
+}
+
+// KeyFrame::ComputeBoW for every keyframe of a loaded map (the loop of Osmap::rebuild, src/Osmap.cpp) in ONE submission.  The
+// reference's guard `if(mBowVec.empty())` holds per keyframe: a keyframe that has its vectors keeps them and sends nothing.
+// ctx (optional): a keyframe whose resident copy the context holds passes that copy's device rows; its descriptors do not
+// cross PCIe again.  Every keyframe ends up with the vectors the one-keyframe overload gives it.
+namespace detail {
+template <class KeyFrameT>
+inline void computeBoWBatch(Vocabulary& voc, const std::vector<KeyFrameT*>& vpKFs, MatcherContext* ctx) {
+  typedef typename std::remove_reference<decltype(vpKFs[0]->mBowVec)>::type BowVectorT;
+  typedef typename std::remove_reference<decltype(vpKFs[0]->mFeatVec)>::type FeatureVectorT;
+  std::vector<const uint8_t*> rows;
+  std::vector<int> n;
+  std::vector<BowVectorT*> bow;
+  std::vector<FeatureVectorT*> fv;
+  std::vector<std::vector<uint8_t> > packed;   // keyframes whose cv::Mat rows are not contiguous
+  packed.reserve(vpKFs.size());                // (the pointers handed out below must stay)
+  for (KeyFrameT* pKF : vpKFs) {
+    if (!pKF || !pKF->mBowVec.empty()) continue;
+    const int nk = (int)pKF->mDescriptors.rows;
+    const uint8_t* r = nullptr;
+    if (nk > 0 && ctx)
+      if (orbfe_frame* rf = ctx->residentIfHeld(*pKF)) r = orbfe_frame_descriptors_device(rf);
+    if (!r) {
+      packed.emplace_back();
+      r = detail::packedDescriptors(pKF->mDescriptors, nk, packed.back());
+    }
+    rows.push_back(r); n.push_back(nk); bow.push_back(&pKF->mBowVec); fv.push_back(&pKF->mFeatVec);
+  }
+  voc.transformBatch(rows, n, bow, fv, 4);
+}
+}  // namespace detail
+// (two overloads, so that a vector of keyframes never deduces as the FrameT of the one-frame form above)
+template <class KeyFrameT>
+inline void ComputeBoW(Vocabulary& voc, std::vector<KeyFrameT*>& vpKFs, MatcherContext* ctx = nullptr) {
+  detail::computeBoWBatch(voc, vpKFs, ctx);
+}
+template <class KeyFrameT>
+inline void ComputeBoW(Vocabulary& voc, const std::vector<KeyFrameT*>& vpKFs, MatcherContext* ctx = nullptr) {
+  detail::computeBoWBatch(voc, vpKFs, ctx);
 }
 
 namespace detail {
@@ -1856,6 +1946,49 @@ class KeyFrameDatabaseT {
   void add(KeyFrameT* pKF) {
     std::unique_lock<std::mutex> lock(mMutex);
     addLocked(pKF);
+  }
+  // add(pKF) for every keyframe of a loaded map, in the vector's order (the loop of Osmap::rebuild, src/Osmap.cpp): one
+  // orbfe_kfdb_add_batch.  The database afterwards is the database after the single adds; a keyframe that is already in it, or
+  // named twice, throws and nothing is added.
+  void add(const std::vector<KeyFrameT*>& vpKFs) {
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (vpKFs.empty()) return;
+    if (!db_) create(capK_, capE_);
+    const size_t n = vpKFs.size();
+    std::vector<uint64_t> keys(n);
+    std::vector<int> counts(n);
+    std::vector<size_t> at(n + 1, 0);
+    std::set<KeyFrameT*> named;
+    for (size_t j = 0; j < n; j++) {
+      if (seq_.count(vpKFs[j]) || !named.insert(vpKFs[j]).second)
+        throw std::runtime_error("orbfe: KeyFrameDatabase::add of a keyframe that is already in the database");
+      keys[j] = key(vpKFs[j]);
+      counts[j] = (int)vpKFs[j]->mBowVec.size();
+      at[j + 1] = at[j] + (size_t)counts[j];
+    }
+    std::vector<uint32_t> w(at[n] + 1);
+    std::vector<double> v(at[n] + 1);
+    std::vector<const uint32_t*> pw(n);
+    std::vector<const double*> pv(n);
+    for (size_t j = 0; j < n; j++) {
+      size_t i = at[j];
+      for (auto it = vpKFs[j]->mBowVec.begin(); it != vpKFs[j]->mBowVec.end(); ++it, ++i) { w[i] = (uint32_t)it->first; v[i] = it->second; }
+      pw[j] = w.data() + at[j]; pv[j] = v.data() + at[j];
+    }
+    int rc = orbfe_kfdb_add_batch(db_, (int)n, keys.data(), pw.data(), pv.data(), counts.data());
+    if (rc == ORBFE_ERR_OVERFLOW) {   // the reference's database has no capacity: grow the pool, as add(pKF) does
+      int nk = 0, ne = 0;
+      check(orbfe_kfdb_size(db_, &nk, &ne));
+      const long long wantE = (long long)ne + (long long)at[n], wantK = (long long)nk + (long long)n;
+      long long capE = capE_, capK = capK_;
+      while (capE < wantE) capE *= 2;
+      while (capK < wantK) capK *= 2;
+      if (capE > 0x7fffffffLL || capK > 0x7fffffffLL) throw std::runtime_error("orbfe: KeyFrameDatabase: more than 2^31 BowVector entries");
+      rebuild((int)capK, (int)capE);
+      rc = orbfe_kfdb_add_batch(db_, (int)n, keys.data(), pw.data(), pv.data(), counts.data());
+    }
+    check(rc);
+    for (size_t j = 0; j < n; j++) seq_[vpKFs[j]] = next_++;
   }
   // void KeyFrameDatabase::erase(KeyFrame* pKF)   :46-65
   void erase(KeyFrameT* pKF) {

@@ -147,6 +147,8 @@ def load_library():
     L.orbfe_kfdb_destroy.argtypes = [vp]
     L.orbfe_kfdb_destroy.restype = None
     L.orbfe_kfdb_add.argtypes = [vp, C.c_uint64, vp, vp, ci]
+    L.orbfe_kfdb_add_batch.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.orbfe_bow_transform_batch.argtypes = [vp, ci, ci] + [vp] * 12
     L.orbfe_kfdb_erase.argtypes = [vp, C.c_uint64]
     L.orbfe_kfdb_clear.argtypes = [vp]
     L.orbfe_kfdb_size.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
@@ -1278,6 +1280,37 @@ class Vocabulary:
         nw, nn = nw.value, nn.value
         return ids[:nw], vals[:nw], (fvn[:nn], fvo[:nn + 1], fvf[:int(fvo[nn])]), wof[:n], nof[:n]
 
+    def transform_batch(self, descs, levelsup=4, capacity=None, out=None):
+        """transform() of several descriptor sets in one submission (orbfe_bow_transform_batch) -> a list of transform()'s tuples.
+        A set is an (n, 32) uint8 array (ordinary memory, or the view of a PinnedArray: read in place) or a DeviceRows (a resident
+        frame's rows: read in place).  capacity: per-set output capacities (default: each set's size).  out: a BowBatchOutputs to
+        write into instead of fresh arrays."""
+        ns = len(descs)
+        keep, ptr, n = [], np.zeros(max(ns, 1), np.uint64), np.zeros(max(ns, 1), np.int32)
+        for s, d in enumerate(descs):
+            if isinstance(d, DeviceRows):
+                ptr[s], n[s] = d.ptr, d.n
+            else:
+                d = np.ascontiguousarray(d, np.uint8)
+                keep.append(d)
+                ptr[s], n[s] = (d.ctypes.data if len(d) else 0), len(d)
+        cap = n.copy() if capacity is None else np.ascontiguousarray(capacity, np.int32)
+        if out is None:
+            out = BowBatchOutputs(cap[:ns])
+        nw, nn = out.nw, out.nn
+        tab = np.zeros((7, max(ns, 1)), np.uint64)
+        for s in range(ns):
+            for k in range(7):
+                tab[k, s] = out[s][k].ctypes.data
+        _check(self.L.orbfe_bow_transform_batch(self.h, levelsup, ns, _p(ptr), _p(n), _p(cap), _p(tab[0]), _p(tab[1]), _p(nw), _p(tab[2]),
+                                                _p(tab[3]), _p(tab[4]), _p(nn), _p(tab[5]), _p(tab[6])))
+        res = []
+        for s in range(ns):
+            ids, vals, fvn, fvo, fvf, wof, nof = out[s]
+            a, b = int(nw[s]), int(nn[s])
+            res.append((ids[:a], vals[:a], (fvn[:b], fvo[:b + 1], fvf[:int(fvo[b])]), wof[:int(n[s])], nof[:int(n[s])]))
+        return res
+
     def close(self):
         if getattr(self, 'h', None):
             self.L.orbfe_vocabulary_destroy(self.h)
@@ -1288,6 +1321,26 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+class BowBatchOutputs(list):
+    """Caller-owned outputs for Vocabulary.transform_batch(out=...): a list of per-set (ids, vals, fvn, fvo, fvf, wof, nof) arrays plus
+    the n_words / n_fv_nodes arrays `nw` / `nn` -- for callers that want to see what a refused call left in them."""
+
+    def __init__(self, capacities, fill=0):
+        super().__init__()
+        for c in capacities:
+            c = int(c)
+            t = (np.zeros(max(c, 1), np.uint32), np.zeros(max(c, 1), np.float64), np.zeros(max(c, 1), np.uint32),
+                 np.zeros(max(c, 0) + 1, np.uint32), np.zeros(max(c, 1), np.uint32), np.zeros(max(c, 1), np.uint32),
+                 np.zeros(max(c, 1), np.uint32))
+            for a in t:
+                a.view(np.uint8)[:] = fill
+            self.append(t)
+        self.nw = np.zeros(max(len(self), 1), np.int32)
+        self.nn = np.zeros(max(len(self), 1), np.int32)
+        self.nw.view(np.uint8)[:] = fill
+        self.nn.view(np.uint8)[:] = fill
 
 
 class KeyFrameDatabase:
@@ -1307,6 +1360,20 @@ class KeyFrameDatabase:
         values = np.ascontiguousarray(values, np.float64)
         assert words.shape == values.shape and words.ndim == 1
         _check(self.L.orbfe_kfdb_add(self.h, key, _p(words), _p(values), len(words)))
+
+    def add_batch(self, keys, words, values):
+        """add() for several keyframes in one call (orbfe_kfdb_add_batch): the database afterwards is the database after the single
+        adds in order; an error at any entry raises and changes nothing."""
+        n = len(keys)
+        assert len(words) == n and len(values) == n
+        keys = np.ascontiguousarray(keys, np.uint64)
+        words = [np.ascontiguousarray(w, np.uint32) for w in words]
+        values = [np.ascontiguousarray(v, np.float64) for v in values]
+        pw = np.array([w.ctypes.data if len(w) else 0 for w in words] + [0], np.uint64)
+        pv = np.array([v.ctypes.data if len(v) else 0 for v in values] + [0], np.uint64)
+        cnt = np.array([len(w) for w in words] + [0], np.int32)
+        assert all(w.shape == v.shape and w.ndim == 1 for w, v in zip(words, values))
+        _check(self.L.orbfe_kfdb_add_batch(self.h, n, _p(keys) if n else None, _p(pw), _p(pv), _p(cnt)))
 
     def erase(self, key):
         _check(self.L.orbfe_kfdb_erase(self.h, key))

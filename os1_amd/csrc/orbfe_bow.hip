@@ -25,9 +25,11 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "bow_batch_plan.h"
 
 namespace orbfe {
 void set_err(const char* fmt, ...);
+int gpu_readable(const void* p, int device);   // orbfe_frame.hip: 0 ordinary host memory, 1 page-locked, 2 this device's, -1 another's
 int matcher_device(const orbfe_matcher* m);
 hipStream_t matcher_stream(const orbfe_matcher* m);
 std::shared_ptr<void>& matcher_bow_slot(orbfe_matcher* m);
@@ -111,16 +113,12 @@ __device__ inline int hamming256(const uint4& a0, const uint4& a1, const uint4& 
 // Tree descent (TemplatedVocabulary.h:1306-1347).  16 lanes per descriptor; lane c compares child c, c+16, ... of the
 // current node; key = distance << 8 | child position, so the row minimum is the first child with the least distance
 // (`d < best_d` strict).  Children of a node are contiguous "slots" (descriptor + node id) in the order the reference
-// appends them.  out[f] = (leaf node id, node id at level nidLevel or 0).
-__global__ void __launch_bounds__(256) k_bow_descend(const uint4* __restrict__ desc, int n, const int* __restrict__ childBegin,
-                                                     const int* __restrict__ childCount, const int* __restrict__ slotNode,
-                                                     const uint4* __restrict__ slotDesc, int nidLevel, int maxDepth,
-                                                     uint2* __restrict__ out) {
-  const int lane16 = threadIdx.x & 15;
-  const int f = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 4);
-  const bool live = f < n;
-  uint4 f0 = make_uint4(0, 0, 0, 0), f1 = f0;
-  if (live) { f0 = desc[2 * (size_t)f]; f1 = desc[2 * (size_t)f + 1]; }
+// appends them.  Returns (leaf node id, node id at level nidLevel or 0).  ONE walk for both launch forms below; every lane
+// of the wave must call it (the DPP reduction needs all 16 lanes of a row, live or not).
+__device__ __forceinline__ uint2 bow_descend_feature(const uint4 f0, const uint4 f1, const bool live, const int lane16,
+                                                     const int* __restrict__ childBegin, const int* __restrict__ childCount,
+                                                     const int* __restrict__ slotNode, const uint4* __restrict__ slotDesc,
+                                                     const int nidLevel, const int maxDepth) {
   int cur = 0;
   unsigned nid = 0;
   bool done = !live;
@@ -142,7 +140,52 @@ __global__ void __launch_bounds__(256) k_bow_descend(const uint4* __restrict__ d
       done = childCount[cur] == 0;
     }
   }
-  if (live && lane16 == 0) out[f] = make_uint2((unsigned)cur, nid);
+  return make_uint2((unsigned)cur, nid);
+}
+
+// out[f] = bow_descend_feature(descriptor f) for the n descriptors of ONE set.
+__global__ void __launch_bounds__(256) k_bow_descend(const uint4* __restrict__ desc, int n, const int* __restrict__ childBegin,
+                                                     const int* __restrict__ childCount, const int* __restrict__ slotNode,
+                                                     const uint4* __restrict__ slotDesc, int nidLevel, int maxDepth,
+                                                     uint2* __restrict__ out) {
+  const int lane16 = threadIdx.x & 15;
+  const int f = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  const bool live = f < n;
+  uint4 f0 = make_uint4(0, 0, 0, 0), f1 = f0;
+  if (live) { f0 = desc[2 * (size_t)f]; f1 = desc[2 * (size_t)f + 1]; }
+  const uint2 r = bow_descend_feature(f0, f1, live, lane16, childBegin, childCount, slotNode, slotDesc, nidLevel, maxDepth);
+  if (live && lane16 == 0) out[f] = r;
+}
+
+// The descent of SEVERAL descriptor sets in one grid (orbfe_bow_transform_batch).  A wave takes four features of ONE set: set s
+// owns the waves [waveStart[s], waveStart[s + 1]) (bow_batch_plan.h; an empty set owns none), so no wave straddles two sets and
+// the last wave of a set is partly idle.  The wave finds its set by a binary search over waveStart -- the index is wave-uniform,
+// so these are scalar loads from a table of a few KB that every wave reads (it stays in the scalar cache) -- then fetches the
+// set's record (row pointer, first output index, size) with one 16-byte scalar load.  The rows of a set lie wherever the caller
+// has them: device memory, page-locked host memory (read in place, once) or the call's upload arena.
+struct BowSetRec { const uint4* rows; uint32_t out0, n; };
+static_assert(sizeof(BowSetRec) == 16, "one 16-byte scalar load");
+__global__ void __launch_bounds__(256) k_bow_descend_batch(const uint32_t* __restrict__ waveStart, const BowSetRec* __restrict__ sets,
+                                                           int nSets, int nWaves, const int* __restrict__ childBegin,
+                                                           const int* __restrict__ childCount, const int* __restrict__ slotNode,
+                                                           const uint4* __restrict__ slotDesc, int nidLevel, int maxDepth,
+                                                           uint2* __restrict__ out) {
+  const int wave = (int)(blockIdx.x * (blockDim.x >> 6)) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave >= nWaves) return;   // whole waves only: the rows of the DPP reduction stay complete
+  int lo = 0, hi = nSets;       // waveStart[lo] <= wave < waveStart[hi]; ends at the one set that owns the wave
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (waveStart[mid] <= (uint32_t)wave) lo = mid;
+    else hi = mid;
+  }
+  const BowSetRec S = sets[lo];
+  const int lane16 = threadIdx.x & 15;
+  const uint32_t f = ((uint32_t)wave - waveStart[lo]) * 4u + ((threadIdx.x & 63u) >> 4);
+  const bool live = f < S.n;
+  uint4 f0 = make_uint4(0, 0, 0, 0), f1 = f0;
+  if (live) { f0 = S.rows[2 * (size_t)f]; f1 = S.rows[2 * (size_t)f + 1]; }
+  const uint2 r = bow_descend_feature(f0, f1, live, lane16, childBegin, childCount, slotNode, slotDesc, nidLevel, maxDepth);
+  if (live && lane16 == 0) out[(size_t)S.out0 + f] = r;
 }
 
 // SearchByBoW inner search: one wave per vocabulary node common to both FeatureVectors.  Frame-1 features of the node
@@ -609,6 +652,8 @@ struct orbfe_vocabulary {
   DevBuf<uint4> d_desc;
   DevBuf<uint2> d_out;
   PinBuf<uint2> h_out;
+  DevBuf<uint8_t> d_batch;        // orbfe_bow_transform_batch: wave offsets, set records and the rows that had to be copied ...
+  PinBuf<uint8_t> h_batch;        // ... and the page-locked image they are uploaded from, in one copy
   hipStream_t stream = nullptr;
 };
 
@@ -824,6 +869,87 @@ int orbfe_bow_transform(orbfe_vocabulary* v, const uint8_t* desc, int n, int in_
 
   return orbfe::bow_assemble(v, v->h_out.p, n, bow_ids, bow_values, n_words, fv_nodes, fv_offsets, fv_features, n_fv_nodes,
                              word_of_feature, node_of_feature);
+}
+
+// transform() for n_sets descriptor sets -- the ComputeBoW loop of a map load (src/Osmap.cpp, rebuild) -- as ONE upload, ONE
+// launch of k_bow_descend_batch over every (set, feature) pair, ONE download and ONE wait; the vectors are then assembled per
+// set by the same host bookkeeping as the single call's.
+int orbfe_bow_transform_batch(orbfe_vocabulary* v, int levelsup, int n_sets, const uint8_t* const* desc, const int* n,
+                              const int* capacity, uint32_t* const* bow_ids, double* const* bow_values, int* n_words,
+                              uint32_t* const* fv_nodes, uint32_t* const* fv_offsets, uint32_t* const* fv_features, int* n_fv_nodes,
+                              uint32_t* const* word_of_feature, uint32_t* const* node_of_feature) {
+  if (!v || n_sets < 0 || (n_sets > 0 && (!desc || !n || !capacity || !bow_ids || !bow_values || !n_words || !fv_nodes || !fv_offsets ||
+                                          !fv_features || !n_fv_nodes))) {
+    set_err("bad argument");
+    return ORBFE_ERR_INVALID;
+  }
+  if (n_sets == 0) return ORBFE_OK;
+  HIP_TRY(hipSetDevice(v->device));
+  // everything that can refuse the call comes first: nothing is written for any set before all sets have passed
+  std::vector<int> where(n_sets, orbfe::kBowRowsHost);
+  for (int s = 0; s < n_sets; s++) {
+    if (n[s] < 0 || capacity[s] < 0 || (n[s] > 0 && !desc[s]) || !bow_ids[s] || !bow_values[s] || !fv_nodes[s] || !fv_offsets[s] || !fv_features[s]) {
+      set_err("bad argument for set %d", s);
+      return ORBFE_ERR_INVALID;
+    }
+    if (n[s] == 0) continue;
+    const int g = orbfe::gpu_readable(desc[s], v->device);
+    if (g < 0 || (g == 2 && ((uintptr_t)desc[s] & 15u) != 0)) {
+      set_err("set %d: descriptor rows in device memory must belong to the vocabulary's device and be 16-byte aligned", s);
+      return ORBFE_ERR_INVALID;
+    }
+    // page-locked rows are read in place too, once per feature; misaligned ones are copied like ordinary memory
+    if (g == 2 || (g == 1 && ((uintptr_t)desc[s] & 15u) == 0)) where[s] = orbfe::kBowRowsInPlace;
+  }
+  orbfe::BowBatchPlan plan;
+  int rc = orbfe::bow_batch_plan(n_sets, n, capacity, where.data(), plan);
+  if (rc == orbfe::kBowBatchOverflow) {
+    if (capacity[plan.failed] < n[plan.failed])
+      set_err("set %d: output capacity %d is below its %d descriptors", plan.failed, capacity[plan.failed], n[plan.failed]);
+    else
+      set_err("set %d: more than %u descriptors in one call", plan.failed, orbfe::kBowBatchMaxFeatures);
+    return ORBFE_ERR_OVERFLOW;
+  }
+  if (rc) { set_err("bad argument for set %d", plan.failed); return ORBFE_ERR_INVALID; }
+  const uint32_t nWaves = plan.waveStart[n_sets], total = plan.out0[n_sets];
+  if (total > 0) {
+    // the upload image: [wave offsets | set records | copied rows], each part 256-byte aligned
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t oSets = al(sizeof(uint32_t) * ((size_t)n_sets + 1)), oRows = oSets + al(sizeof(BowSetRec) * (size_t)n_sets),
+                 bytes = oRows + 32 * (size_t)plan.stagedRows;
+    if ((rc = v->h_batch.ensure(bytes)) || (rc = v->d_batch.ensure(bytes)) || (rc = v->d_out.ensure(total)) || (rc = v->h_out.ensure(total))) return rc;
+    uint8_t* H = v->h_batch.p;
+    memcpy(H, plan.waveStart.data(), sizeof(uint32_t) * ((size_t)n_sets + 1));
+    BowSetRec* rec = reinterpret_cast<BowSetRec*>(H + oSets);
+    for (int s = 0; s < n_sets; s++) {
+      rec[s].out0 = plan.out0[s];
+      rec[s].n = (uint32_t)n[s];
+      if (where[s] == orbfe::kBowRowsInPlace) rec[s].rows = reinterpret_cast<const uint4*>(desc[s]);
+      else {
+        rec[s].rows = reinterpret_cast<const uint4*>(v->d_batch.p + oRows + 32 * (size_t)plan.stageRow[s]);
+        if (n[s]) memcpy(H + oRows + 32 * (size_t)plan.stageRow[s], desc[s], 32 * (size_t)n[s]);
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(v->d_batch.p, H, bytes, hipMemcpyHostToDevice, v->stream));
+    const int nidLevel = v->L - levelsup;   // <= 0: the node is the root (0), TemplatedVocabulary.h:1315-1316
+    hipLaunchKernelGGL(k_bow_descend_batch, dim3((nWaves + 3) / 4), dim3(256), 0, v->stream, (const uint32_t*)v->d_batch.p,
+                       (const BowSetRec*)(v->d_batch.p + oSets), n_sets, (int)nWaves, v->d_childBegin.p, v->d_childCount.p,
+                       v->d_slotNode.p, v->d_slotDesc.p, nidLevel, v->maxDepth, v->d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(v->h_out.p, v->d_out.p, sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+  }
+  for (int s = 0; s < n_sets; s++) {
+    n_words[s] = 0;
+    n_fv_nodes[s] = 0;
+    fv_offsets[s][0] = 0;
+    if (n[s] == 0) continue;
+    if ((rc = orbfe::bow_assemble(v, v->h_out.p + plan.out0[s], n[s], bow_ids[s], bow_values[s], &n_words[s], fv_nodes[s], fv_offsets[s],
+                                  fv_features[s], &n_fv_nodes[s], word_of_feature ? word_of_feature[s] : nullptr,
+                                  node_of_feature ? node_of_feature[s] : nullptr)))
+      return rc;
+  }
+  return ORBFE_OK;
 }
 
 }  // extern "C"

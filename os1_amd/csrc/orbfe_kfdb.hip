@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "bow_batch_plan.h"
 
 namespace orbfe {
 void set_err(const char* fmt, ...);
@@ -365,6 +366,59 @@ int orbfe_kfdb_add(orbfe_kfdb* db, uint64_t key, const uint32_t* words, const do
   db->tail += (size_t)n;
   db->liveEntries += (size_t)n;
   db->nLive++;
+  db->slotsDirty = true;
+  return ORBFE_OK;
+}
+
+// orbfe_kfdb_add for n keyframes (the KeyFrameDatabase::add loop of a map load): every check of every keyframe first
+// (kfdb_batch_plan, bow_batch_plan.h), then at most one compaction, ONE staging image, one copy per pool array and one wait.
+int orbfe_kfdb_add_batch(orbfe_kfdb* db, int n, const uint64_t* keys, const uint32_t* const* words, const double* const* values,
+                         const int* n_words) {
+  if (!db || n < 0 || (n > 0 && (!keys || !words || !values || !n_words))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  std::lock_guard<std::mutex> lock(db->mu);
+  orbfe::KfdbBatchPlan plan;
+  int rc = orbfe::kfdb_batch_plan(n, keys, words, values, n_words, db->nWords, db->nLive, db->capK, db->liveEntries, db->capE, db->tail,
+                                  [&](uint64_t k) { return db->byKey.count(k) != 0; }, plan);
+  if (rc) {
+    const int j = plan.failed;
+    switch (plan.why) {
+      case 1: set_err("entry %d: words must be ascending and below n_words", j); break;
+      case 2: set_err("entry %d: key %llu is already in the database or named twice", j, (unsigned long long)keys[j]); break;
+      case 3: set_err("entry %d: keyframe capacity %d exceeded", j, db->capK); break;
+      case 4: set_err("entry %d: entry capacity %zu exceeded", j, db->capE); break;
+      default: set_err("bad argument for entry %d", j);
+    }
+    return rc;
+  }
+  if (n == 0) return ORBFE_OK;
+  HIP_TRY(hipSetDevice(db->device));
+  if (plan.compactAt >= 0 && (rc = compact(db))) return rc;   // tombstones hold the room: squeeze them out
+  if (plan.total > 0) {
+    const size_t offW = sizeof(double) * plan.total;
+    if ((rc = ensure_stage(db, offW + sizeof(uint32_t) * plan.total))) return rc;
+    size_t at = 0;
+    for (int j = 0; j < n; j++) {
+      const size_t c = (size_t)n_words[j];
+      if (!c) continue;
+      memcpy(db->h_stage + sizeof(double) * at, values[j], sizeof(double) * c);
+      memcpy(db->h_stage + offW + sizeof(uint32_t) * at, words[j], sizeof(uint32_t) * c);
+      at += c;
+    }
+    HIP_TRY(hipMemcpyAsync(db->d_value + db->tail, db->h_stage, offW, hipMemcpyHostToDevice, db->stream));
+    HIP_TRY(hipMemcpyAsync(db->d_word + db->tail, db->h_stage + offW, sizeof(uint32_t) * plan.total, hipMemcpyHostToDevice, db->stream));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+  }
+  for (int j = 0; j < n; j++) {   // the slots, in the order n single adds take them
+    int s;
+    if (!db->freeSlots.empty()) { s = db->freeSlots.back(); db->freeSlots.pop_back(); }
+    else s = db->hiSlot++;
+    Slot& S = db->slots[s];
+    S.key = keys[j]; S.add_seq = db->addSeq++; S.offset = (uint32_t)plan.offset[j]; S.count = (uint32_t)n_words[j]; S.alive = true;
+    db->byKey[keys[j]] = s;
+  }
+  db->tail += plan.total;
+  db->liveEntries += plan.total;
+  db->nLive += n;
   db->slotsDirty = true;
   return ORBFE_OK;
 }
