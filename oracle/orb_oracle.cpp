@@ -1064,7 +1064,9 @@ int orc_search_by_projection_uv(const OrcKeyPoint* kpsUn, const uint8_t* desc, i
       const int dist = descriptor_distance(dMP, desc + 32 * i2);
       if (dist < bestDist) { bestDist = dist; bestIdx2 = (int)i2; }
     }
-    if (bestDist <= max_dist) {
+    // (bestIdx2 < 0: max_dist >= 256 and no candidate below 256 -- the reference would write mvpMapPoints[-1]; no caller of
+    // its passes more than TH_HIGH)
+    if (bestDist <= max_dist && bestIdx2 >= 0) {
       kp_assigned[bestIdx2] = i;
       occ[bestIdx2] = skip_any_occupied ? 1 : ((src_flags[i] & 8) ? 1 : 0);
       nmatches++;

@@ -539,3 +539,78 @@ def test_device_pointers_are_refused_for_host_read_arrays(api, oracle):
                                api._p(m12), C.byref(n))
     assert rc != 0 and b'16-byte aligned' in L.orbfe_last_error()
     L.orbfe_device_free(0, dev)
+
+
+def test_randomised_searches(api, oracle):
+    """tools/sweep_matcher.py's random sweep of the searches on resident frames, as a test: twelve configurations from a fixed
+    seed -- image sizes up to 640 x 480, feature counts, query counts, radii from tracking-sized to image-sized, occupancy
+    densities, claim / skip / chi-square settings, all three search forms -- on frames built from host arrays and from the
+    extractor's arena alternately, bit-exact against the oracle.  (Counterpart of test_randomised_sizes_and_parameters.)"""
+    rng = np.random.default_rng(20240611)
+    m = api.Matcher()
+    kinds, from_extract = set(), 0
+    for done in range(12):
+        # geometries the extractor takes on its GPU-quadtree route by construction (no error is caught anywhere below): between
+        # 1:2 and 7:5, so every level has one to four quadtree roots, and every level holds a 30-pixel FAST cell inside the border
+        W = int(rng.integers(160, 641))
+        H = int(np.clip(rng.integers(120, 481), (W + 1) // 2, min(480, int(1.4 * W))))
+        N = int(rng.choice([60, 300, 1000]))
+        nl = int(rng.integers(2, 9))
+        while min(W, H) / 1.2 ** (nl - 1) < 66:
+            nl -= 1
+        ex = api.Extractor(N, 1.2, nl, 20, 7)
+        k, d = ex(synth(int(rng.integers(1, 10**6)), W, H))
+        assert len(k) > 0
+        b = (float(rng.uniform(-40, 0)), float(W + rng.uniform(0, 40)), float(rng.uniform(-30, 0)), float(H + rng.uniform(0, 30)))
+        if done % 2:
+            fr = api.Frame.from_extract(ex, 0, b)
+            from_extract += 1
+        else:
+            fr = api.Frame.from_host(m, k, d, b)
+        assert len(fr) == len(k)
+        tab = ex.tables()
+        sf = tab['sf']
+        nq = int(rng.choice([1, 17, 400, 3000]))
+        src = rng.integers(0, len(k), nq)
+        qd = d[src].copy()
+        flip = rng.integers(0, 60, nq)
+        for i in range(nq):
+            for bit in rng.integers(0, 256, flip[i]):
+                qd[i, bit >> 3] ^= np.uint8(1 << (bit & 7))
+        spread = float(rng.choice([1.0, 4.0, 30.0]))
+        xy = (np.stack([k['x'][src], k['y'][src]], 1) + rng.normal(0, spread, (nq, 2))).astype(np.float32)
+        lvl = np.clip(k['octave'][src] + rng.integers(-1, 2, nq), 0, nl - 1).astype(np.int32)
+        occ = (rng.random(len(k)) < rng.choice([0.0, 0.05, 0.5])).astype(np.uint8)
+        th = float(rng.choice([1.0, 3.0, 8.0, 40.0]))
+        kind = done % 3                                # (the tool draws the kind; here every kind gets four configurations)
+        what = (done, W, H, N, nl, len(k), nq, th, kind)
+        if kind == 0:
+            vc = rng.uniform(0.9, 1.0, nq).astype(np.float32)
+            fl = np.full(nq, 1 | 8, np.uint8)
+            fl[rng.random(nq) < 0.1] &= ~np.uint8(8)
+            fl[rng.random(nq) < 0.05] |= 2
+            fl[rng.random(nq) < 0.05] |= 4
+            ratio = float(rng.choice([0.6, 0.8, 0.95]))
+            g = m.search_by_projection(fr, None, None, sf, occ, xy, lvl, vc, fl, qd, th, ratio)
+            w = oracle.search_by_projection(k, d, b, sf, occ, xy, lvl, vc, fl, qd, th, ratio)
+            assert g[0] == w[0] and (g[1] == w[1]).all(), what
+        elif kind == 1:
+            ang = rng.uniform(0, 360, nq).astype(np.float32)
+            fl = np.where(rng.random(nq) < 0.8, 8, 0).astype(np.uint8)
+            va = (rng.random(nq) < 0.9).astype(np.uint8)
+            maxd, skip_any, ori = int(rng.choice([50, 100])), int(rng.integers(0, 2)), bool(rng.integers(0, 2))
+            g = m.search_by_projection_uv(fr, None, None, sf, occ, xy, lvl, ang, fl, va, qd, th, maxd, skip_any, ori)
+            w = oracle.search_by_projection_uv(k, d, b, sf, occ, xy, lvl, ang, fl, va, qd, th, maxd, skip_any, ori)
+            assert g[0] == w[0] and (g[1] == w[1]).all(), what
+        else:
+            va = (rng.random(nq) < 0.9).astype(np.uint8)
+            rad = (th * sf[lvl]).astype(np.float32)
+            claim, gate = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+            skip = occ if rng.random() < 0.5 else None
+            maxd = int(rng.choice([50, 100]))
+            g = m.search_projected(fr, None, None, xy, rad, lvl, va, qd, skip, claim, tab['is2'] if gate else None, 5.99, maxd)
+            w = oracle.search_projected(k, d, b, xy, rad, lvl, va, qd, skip, claim, tab['is2'] if gate else None, 5.99, maxd)
+            assert g[0] == w[0] and g[1].tobytes() == w[1].tobytes() and g[2].tobytes() == w[2].tobytes(), what
+        kinds.add(kind)
+        fr.close()
+    assert kinds == {0, 1, 2} and from_extract == 6
