@@ -647,14 +647,20 @@ def rot_bin32(a1, a2):
     return 0 if b == 30 else b
 
 
+# counts per bin: bin b is produced by a query angle of 30 b against a keypoint angle of 0
+HIST_COUNTS = [('only_30', [30], [0]), ('10_1_keeps_small', [10, 1], [0, 1]), ('11_1_drops_small', [11, 1], [0]), ('30_3_keeps_small', [30, 3], [0, 1]),
+          ('31_3_drops_small', [31, 3], [0]), ('10_5_1_keeps_third', [10, 5, 1], [0, 1, 2]), ('11_5_1_drops_third', [11, 5, 1], [0, 1]),
+          ('two_equal_top_bins', [7, 7], [0, 1]), ('four_equal_bins_highest_index_loses', [4, 4, 4, 4], [0, 1, 2]),
+          ('5_5_5_4_drops_fourth', [5, 5, 5, 4], [0, 1, 2]), ('10_1_small_bin_first', [0, 1, 10], [1, 2]),
+          ('four_equal_bins_descending_later', [0, 3, 4, 4, 4, 4], [2, 3, 4])]
+# bin edges: three bins of three matches each; the probe (last match) survives only if it falls into the bin stated
+ROT_PROBES = [('diff_0_bin_0', 0.0, 0.0, 0), ('diff_15_bin_1', 15.0, 0.0, 1), ('diff_45_bin_2', 45.0, 0.0, 2), ('diff_345_bin_12', 345.0, 0.0, 12),
+          ('diff_359p99_bin_12', 359.99, 0.0, 12), ('negative_wraps_to_bin_11', 10.0, 40.0, 11), ('negative_small_wraps_to_bin_12', 0.0, 0.01, 12),
+          ('minus_zero_bin_0', -0.0, 0.0, 0), ('diff_14p99_bin_0', 14.99, 0.0, 0)]
+
+
 def _family_g():
-    # counts per bin: bin b is produced by a query angle of 30 b against a keypoint angle of 0
-    counts = [('only_30', [30], [0]), ('10_1_keeps_small', [10, 1], [0, 1]), ('11_1_drops_small', [11, 1], [0]), ('30_3_keeps_small', [30, 3], [0, 1]),
-              ('31_3_drops_small', [31, 3], [0]), ('10_5_1_keeps_third', [10, 5, 1], [0, 1, 2]), ('11_5_1_drops_third', [11, 5, 1], [0, 1]),
-              ('two_equal_top_bins', [7, 7], [0, 1]), ('four_equal_bins_highest_index_loses', [4, 4, 4, 4], [0, 1, 2]),
-              ('5_5_5_4_drops_fourth', [5, 5, 5, 4], [0, 1, 2]), ('10_1_small_bin_first', [0, 1, 10], [1, 2]),
-              ('four_equal_bins_descending_later', [0, 3, 4, 4, 4, 4], [2, 3, 4])]
-    for tag, cnt, kept_bins in counts:
+    for tag, cnt, kept_bins in HIST_COUNTS:
         matches, keep = [], []
         for b, c in enumerate(cnt):
             for _ in range(c):
@@ -675,11 +681,7 @@ def _family_g():
     five = [(0.0, 0.0), (30.0, 0.0), (60.0, 0.0), (90.0, 0.0), (120.0, 0.0)]     # complement rows: distance 256, nothing is accepted
     _hist_scene('histogram_no_match_at_all_uv', five, [], True, False, lambda: hamming(row(0), row(256)) == 256, 256)
     _hist_scene('histogram_no_match_at_all_init', five, [], True, True, lambda: hamming(row(0), row(256)) == 256, 256)
-    # bin edges: three bins of three matches each; the probe (last match) survives only if it falls into the bin stated
-    probes = [('diff_0_bin_0', 0.0, 0.0, 0), ('diff_15_bin_1', 15.0, 0.0, 1), ('diff_45_bin_2', 45.0, 0.0, 2), ('diff_345_bin_12', 345.0, 0.0, 12),
-              ('diff_359p99_bin_12', 359.99, 0.0, 12), ('negative_wraps_to_bin_11', 10.0, 40.0, 11), ('negative_small_wraps_to_bin_12', 0.0, 0.01, 12),
-              ('minus_zero_bin_0', -0.0, 0.0, 0), ('diff_14p99_bin_0', 14.99, 0.0, 0)]
-    for tag, a1, a2, want_bin in probes:
+    for tag, a1, a2, want_bin in ROT_PROBES:
         others = [b for b in (4, 8, 6) if b != want_bin][:2]
         matches = []
         for b in [want_bin] + others:

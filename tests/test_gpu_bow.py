@@ -342,3 +342,66 @@ def test_vocabulary_image_with_the_reference_loaders_trailing_duplicate(api, ora
         _same_transform(v.transform(d, lu), want)
         _same_transform(vd.transform(d, lu), want)
     v.close(); vd.close()
+
+
+def test_tie_dense_sweep_of_the_bow_guided_searches(api, oracle, monkeypatch):
+    """Twelve seeded configurations against the oracle, all three searches, both routes.  Descriptors are row(n) of the boundary
+    scenes, n uniform in 0 ... 70: every distance is a small integer, ties are everywhere and a third of all pairs lie within 2 of
+    TH_LOW.  Node sizes come from {1, 8, 63, 64, 65, 255, 256, 257, 300, 2 049}; valid / has-no-MapPoint flags at 0.8.  For
+    SearchForTriangulation the keypoints lie on a quarter-pixel lattice scaled by the octave's scale factor, F12 = [t]x with
+    t = (1, 0, 0) (dsqr = (y2 - y1)^2) and the epipole is inside the image.  Every configuration produces at least one match in each of the three searches; over all twelve
+    there is an accepted SearchByBoW match at distance exactly 50 and a SearchForTriangulation tie resolved: a match that has an
+    equally distant candidate without MapPoint, passing both gates, EARLIER in its node's list."""
+    from bow_boundary_util import S2, desc_rows
+    from search_boundary_util import F32, SF, hamming, make_kps
+    m = api.Matcher()
+    sizes = [1, 8, 63, 64, 65, 255, 256, 257, 300, 2049]
+    ratios = [0.6, 0.7, 0.75, 0.9, 1.0]
+    at50 = ties = 0
+    F12 = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)
+    for seed in range(12):
+        rng = np.random.default_rng(5000 + seed)
+        nn = 30                # 24 nodes of 1 or 8 features per side (lone candidates: where a best distance of exactly 50 survives), 5 of any size, a last one
+        s1 = [sizes[j] for j in rng.integers(0, 2, 24)] + [sizes[j] for j in rng.integers(0, 9, 5)] + [2049 if seed % 3 == 0 else 300]
+        s2 = [sizes[j] for j in rng.integers(0, 2, 24)] + [sizes[j] for j in rng.integers(0, 9, 5)] + [2049 if seed % 3 == 1 else 257]
+        n1, n2 = sum(s1), sum(s2)
+        fv1 = (np.arange(nn, dtype=np.uint32) * 3, np.concatenate([[0], np.cumsum(s1)]).astype(np.uint32), np.arange(n1, dtype=np.uint32))
+        fv2 = (np.arange(nn, dtype=np.uint32) * 3, np.concatenate([[0], np.cumsum(s2)]).astype(np.uint32), np.arange(n2, dtype=np.uint32))
+        c1, c2 = rng.integers(0, 71, n1), rng.integers(0, 71, n2)
+        d1, d2 = desc_rows(c1), desc_rows(c2)
+        f1, f2 = (rng.random(n1) < 0.8).astype(np.uint8), (rng.random(n2) < 0.8).astype(np.uint8)
+        o1, o2 = rng.integers(0, 8, n1), rng.integers(0, 8, n2)
+        k1 = make_kps([(F32(rng.integers(0, 2560) / 4) * SF[o], F32(rng.integers(400, 412) / 4) * SF[o], o, float(rng.integers(0, 360))) for o in o1])
+        k2 = make_kps([(F32(rng.integers(0, 2560) / 4) * SF[o], F32(rng.integers(400, 412) / 4) * SF[o], o, float(rng.integers(0, 360))) for o in o2])
+        ex, ey = float(F32(rng.integers(0, 2560) / 4)), float(F32(rng.integers(400, 1200) / 4))
+        ratio, ori = ratios[seed % 5], bool(seed & 1)
+        per_kind = {}          # matches on the default route, per search
+        for zc in (None, '0'):
+            if zc:
+                monkeypatch.setenv('ORBFE_BOW_ZEROCOPY', zc)
+            for valid2, strict in [(None, False), (f2, True)]:
+                got = m.search_by_bow(d1, k1['angle'], f1, fv1, d2, k2['angle'], valid2, fv2, ratio, ori, strict)
+                want = oracle.search_by_bow(d1, k1['angle'], f1, fv1, d2, k2['angle'], valid2, fv2, ratio, ori)
+                assert got[0] == want[0] and got[1].tobytes() == want[1].tobytes(), (seed, zc, strict)
+                if not zc:
+                    per_kind['kf_kf' if strict else 'kf_frame'] = got[0]
+                if not strict and not zc:
+                    at50 += sum(1 for i, j in enumerate(want[1]) if j >= 0 and abs(int(c1[i]) - int(c2[j])) == 50 and hamming(d1[i], d2[j]) == 50)
+            h1, h2 = (1 - f1).astype(np.uint8), (1 - f2).astype(np.uint8)
+            got = m.search_for_triangulation(k1, d1, h1, fv1, k2, d2, h2, fv2, F12, ex, ey, SF, S2, ori)
+            want = oracle.search_for_triangulation(k1, d1, h1, fv1, k2, d2, h2, fv2, F12, ex, ey, SF, S2, ori)
+            assert got[0] == want[0] and got[1].tobytes() == want[1].tobytes(), (seed, zc, 'tri')
+            if not zc:
+                per_kind['tri'] = got[0]
+            if zc:
+                monkeypatch.delenv('ORBFE_BOW_ZEROCOPY')
+                continue
+            node_of2 = np.repeat(np.arange(nn), s2)
+            for i, j in want[1]:
+                dx, dy = F32(ex) - k2['x'], F32(ey) - k2['y']
+                dl = k2['y'] - k1['y'][i]
+                ok = (h2 == 0) & (node_of2 == node_of2[j]) & (np.arange(n2) < j) & (np.abs(c2 - c1[i]) == abs(int(c2[j]) - int(c1[i]))) \
+                    & ~(dx * dx + dy * dy < F32(100) * SF[k2['octave']]) & ((dl * dl).astype(np.float64) < 3.84 * S2[k2['octave']].astype(np.float64))
+                ties += int(ok.any())
+        assert len(per_kind) == 3 and all(v >= 1 for v in per_kind.values()), (seed, per_kind)
+    assert at50 >= 1 and ties >= 1, (at50, ties)
