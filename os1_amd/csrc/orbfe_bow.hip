@@ -13,22 +13,23 @@
 // (double, so the order is part of the result), the L1/L2 normalisation in ascending word order, grouping feature
 // indices by node, and the rotation-histogram pruning.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <mutex>
-#include <chrono>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
+#include <mutex>
 #include <vector>
 
 #include "../../include/orbfe.h"
 #include "bow_batch_plan.h"
+#include "hip_buffers.h"
 
 namespace orbfe {
-void set_err(const char* fmt, ...);
 int gpu_readable(const void* p, int device);   // orbfe_frame.hip: 0 ordinary host memory, 1 page-locked, 2 this device's, -1 another's
 int matcher_device(const orbfe_matcher* m);
 hipStream_t matcher_stream(const orbfe_matcher* m);
@@ -36,53 +37,11 @@ std::shared_ptr<void>& matcher_bow_slot(orbfe_matcher* m);
 }
 using orbfe::set_err;
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return ORBFE_ERR_HIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
 namespace {
 
 constexpr int TH_LOW = 50, HISTO_LENGTH = 30;   // ORBmatcher.cc:37-39
 constexpr int kRecord = 45;                     // bytes per node record of the binary vocabulary file
 constexpr int kMaxGroup = 65535;                // SearchByBoW: features of one frame under one vocabulary node
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n) return ORBFE_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-    n = count;
-    return ORBFE_OK;
-  }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n) return ORBFE_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-    // Coherent (fine-grained, uncached on the GPU side) EXPLICITLY: kernels store results and completion words here and the
-    // host polls them while the kernel runs; with hipHostMallocDefault that property would hang on HIP_HOST_COHERENT.
-    HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocCoherent));
-    n = count;
-    return ORBFE_OK;
-  }
-  ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
 
 // row_ror:n -- rotate right by n lanes inside each row of 16 lanes
 template <int N>
@@ -186,6 +145,19 @@ __global__ void __launch_bounds__(256) k_bow_descend_batch(const uint32_t* __res
   if (live) { f0 = S.rows[2 * (size_t)f]; f1 = S.rows[2 * (size_t)f + 1]; }
   const uint2 r = bow_descend_feature(f0, f1, live, lane16, childBegin, childCount, slotNode, slotDesc, nidLevel, maxDepth);
   if (live && lane16 == 0) out[(size_t)S.out0 + f] = r;
+}
+
+// Completion word (the route without copy commands: inputs read from, matches written to page-locked host memory).  Called by
+// ONE thread of a block once the block's stores are acknowledged (s_waitcnt vmcnt(0); each kernel has its own lead-in): the
+// block counts itself off, the last one resets the counter and writes the call's number for the polling host.
+// Why an acknowledgement wait is enough for the blocks that are not last: matches12 / host live in COHERENT page-locked
+// memory (PinBuf: hipHostMallocCoherent), which the GPU maps uncached -- a store that has been acknowledged (vmcnt 0) has
+// left every XCD's L2 and is visible to the host; the counter only orders "all blocks got that far" before the flag.
+__device__ __forceinline__ void signal_last_block(unsigned* counter, int* host, int seq) {
+  if (atomicAdd(counter, 1u) != gridDim.x - 1u) return;
+  *counter = 0u;
+  __threadfence_system();
+  __hip_atomic_store(host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // SearchByBoW inner search: one wave per vocabulary node common to both FeatureVectors.  Frame-1 features of the node
@@ -306,18 +278,10 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_match(const uint4* __restri
   const int n1g = P.e1 - P.b1, n2g = P.e2 - P.b2;
   for (int i = tid; i < (n2g + 31) / 32; i += kBowThreads) matched[i] = 0;
   const bool inLds = n1g <= kBowSide && n2g <= kBowSide;
-  // completion word (the route without copy commands: inputs read from, matches written to page-locked host memory): the
-  // block's stores are acknowledged, it counts itself off, the last one writes the call's number for the polling host.
-  // Why an acknowledgement wait is enough for the blocks that are not last: matches12 / doneHost live in COHERENT page-locked
-  // memory (PinBuf: hipHostMallocCoherent), which the GPU maps uncached -- a store that has been acknowledged (vmcnt 0) has
-  // left every XCD's L2 and is visible to the host; the counter only orders "all blocks got that far" before the flag.
-  auto done = [&]() {
+  auto done = [&]() {   // (no barrier here: waves 1-3 of a large node retire early)
     if (!doneCounter || tid != 0) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (atomicAdd(doneCounter, 1u) != gridDim.x - 1u) return;
-    *doneCounter = 0u;
-    __threadfence_system();
-    __hip_atomic_store(doneHost, doneSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    signal_last_block(doneCounter, doneHost, doneSeq);
   };
   if (inLds) {
     // the node's feature lists and descriptors first -- the walk below must not chase global pointers: every dependent
@@ -408,8 +372,8 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_match(const uint4* __restri
   // without a MapPoint has an all-empty list -- k_bow_topk wrote it -- and decides "no match" by itself.)
   if (tid >= 64) { done(); return; }
   const uint32_t* tkRows = topk + (size_t)P.tk * kBowTopK;
-  uint16_t* sel = dmat;   // [n1g] winner position + 1, 0 = none (n1g <= kMaxGroup < 2^16; dmat is free on this path: 12 288 entries ...
-  int32_t* selBig = nullptr;   // ... larger nodes keep the winners in matches12 itself, as positions, and translate in place)
+  uint16_t* sel = dmat;   // [n1g] winner position + 1, 0 = none (n1g <= kMaxGroup < 2^16; dmat is free on this path: 12 288 entries;
+                          // larger nodes write matches12 as they go)
   const bool selInLds = n1g <= kBowMatrix;
   for (int i = lane; i < n1g && selInLds; i += 64) sel[i] = 0;
   unsigned keyN = (lane >> 3) < n1g ? tkRows[lane] : 0xffffffffu;   // keys of the first group
@@ -521,7 +485,6 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_match(const uint4* __restri
       const unsigned w = sel[i];
       if (w) matches12[(unsigned)P.base1 + feat1[P.b1 + i]] = (int32_t)feat2[P.b2 + (int)w - 1];
     }
-  (void)selBig;
   done();
 }
 
@@ -534,6 +497,28 @@ struct TriParams {
   float ex, ey;
   float scale2[16], sigma2[16];
 };
+
+// epipolar line in image 2, l = x1' F12 (ORBmatcher.cc:138-140), and the squared length of its normal
+__device__ __forceinline__ void epipolar_line(float x1, float y1, const TriParams& T, float* la, float* lb, float* lc, float* den) {
+  *la = x1 * T.F12[0] + y1 * T.F12[3] + T.F12[6];
+  *lb = x1 * T.F12[1] + y1 * T.F12[4] + T.F12[7];
+  *lc = x1 * T.F12[2] + y1 * T.F12[5] + T.F12[8];
+  *den = *la * *la + *lb * *lb;
+}
+// The reference's test of ONE frame-2 candidate (ORBmatcher.cc:720-740, CheckDistEpipolarLine :135-152), in its order: TH_LOW,
+// the distance from the epipole, the distance from the epipolar line.  Returns the candidate's key (p = position in the node's
+// frame-2 list; the LAST one wins a tie), or 0xffffffff: skip.
+__device__ __forceinline__ unsigned tri_candidate_key(int dist, float x2, float y2, int oct, int p, float la, float lb, float lc,
+                                                      float den, const TriParams& T) {
+  if (dist > TH_LOW) return 0xffffffffu;
+  const float distex = T.ex - x2, distey = T.ey - y2;
+  if (distex * distex + distey * distey < 100 * T.scale2[oct]) return 0xffffffffu;
+  const float num = la * x2 + lb * y2 + lc;
+  if (den == 0) return 0xffffffffu;
+  const float dsqr = num * num / den;
+  if (!((double)dsqr < 3.84 * (double)T.sigma2[oct])) return 0xffffffffu;
+  return ((unsigned)dist << 16) | (0xffffu - (unsigned)p);
+}
 
 // Round 3: a block of four waves per node.  Both feature lists with their flags, descriptors and keypoint coordinates are
 // fetched once into LDS (nodes of up to kBowSide features per side; from the page-locked arena directly on the route
@@ -556,11 +541,7 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyP
   auto done = [&]() {   // (every wave's stores are acknowledged before the block counts itself off)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (!doneCounter || tid != 0) return;
-    if (atomicAdd(doneCounter, 1u) != gridDim.x - 1u) return;
-    *doneCounter = 0u;
-    __threadfence_system();
-    __hip_atomic_store(doneHost, doneSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (doneCounter && tid == 0) signal_last_block(doneCounter, doneHost, doneSeq);
   };
   if (n1g <= kBowSide && n2g <= kBowSide) {
     for (int i = tid; i < n1g; i += kBowThreads) {
@@ -581,25 +562,13 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyP
       if (idx1 & 0x80000000u) continue;   // wave-uniform
       const uint4 a0 = d1s[2 * r], a1 = d1s[2 * r + 1];
       const float x1 = x1s[r], y1 = y1s[r];
-      // epipolar line in image 2, l = x1' F12 (ORBmatcher.cc:138-140)
-      const float la = x1 * T.F12[0] + y1 * T.F12[3] + T.F12[6];
-      const float lb = x1 * T.F12[1] + y1 * T.F12[4] + T.F12[7];
-      const float lc = x1 * T.F12[2] + y1 * T.F12[5] + T.F12[8];
-      const float den = la * la + lb * lb;
+      float la, lb, lc, den;
+      epipolar_line(x1, y1, T, &la, &lb, &lc, &den);
       unsigned key = 0xffffffffu;
       for (int p = lane; p < n2g; p += 64) {
         if (row2[p] & 0x80000000u) continue;
         const int dist = hamming256(a0, a1, d2s[2 * p], d2s[2 * p + 1]);
-        if (dist > TH_LOW) continue;
-        const float x2 = x2s[p], y2 = y2s[p];
-        const int oct = o2s[p];
-        const float distex = T.ex - x2, distey = T.ey - y2;
-        if (distex * distex + distey * distey < 100 * T.scale2[oct]) continue;
-        const float num = la * x2 + lb * y2 + lc;
-        if (den == 0) continue;
-        const float dsqr = num * num / den;
-        if (!((double)dsqr < 3.84 * (double)T.sigma2[oct])) continue;
-        key = min(key, ((unsigned)dist << 16) | (0xffffu - (unsigned)p));
+        key = min(key, tri_candidate_key(dist, x2s[p], y2s[p], o2s[p], p, la, lb, lc, den, T));
       }
       key = wave_min(key);
       if (key != 0xffffffffu && lane == 0) matches12[idx1] = (int32_t)row2[(int)(0xffffu - (key & 0xffffu))];
@@ -613,25 +582,14 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyP
       if (hasMP1[idx1]) continue;   // wave-uniform
       const uint4 a0 = desc1[2 * (size_t)idx1], a1 = desc1[2 * (size_t)idx1 + 1];
       const float x1 = kps1[idx1].x, y1 = kps1[idx1].y;
-      const float la = x1 * T.F12[0] + y1 * T.F12[3] + T.F12[6];
-      const float lb = x1 * T.F12[1] + y1 * T.F12[4] + T.F12[7];
-      const float lc = x1 * T.F12[2] + y1 * T.F12[5] + T.F12[8];
-      const float den = la * la + lb * lb;
+      float la, lb, lc, den;
+      epipolar_line(x1, y1, T, &la, &lb, &lc, &den);
       unsigned key = 0xffffffffu;
       for (int p = lane; p < n2g; p += 64) {
         const unsigned idx2 = feat2[P.b2 + p];
         if (hasMP2[idx2]) continue;
         const int dist = hamming256(a0, a1, desc2[2 * (size_t)idx2], desc2[2 * (size_t)idx2 + 1]);
-        if (dist > TH_LOW) continue;
-        const float x2 = kps2[idx2].x, y2 = kps2[idx2].y;
-        const int oct = kps2[idx2].octave;
-        const float distex = T.ex - x2, distey = T.ey - y2;
-        if (distex * distex + distey * distey < 100 * T.scale2[oct]) continue;
-        const float num = la * x2 + lb * y2 + lc;
-        if (den == 0) continue;
-        const float dsqr = num * num / den;
-        if (!((double)dsqr < 3.84 * (double)T.sigma2[oct])) continue;
-        key = min(key, ((unsigned)dist << 16) | (0xffffu - (unsigned)p));
+        key = min(key, tri_candidate_key(dist, kps2[idx2].x, kps2[idx2].y, kps2[idx2].octave, p, la, lb, lc, den, T));
       }
       key = wave_min(key);
       if (key != 0xffffffffu && lane == 0) matches12[idx1] = (int32_t)feat2[P.b2 + (int)(0xffffu - (key & 0xffffu))];
@@ -914,7 +872,6 @@ int orbfe_bow_transform_batch(orbfe_vocabulary* v, int levelsup, int n_sets, con
   const uint32_t nWaves = plan.waveStart[n_sets], total = plan.out0[n_sets];
   if (total > 0) {
     // the upload image: [wave offsets | set records | copied rows], each part 256-byte aligned
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t oSets = al(sizeof(uint32_t) * ((size_t)n_sets + 1)), oRows = oSets + al(sizeof(BowSetRec) * (size_t)n_sets),
                  bytes = oRows + 32 * (size_t)plan.stagedRows;
     if ((rc = v->h_batch.ensure(bytes)) || (rc = v->d_batch.ensure(bytes)) || (rc = v->d_out.ensure(total)) || (rc = v->h_out.ensure(total))) return rc;
@@ -973,21 +930,90 @@ void three_maxima(const int* count, int L, int& ind1, int& ind2, int& ind3) {
 }
 
 struct BowScratch {
-  DevBuf<uint4> d_desc1, d_desc2;
-  DevBuf<uint8_t> d_valid1, d_valid2;
-  DevBuf<uint32_t> d_feat1, d_feat2;
-  DevBuf<BowPair> d_pairs;
   DevBuf<int32_t> d_m12;
   PinBuf<int32_t> h_m12;
-  DevBuf<OrbfeKeyPoint> d_kps1, d_kps2;
-  DevBuf<uint8_t> d_arena;    // batched search: everything that goes up in one copy
-  PinBuf<uint8_t> h_arena;
+  DevBuf<uint8_t> d_arena;    // everything a search reads, uploaded in one copy ...
+  PinBuf<uint8_t> h_arena;    // ... from this image, or read here in place
   DevBuf<uint32_t> d_topk;    // large nodes: kBowTopK least keys per frame-1 feature (k_bow_topk)
   DevBuf<TopkItem> d_items;
   DevBuf<unsigned> d_done;    // route without copy commands: block counter, the call's number (page-locked)
   PinBuf<int> h_done;
   int seq = 0;
 };
+
+// One call of a vocabulary-guided search (SearchByBoW, SearchForTriangulation): everything the kernel reads goes into ONE
+// page-locked arena (a copy command per array from ordinary memory, about 12 us each, was half of a call), and the arena
+// takes one of two routes.  Nodes whose two feature lists fit the kernel's LDS (up to kBowSide features per side: every node
+// of a real vocabulary at levelsup 4) are read ONCE per feature, so the kernel reads the arena where it is and writes the
+// matches into page-locked memory: no copy command, no fill, and the host polls the kernel's completion word instead of
+// waiting on the stream.  ORBFE_BOW_ZEROCOPY=0, or a larger node: upload, fill, launch, download, wait.
+struct BowCall {
+  BowScratch* S = nullptr;
+  hipStream_t st = nullptr;
+  std::vector<size_t> off;   // where each part of the arena starts (256-byte aligned); the last entry is the arena's size
+  size_t rows = 0;           // entries of matches12
+  bool zerocopy = false;
+
+  // parts: bytes of each array of the arena, in order; the caller fills them at host(i) and then submits
+  int open(orbfe_matcher* m, std::initializer_list<size_t> parts, size_t nRows, const std::vector<BowPair>& pairs) {
+    HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
+    std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
+    if (!slot) slot = std::make_shared<BowScratch>();
+    S = static_cast<BowScratch*>(slot.get());
+    st = orbfe::matcher_stream(m);
+    rows = nRows;
+    off.assign(1, 0);
+    for (const size_t bytes : parts) off.push_back(off.back() + al(bytes));
+    int rc;
+    if ((rc = S->h_arena.ensure(off.back())) || (rc = S->d_arena.ensure(off.back())) || (rc = S->d_m12.ensure(rows)) || (rc = S->h_m12.ensure(rows))) return rc;
+    bool small = true;
+    for (const BowPair& p : pairs) small = small && p.e1 - p.b1 <= kBowSide && p.e2 - p.b2 <= kBowSide;
+    const char* zce = getenv("ORBFE_BOW_ZEROCOPY");   // (read per call: the parity tests run both routes in one process)
+    zerocopy = small && !(zce && atoi(zce) == 0);
+    return ORBFE_OK;
+  }
+  uint8_t* host(int part) const { return S->h_arena.p + off[part]; }
+  template <class T>
+  const T* at(const uint8_t* base, int part) const { return reinterpret_cast<const T*>(base + off[part]); }   // part of the arena at `base`
+
+  // launch(base, matches12, doneCounter, doneHost, doneSeq) issues the search kernel on `st`: base is the arena as the kernel
+  // sees it.  before(base) runs on the upload route only, between the arena's upload and the search.  Afterwards the
+  // matches are in S->h_m12.
+  template <class Launch, class Before>
+  int submit(Launch launch, Before before) {
+    int rc;
+    if (zerocopy) {
+      if (!S->d_done.p) {
+        if ((rc = S->d_done.ensure(16)) || (rc = S->h_done.ensure(16))) return rc;
+        HIP_TRY(hipMemsetAsync(S->d_done.p, 0, 16 * sizeof(unsigned), st));
+        S->h_done.p[0] = 0;
+      }
+      memset(S->h_m12.p, 0xff, sizeof(int32_t) * rows);
+      S->seq = S->seq == INT_MAX ? 1 : S->seq + 1;
+      launch(S->h_arena.p, S->h_m12.p, S->d_done.p, S->h_done.p, S->seq);
+      HIP_TRY(hipGetLastError());
+      return wait_for_word(S->h_done.p, S->seq, st);
+    }
+    uint8_t* D = S->d_arena.p;
+    HIP_TRY(hipMemcpyAsync(D, S->h_arena.p, off.back(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(S->d_m12.p, 0xff, sizeof(int32_t) * rows, st));
+    if ((rc = before(D))) return rc;
+    launch(D, S->d_m12.p, (unsigned*)nullptr, (int*)nullptr, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S->h_m12.p, S->d_m12.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return ORBFE_OK;
+  }
+  template <class Launch>
+  int submit(Launch launch) { return submit(launch, [](uint8_t*) { return ORBFE_OK; }); }
+};
+
+// which: "fv1" / "fv2"
+int check_features(const char* which, const uint32_t* features, int nf, int n) {
+  for (int i = 0; i < nf; i++)
+    if (features[i] >= (uint32_t)n) { set_err("%s feature index out of range", which); return ORBFE_ERR_INVALID; }
+  return ORBFE_OK;
+}
 
 // common vocabulary nodes of two FeatureVectors (the lower_bound zig-zag of ORBmatcher.cc:175-258 visits exactly the
 // intersection, in ascending order) as feature ranges
@@ -1033,7 +1059,6 @@ int prune_by_orientation(const float* angle1, size_t stride1, const float* angle
   return removed;
 }
 
-
 }  // namespace
 
 // int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, ...) for SEVERAL keyframes against one frame -- the loop of
@@ -1056,10 +1081,10 @@ static int bow_batch_core(orbfe_matcher* m, int n_kf, const uint8_t* const* desc
     return ORBFE_ERR_INVALID;
   }
   const int nf2 = n_fv2 ? (int)fv2_offsets[n_fv2] : 0;
-  for (int i = 0; i < nf2; i++) if (fv2_features[i] >= (uint32_t)n2) { set_err("fv2 feature index out of range"); return ORBFE_ERR_INVALID; }
+  int rc;
+  if ((rc = check_features("fv2", fv2_features, nf2, n2))) return rc;
   std::vector<BowPair> pairs, all;
   std::vector<size_t> rowBase(n_kf + 1, 0), featBase(n_kf + 1, 0);
-  int rc;
   for (int k = 0; k < n_kf; k++) {
     nmatches[k] = 0;
     if (n1[k] < 0 || n_fv1[k] < 0 || (n1[k] > 0 && (!desc1[k] || !valid1[k] || !matches12[k])) ||
@@ -1069,7 +1094,7 @@ static int bow_batch_core(orbfe_matcher* m, int n_kf, const uint8_t* const* desc
     }
     for (int i = 0; i < n1[k]; i++) matches12[k][i] = -1;
     const int nf1 = n_fv1[k] ? (int)fv1_offsets[k][n_fv1[k]] : 0;
-    for (int i = 0; i < nf1; i++) if (fv1_features[k][i] >= (uint32_t)n1[k]) { set_err("fv1 feature index out of range"); return ORBFE_ERR_INVALID; }
+    if ((rc = check_features("fv1", fv1_features[k], nf1, n1[k]))) return rc;
     if ((rc = common_nodes(fv1_nodes[k], fv1_offsets[k], n_fv1[k], fv2_nodes, fv2_offsets, n_fv2, pairs))) return rc;
     for (BowPair p : pairs) {
       p.b1 += (int)featBase[k]; p.e1 += (int)featBase[k]; p.base1 = (int)rowBase[k];
@@ -1093,90 +1118,53 @@ static int bow_batch_core(orbfe_matcher* m, int n_kf, const uint8_t* const* desc
     for (int r = 0; r < n1g; r += kTopkRows) items.push_back(TopkItem{(int)i, r});
   }
   const size_t rows1 = rowBase[n_kf], feats1 = featBase[n_kf];
-  HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
-  std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
-  if (!slot) slot = std::make_shared<BowScratch>();
-  BowScratch* S = static_cast<BowScratch*>(slot.get());
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t oD1 = 0, oD2 = oD1 + al(32 * rows1), oV1 = oD2 + al(32 * (size_t)n2), oV2 = oV1 + al(rows1), oF1 = oV2 + al((size_t)std::max(n2, 1)),
-               oF2 = oF1 + al(4 * feats1), oP = oF2 + al(4 * (size_t)nf2), total = oP + al(sizeof(BowPair) * all.size());
-  if ((rc = S->h_arena.ensure(total)) || (rc = S->d_arena.ensure(total)) || (rc = S->d_m12.ensure(rows1)) || (rc = S->h_m12.ensure(rows1))) return rc;
-  uint8_t* H = S->h_arena.p;
+  enum { D1, D2, V1, V2, F1, F2, P };   // the arena's parts
+  BowCall C;
+  if ((rc = C.open(m, {32 * rows1, 32 * (size_t)n2, rows1, (size_t)std::max(n2, 1), 4 * feats1, 4 * (size_t)nf2, sizeof(BowPair) * all.size()}, rows1, all)))
+    return rc;
+  BowScratch* S = C.S;
   for (int k = 0; k < n_kf; k++) {
     if (n1[k]) {
-      if (!dev1) memcpy(H + oD1 + 32 * rowBase[k], desc1[k], 32 * (size_t)n1[k]);
-      memcpy(H + oV1 + rowBase[k], valid1[k], (size_t)n1[k]);
+      if (!dev1) memcpy(C.host(D1) + 32 * rowBase[k], desc1[k], 32 * (size_t)n1[k]);
+      memcpy(C.host(V1) + rowBase[k], valid1[k], (size_t)n1[k]);
     }
     const size_t nf1 = featBase[k + 1] - featBase[k];
-    if (nf1) memcpy(H + oF1 + 4 * featBase[k], fv1_features[k], 4 * nf1);
+    if (nf1) memcpy(C.host(F1) + 4 * featBase[k], fv1_features[k], 4 * nf1);
   }
-  if (n2 && !dev2) memcpy(H + oD2, desc2, 32 * (size_t)n2);
-  if (valid2 && n2) memcpy(H + oV2, valid2, (size_t)n2);
-  if (nf2) memcpy(H + oF2, fv2_features, 4 * (size_t)nf2);
-  memcpy(H + oP, all.data(), sizeof(BowPair) * all.size());
-  hipStream_t st = orbfe::matcher_stream(m);
-  // Nodes whose two feature lists fit the kernel's LDS (up to kBowSide features per side: every node of a real vocabulary at
-  // levelsup 4) are read ONCE per feature, so the kernel reads the page-locked arena itself and writes the matches into
-  // page-locked memory: no copy command, no fill, and the host polls the kernel's completion word instead of waiting on the
-  // stream (ORBFE_BOW_ZEROCOPY=0, or a larger node: upload, fill, launch, download as before).
-  bool small = true;
-  for (const BowPair& p : all) small = small && p.e1 - p.b1 <= kBowSide && p.e2 - p.b2 <= kBowSide;
-  const char* zce = getenv("ORBFE_BOW_ZEROCOPY");   // (read per call: the parity tests run both routes in one process)
-  const bool zc = !(zce && atoi(zce) == 0);
-  if (small && zc) {
-    if (!S->d_done.p) {
-      if ((rc = S->d_done.ensure(16)) || (rc = S->h_done.ensure(16))) return rc;
-      HIP_TRY(hipMemsetAsync(S->d_done.p, 0, 16 * sizeof(unsigned), st));
-      S->h_done.p[0] = 0;
-    }
-    memset(S->h_m12.p, 0xff, sizeof(int32_t) * rows1);
-    S->seq = S->seq == INT_MAX ? 1 : S->seq + 1;
-    hipLaunchKernelGGL(k_bow_match, dim3((unsigned)all.size()), dim3(kBowThreads), 0, st, dev1 ? dev1 : (const uint4*)(H + oD1), (const uint8_t*)(H + oV1),
-                       (const uint32_t*)(H + oF1), dev2 ? dev2 : (const uint4*)(H + oD2), valid2 ? (const uint8_t*)(H + oV2) : (const uint8_t*)nullptr,
-                       (const uint32_t*)(H + oF2), (const BowPair*)(H + oP), strict_threshold ? TH_LOW - 1 : TH_LOW, nnratio, S->h_m12.p,
-                       S->d_done.p, S->h_done.p, S->seq, (const uint32_t*)nullptr);
-    HIP_TRY(hipGetLastError());
-    const volatile int* flag = S->h_done.p;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spin = 1;; spin++) {
-      if (*flag == S->seq) { seen = true; break; }
-      if ((spin & 255u) == 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 2.0) break;
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) HIP_TRY(hipStreamSynchronize(st));
-  } else {
-    uint8_t* D = S->d_arena.p;
-    HIP_TRY(hipMemcpyAsync(D, H, total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(S->d_m12.p, 0xff, sizeof(int32_t) * rows1, st));
-    if (!items.empty()) {
-      if ((rc = S->d_topk.ensure(topkRows * kBowTopK)) || (rc = S->d_items.ensure(items.size()))) return rc;
-      HIP_TRY(hipMemcpyAsync(S->d_items.p, items.data(), sizeof(TopkItem) * items.size(), hipMemcpyHostToDevice, st));   // (waited for below)
-      const size_t ldsBytes = (size_t)maxStage * 36 + 16;
-      static std::mutex mu;
-      static size_t attr[64] = {};
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        const int dv = orbfe::matcher_device(m);
-        if (dv >= 0 && dv < 64 && ldsBytes > attr[dv]) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-          attr[dv] = ldsBytes;
-        }
+  if (n2 && !dev2) memcpy(C.host(D2), desc2, 32 * (size_t)n2);
+  if (valid2 && n2) memcpy(C.host(V2), valid2, (size_t)n2);
+  if (nf2) memcpy(C.host(F2), fv2_features, 4 * (size_t)nf2);
+  memcpy(C.host(P), all.data(), sizeof(BowPair) * all.size());
+  // the large nodes' top-K lists: after the arena's upload, before k_bow_match, on the same stream
+  auto topkStage = [&](uint8_t* B) -> int {
+    if (items.empty()) return ORBFE_OK;
+    int rc;
+    if ((rc = S->d_topk.ensure(topkRows * kBowTopK)) || (rc = S->d_items.ensure(items.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(S->d_items.p, items.data(), sizeof(TopkItem) * items.size(), hipMemcpyHostToDevice, C.st));   // (waited for by submit)
+    const size_t ldsBytes = (size_t)maxStage * 36 + 16;
+    static std::mutex mu;
+    static size_t attr[64] = {};
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      const int dv = orbfe::matcher_device(m);
+      if (dv >= 0 && dv < 64 && ldsBytes > attr[dv]) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
+        attr[dv] = ldsBytes;
       }
-      hipLaunchKernelGGL(k_bow_topk, dim3((unsigned)items.size()), dim3(256), ldsBytes, st, dev1 ? dev1 : (const uint4*)(D + oD1), (const uint8_t*)(D + oV1),
-                         (const uint32_t*)(D + oF1), dev2 ? dev2 : (const uint4*)(D + oD2), valid2 ? (const uint8_t*)(D + oV2) : (const uint8_t*)nullptr,
-                         (const uint32_t*)(D + oF2), (const BowPair*)(D + oP), (const TopkItem*)S->d_items.p, S->d_topk.p);
-      HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_bow_match, dim3((unsigned)all.size()), dim3(kBowThreads), 0, st, dev1 ? dev1 : (const uint4*)(D + oD1), (const uint8_t*)(D + oV1),
-                       (const uint32_t*)(D + oF1), dev2 ? dev2 : (const uint4*)(D + oD2), valid2 ? (const uint8_t*)(D + oV2) : (const uint8_t*)nullptr,
-                       (const uint32_t*)(D + oF2), (const BowPair*)(D + oP), strict_threshold ? TH_LOW - 1 : TH_LOW, nnratio, S->d_m12.p,
-                       (unsigned*)nullptr, (int*)nullptr, 0, (const uint32_t*)S->d_topk.p);
+    hipLaunchKernelGGL(k_bow_topk, dim3((unsigned)items.size()), dim3(256), ldsBytes, C.st, dev1 ? dev1 : C.at<uint4>(B, D1),
+                       C.at<uint8_t>(B, V1), C.at<uint32_t>(B, F1), dev2 ? dev2 : C.at<uint4>(B, D2), valid2 ? C.at<uint8_t>(B, V2) : (const uint8_t*)nullptr,
+                       C.at<uint32_t>(B, F2), C.at<BowPair>(B, P), (const TopkItem*)S->d_items.p, S->d_topk.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S->h_m12.p, S->d_m12.p, sizeof(int32_t) * rows1, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
+    return ORBFE_OK;
+  };
+  rc = C.submit([&](uint8_t* B, int32_t* m12, unsigned* doneCounter, int* doneHost, int doneSeq) {
+    hipLaunchKernelGGL(k_bow_match, dim3((unsigned)all.size()), dim3(kBowThreads), 0, C.st, dev1 ? dev1 : C.at<uint4>(B, D1),
+                       C.at<uint8_t>(B, V1), C.at<uint32_t>(B, F1), dev2 ? dev2 : C.at<uint4>(B, D2), valid2 ? C.at<uint8_t>(B, V2) : (const uint8_t*)nullptr,
+                       C.at<uint32_t>(B, F2), C.at<BowPair>(B, P), strict_threshold ? TH_LOW - 1 : TH_LOW, nnratio, m12, doneCounter, doneHost, doneSeq,
+                       C.zerocopy ? (const uint32_t*)nullptr : (const uint32_t*)S->d_topk.p);
+  }, topkStage);
+  if (rc) return rc;
   for (int k = 0; k < n_kf; k++) {
     int nm = 0;
     const int32_t* src = S->h_m12.p + rowBase[k];
@@ -1202,18 +1190,6 @@ extern "C" int orbfe_search_by_bow_batch(orbfe_matcher* m, int n_kf, const uint8
                         nullptr, nullptr);
 }
 
-// descriptor rows: 1 = in the memory of device `device`, 16-byte aligned (read in place); 0 = host memory (copied into the
-// arena); -1 = device memory the kernels cannot take as it is (another device's, or misaligned) -- refused, never memcpy'd
-static int bow_rows_where(const uint8_t* p, int device) {
-  hipPointerAttribute_t attr;
-  if (p && hipPointerGetAttributes(&attr, p) == hipSuccess) {
-    if (attr.type != hipMemoryTypeDevice) return 0;
-    return attr.device == device && ((uintptr_t)p & 15u) == 0 ? 1 : -1;
-  }
-  (void)hipGetLastError();
-  return 0;
-}
-
 extern "C" int orbfe_search_by_bow(orbfe_matcher* m, const uint8_t* desc1, const float* angle1, const uint8_t* valid1, int n1,
                                    const uint32_t* fv1_nodes, const uint32_t* fv1_offsets, const uint32_t* fv1_features,
                                    int n_fv1, const uint8_t* desc2, const float* angle2, const uint8_t* valid2, int n2,
@@ -1229,13 +1205,15 @@ extern "C" int orbfe_search_by_bow(orbfe_matcher* m, const uint8_t* desc1, const
   *nmatches = 0;
   // a side whose rows are a resident frame's (orbfe_frame_descriptors_device) stays where it is
   const int dev = orbfe::matcher_device(m);
-  const int w1 = bow_rows_where(desc1, dev), w2 = bow_rows_where(desc2, dev);
-  if (w1 < 0 || w2 < 0) {
+  // (rows in this device's memory, 16-byte aligned: read in place; another device's, or misaligned: refused, never memcpy'd;
+  // everything else -- ordinary, page-locked and managed memory -- is copied into the arena)
+  const int g1 = orbfe::gpu_readable(desc1, dev), g2 = orbfe::gpu_readable(desc2, dev);
+  if (g1 < 0 || g2 < 0 || (g1 == 2 && ((uintptr_t)desc1 & 15u) != 0) || (g2 == 2 && ((uintptr_t)desc2 & 15u) != 0)) {
     set_err("descriptor rows in device memory must belong to the matcher's device and be 16-byte aligned");
     return ORBFE_ERR_INVALID;
   }
-  const uint4* dev1 = w1 ? (const uint4*)desc1 : nullptr;
-  const uint4* dev2 = w2 ? (const uint4*)desc2 : nullptr;
+  const uint4* dev1 = g1 == 2 ? (const uint4*)desc1 : nullptr;
+  const uint4* dev2 = g2 == 2 ? (const uint4*)desc2 : nullptr;
   return bow_batch_core(m, 1, &desc1, &angle1, &valid1, &n1, &fv1_nodes, &fv1_offsets, &fv1_features, &n_fv1, desc2, angle2,
                         valid2, n2, fv2_nodes, fv2_offsets, fv2_features, n_fv2, nnratio, check_orientation, strict_threshold,
                         &matches12, nmatches, dev1, dev2);
@@ -1260,77 +1238,34 @@ extern "C" int orbfe_search_for_triangulation(orbfe_matcher* m, const OrbfeKeyPo
   int rc = common_nodes(fv1_nodes, fv1_offsets, n_fv1, fv2_nodes, fv2_offsets, n_fv2, pairs);
   if (rc) return rc;
   const int nf1 = n_fv1 ? (int)fv1_offsets[n_fv1] : 0, nf2 = n_fv2 ? (int)fv2_offsets[n_fv2] : 0;
-  for (int i = 0; i < nf1; i++) if (fv1_features[i] >= (uint32_t)n1) { set_err("fv1 feature index out of range"); return ORBFE_ERR_INVALID; }
-  for (int i = 0; i < nf2; i++) if (fv2_features[i] >= (uint32_t)n2) { set_err("fv2 feature index out of range"); return ORBFE_ERR_INVALID; }
+  if ((rc = check_features("fv1", fv1_features, nf1, n1)) || (rc = check_features("fv2", fv2_features, nf2, n2))) return rc;
   for (int i = 0; i < n2; i++) if (kps2_un[i].octave < 0 || kps2_un[i].octave >= nlevels2) { set_err("keypoint octave out of range"); return ORBFE_ERR_INVALID; }
   if (pairs.empty()) return ORBFE_OK;
-  HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
-  std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
-  if (!slot) slot = std::make_shared<BowScratch>();
-  BowScratch* S = static_cast<BowScratch*>(slot.get());
-  // everything the kernel reads in ONE page-locked arena (nine copy commands from ordinary memory, about 12 us each, were
-  // half of the call): read in place by the kernel when every node fits its LDS -- each item is then fetched once --, else
-  // uploaded with one copy
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t oK1 = 0, oK2 = oK1 + al(sizeof(OrbfeKeyPoint) * (size_t)n1), oD1 = oK2 + al(sizeof(OrbfeKeyPoint) * (size_t)n2),
-               oD2 = oD1 + al(32 * (size_t)n1), oV1 = oD2 + al(32 * (size_t)n2), oV2 = oV1 + al((size_t)std::max(n1, 1)),
-               oF1 = oV2 + al((size_t)std::max(n2, 1)), oF2 = oF1 + al(4 * (size_t)nf1), oP = oF2 + al(4 * (size_t)nf2),
-               total = oP + al(sizeof(BowPair) * pairs.size());
-  if ((rc = S->h_arena.ensure(total)) || (rc = S->d_arena.ensure(total)) || (rc = S->d_m12.ensure(n1)) || (rc = S->h_m12.ensure(n1))) return rc;
-  uint8_t* H = S->h_arena.p;
-  memcpy(H + oK1, kps1_un, sizeof(OrbfeKeyPoint) * (size_t)n1);
-  memcpy(H + oK2, kps2_un, sizeof(OrbfeKeyPoint) * (size_t)n2);
-  memcpy(H + oD1, desc1, 32 * (size_t)n1);
-  memcpy(H + oD2, desc2, 32 * (size_t)n2);
-  memcpy(H + oV1, has_mp1, (size_t)n1);
-  memcpy(H + oV2, has_mp2, (size_t)n2);
-  memcpy(H + oF1, fv1_features, 4 * (size_t)nf1);
-  memcpy(H + oF2, fv2_features, 4 * (size_t)nf2);
-  memcpy(H + oP, pairs.data(), sizeof(BowPair) * pairs.size());
-  hipStream_t st = orbfe::matcher_stream(m);
+  enum { K1, K2, D1, D2, V1, V2, F1, F2, P };   // the arena's parts
+  BowCall C;
+  if ((rc = C.open(m, {sizeof(OrbfeKeyPoint) * (size_t)n1, sizeof(OrbfeKeyPoint) * (size_t)n2, 32 * (size_t)n1, 32 * (size_t)n2, (size_t)std::max(n1, 1),
+                       (size_t)std::max(n2, 1), 4 * (size_t)nf1, 4 * (size_t)nf2, sizeof(BowPair) * pairs.size()}, (size_t)n1, pairs)))
+    return rc;
+  BowScratch* S = C.S;
+  memcpy(C.host(K1), kps1_un, sizeof(OrbfeKeyPoint) * (size_t)n1);
+  memcpy(C.host(K2), kps2_un, sizeof(OrbfeKeyPoint) * (size_t)n2);
+  memcpy(C.host(D1), desc1, 32 * (size_t)n1);
+  memcpy(C.host(D2), desc2, 32 * (size_t)n2);
+  memcpy(C.host(V1), has_mp1, (size_t)n1);
+  memcpy(C.host(V2), has_mp2, (size_t)n2);
+  memcpy(C.host(F1), fv1_features, 4 * (size_t)nf1);
+  memcpy(C.host(F2), fv2_features, 4 * (size_t)nf2);
+  memcpy(C.host(P), pairs.data(), sizeof(BowPair) * pairs.size());
   TriParams T;
   memcpy(T.F12, F12, sizeof T.F12);
   T.ex = ex; T.ey = ey;
   for (int i = 0; i < 16; i++) { T.scale2[i] = scale_factors2[std::min(i, nlevels2 - 1)]; T.sigma2[i] = level_sigma2_2[std::min(i, nlevels2 - 1)]; }
-  bool small = true;
-  for (const BowPair& p : pairs) small = small && p.e1 - p.b1 <= kBowSide && p.e2 - p.b2 <= kBowSide;
-  const char* zce = getenv("ORBFE_BOW_ZEROCOPY");
-  const bool zc = !(zce && atoi(zce) == 0);
-  if (small && zc) {
-    if (!S->d_done.p) {
-      if ((rc = S->d_done.ensure(16)) || (rc = S->h_done.ensure(16))) return rc;
-      HIP_TRY(hipMemsetAsync(S->d_done.p, 0, 16 * sizeof(unsigned), st));
-      S->h_done.p[0] = 0;
-    }
-    memset(S->h_m12.p, 0xff, sizeof(int32_t) * (size_t)n1);
-    S->seq = S->seq == INT_MAX ? 1 : S->seq + 1;
-    hipLaunchKernelGGL(k_bow_triangulate, dim3((unsigned)pairs.size()), dim3(kBowThreads), 0, st, (const OrbfeKeyPoint*)(H + oK1),
-                       (const uint4*)(H + oD1), (const uint8_t*)(H + oV1), (const uint32_t*)(H + oF1), (const OrbfeKeyPoint*)(H + oK2),
-                       (const uint4*)(H + oD2), (const uint8_t*)(H + oV2), (const uint32_t*)(H + oF2), (const BowPair*)(H + oP), T,
-                       S->h_m12.p, S->d_done.p, S->h_done.p, S->seq);
-    HIP_TRY(hipGetLastError());
-    const volatile int* flag = S->h_done.p;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spin = 1;; spin++) {
-      if (*flag == S->seq) { seen = true; break; }
-      if ((spin & 255u) == 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 2.0) break;
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) HIP_TRY(hipStreamSynchronize(st));
-  } else {
-    uint8_t* D = S->d_arena.p;
-    HIP_TRY(hipMemcpyAsync(D, H, total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(S->d_m12.p, 0xff, sizeof(int32_t) * (size_t)n1, st));
-    hipLaunchKernelGGL(k_bow_triangulate, dim3((unsigned)pairs.size()), dim3(kBowThreads), 0, st, (const OrbfeKeyPoint*)(D + oK1),
-                       (const uint4*)(D + oD1), (const uint8_t*)(D + oV1), (const uint32_t*)(D + oF1), (const OrbfeKeyPoint*)(D + oK2),
-                       (const uint4*)(D + oD2), (const uint8_t*)(D + oV2), (const uint32_t*)(D + oF2), (const BowPair*)(D + oP), T,
-                       S->d_m12.p, (unsigned*)nullptr, (int*)nullptr, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S->h_m12.p, S->d_m12.p, sizeof(int32_t) * (size_t)n1, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
+  rc = C.submit([&](uint8_t* B, int32_t* m12, unsigned* doneCounter, int* doneHost, int doneSeq) {
+    hipLaunchKernelGGL(k_bow_triangulate, dim3((unsigned)pairs.size()), dim3(kBowThreads), 0, C.st, C.at<OrbfeKeyPoint>(B, K1),
+                       C.at<uint4>(B, D1), C.at<uint8_t>(B, V1), C.at<uint32_t>(B, F1), C.at<OrbfeKeyPoint>(B, K2), C.at<uint4>(B, D2),
+                       C.at<uint8_t>(B, V2), C.at<uint32_t>(B, F2), C.at<BowPair>(B, P), T, m12, doneCounter, doneHost, doneSeq);
+  });
+  if (rc) return rc;
   int nm = 0;
   for (int i = 0; i < n1; i++) if (S->h_m12.p[i] >= 0) nm++;
   if (check_orientation)

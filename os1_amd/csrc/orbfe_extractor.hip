@@ -104,6 +104,7 @@ struct DevBuf {
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
+// (not hip_buffers.h's PinBuf: that one is hipHostMallocCoherent, this one hipHostMallocDefault -- a different kind of memory)
 template <class T>
 struct PinBuf {
   T* p = nullptr;

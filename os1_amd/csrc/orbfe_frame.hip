@@ -949,18 +949,7 @@ int run_search(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const uint
     // stream when it does not show up within 2 ms (ORBFE_FRAME_POLL=0: always the stream).
     {
       static const bool poll = [] { const char* e = ORBFE_EXP_ENV("ORBFE_FRAME_POLL"); return !(e && atoi(e) == 0); }();
-      bool seen = false;
-      if (poll) {
-        const volatile int* done = m->h_r.p + 5;
-        const double tW = orbfe_matcher::nowMs();
-        for (unsigned spin = 1;; spin++) {
-          if (*done == R.seq) { seen = true; break; }
-          if ((spin & 255u) == 0 && orbfe_matcher::nowMs() - tW > 2.0) break;
-          __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-      if (!seen) HIP_TRY(hipStreamSynchronize(st));
+      if ((rc = wait_for_word(m->h_r.p + 5, R.seq, st, poll))) return rc;
     }
     if (!m->h_r.p[1]) {
       m->tSynced = orbfe_matcher::nowMs();

@@ -24,20 +24,9 @@
 
 #include "../../include/orbfe.h"
 #include "bow_batch_plan.h"
+#include "hip_buffers.h"
 
-namespace orbfe {
-void set_err(const char* fmt, ...);
-}
 using orbfe::set_err;
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return ORBFE_ERR_HIP;                                                                  \
-    }                                                                                        \
-  } while (0)
 
 namespace {
 

@@ -1,6 +1,8 @@
 // orbfe_matcher_internal.h -- shared by orbfe_matcher.hip (host-array searches), orbfe_frame.hip (device-resident frames
-// + GPU-side match bookkeeping) and orbfe_bow.hip: the window kernel, its parameter block, buffer helpers and the matcher
-// handle; and the declarations of what the matcher-side files ask of each other.  Reference semantics: Frame::GetFeaturesInArea (src/Frame.cc:209-262) over Frame::AssignFeaturesToGrid's
+// + GPU-side match bookkeeping) and the files built on the matcher handle (orbfe_localmap.hip, orbfe_initscore.hip,
+// orbfe_mprefresh.hip) -- not by orbfe_bow.hip, which reaches the handle through accessors: the window kernel, its parameter
+// block and the matcher handle; and the declarations of what the matcher-side files ask of each other.  Buffer helpers:
+// hip_buffers.h.  Reference semantics: Frame::GetFeaturesInArea (src/Frame.cc:209-262) over Frame::AssignFeaturesToGrid's
 // 64x48 grid (Frame.cc:114-129, 264-274), ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1605-1621).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,22 +22,10 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "hip_buffers.h"
 #include "host_pool.h"
 
-namespace orbfe {
-void set_err(const char* fmt, ...);
-}
 using orbfe::set_err;
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return ORBFE_ERR_HIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
 
 namespace orbfe_match {
 
@@ -432,39 +422,6 @@ __global__ __launch_bounds__(kWinThreads) void k_window_match(MatchParams M) {
     }
   }
 }
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n) return ORBFE_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; n = 0;
-    HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-    n = count;
-    return ORBFE_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n) return ORBFE_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; n = 0;
-    // Coherent (fine-grained, uncached on the GPU side) EXPLICITLY: kernels store results and completion words here and the
-    // host polls them while the kernel runs; with hipHostMallocDefault that property would hang on HIP_HOST_COHERENT.
-    HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocCoherent));
-    n = count;
-    return ORBFE_OK;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
-};
-
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace orbfe_match
 using namespace orbfe_match;

@@ -36,13 +36,13 @@ import numpy as np
 from search_boundary_util import F32, HIST_COUNTS, ROT_PROBES, SF, hamming, make_kps, rot_bin32, row
 
 # constants of os1_amd/csrc/orbfe_bow.hip the scenes of family G are sized to (the CPU test reads them out of the source)
-CONSTANTS = {'TH_LOW': 50,              # :50
-             'kMaxGroup': 65535,        # :52   features of one frame under one node
-             'kBowTopK': 8,             # :208  keys per frame-1 feature of a large node
-             'kTopkRegs': 32,           # :210  keys a lane keeps in registers: nodes of up to 64 * 32 = 2 048 frame-2 features
-             'kTopkLdsFeatures': 4096,  # :211  frame-2 features of a node staged in LDS
-             'kBowMatrix': 12288,       # :292  distance matrix entries / winners kept in LDS
-             'kBowSide': 256}           # :293  features per side of a node handled from LDS
+CONSTANTS = {'TH_LOW': 50,              # :42
+             'kMaxGroup': 65535,        # :44   features of one frame under one node
+             'kBowTopK': 8,             # :180  keys per frame-1 feature of a large node
+             'kTopkRegs': 32,           # :182  keys a lane keeps in registers: nodes of up to 64 * 32 = 2 048 frame-2 features
+             'kTopkLdsFeatures': 4096,  # :183  frame-2 features of a node staged in LDS
+             'kBowMatrix': 12288,       # :264  distance matrix entries / winners kept in LDS
+             'kBowSide': 256}           # :265  features per side of a node handled from LDS
 TH_LOW, K_GROUP = CONSTANTS['TH_LOW'], CONSTANTS['kMaxGroup']
 K_SIDE, K_MATRIX, K_TOPK = CONSTANTS['kBowSide'], CONSTANTS['kBowMatrix'], CONSTANTS['kBowTopK']
 K_REGS2, K_LDS2 = 64 * CONSTANTS['kTopkRegs'], CONSTANTS['kTopkLdsFeatures']      # frame-2 features: keys in registers / staged in LDS
