@@ -1577,33 +1577,11 @@ int orc_search_projected(const OrcKeyPoint* kpsUn, const uint8_t* desc, int n, c
 // =============================================================================================
 #define ORB_ORACLE_IMPLEMENTATION
 #include "orb_oracle_pose.h"
+#include "cv_small.h"   // cvGemm3, cvGemmT3, cvNorm3, cvDot3: shared with the cv::Mat stand-in under os1_decl/
 
 namespace {
 static_assert(sizeof(OrcKp) == sizeof(OrcKeyPoint), "layout");
 
-void cvGemm3(const float A[9], const float b[3], double alpha, const float* c, double beta, float d[3]) {
-  for (int i = 0; i < 3; i++) {
-    const float t = A[3 * i] * b[0] + A[3 * i + 1] * b[1] + A[3 * i + 2] * b[2];
-    d[i] = (float)((double)t * alpha + (double)(c ? c[i] : 0.f) * beta);
-  }
-}
-void cvGemmT3(const float A[9], const float b[3], double alpha, float d[3]) {   // alpha * A^T * b
-  for (int i = 0; i < 3; i++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)A[3 * k + i] * (double)b[k];
-    d[i] = (float)(s * alpha);
-  }
-}
-double cvNorm3(const float v[3]) {
-  double s = 0;
-  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-  return std::sqrt(s);
-}
-double cvDot3(const float a[3], const float b[3]) {
-  double r = 0;
-  for (int k = 0; k < 3; k++) r += (double)a[k] * (double)b[k];
-  return r;
-}
 void poseRt(const float T[16], float R[9], float t[3]) {   // rowRange(0,3).colRange(0,3) / .col(3)
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) R[3 * r + c] = T[4 * r + c];
