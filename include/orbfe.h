@@ -818,7 +818,44 @@ int orbfe_distinctive_descriptors(orbfe_matcher* m, int n_mp, const int32_t* off
                                   int32_t* best_idx);
 
 /* ---------------------------------------------------------------------------------------------
- * Bag of words.  Replaces the DBoW2 calls on the path: Frame::ComputeBoW (src/Frame.cc:277-284) ->
+ * Covisibility counts.  The counting loop of KeyFrame::UpdateConnections (src/KeyFrame.cc:305-331) and of
+ * Tracking::UpdateLocalKeyFrames (src/Tracking.cc:862-879) for a batch of subjects in one call; what follows the counting (the
+ * threshold, AddConnection, the sort, the parent) depends on pointer order and stays with the host (include/orbfe/Covisibility.h).
+ *
+ * Keyframes are named by slots 0..n_kf-1, MapPoints by indices 0..n_mp-1.  MapPoint p is observed by the keyframes
+ * obs_kf[obs_offsets[p] .. obs_offsets[p+1]).  Subject s (a keyframe, or a Frame) holds one entry per keypoint,
+ * subj_mp[subj_offsets[s] .. subj_offsets[s+1]): the MapPoint's index, or -1 for whatever the reference skips (null, isBad(),
+ * plCandidato, plLejano).  For every entry with p = subj_mp[e] >= 0 and every observation o of p, with j = obs_kf[o]:
+ * counter[j]++ unless j == subj_self[s] or j >= subj_limit[s].  A MapPoint named twice by one subject counts twice (the reference
+ * walks the vector mvpMapPoints, not a set); observers that are bad keyframes are counted, as in the reference.
+ *   subj_self[s]   the subject's own slot (KeyFrame.cc:327), or -1: no exclusion -- Tracking's keyframeCounter
+ *   subj_limit     NULL: n_kf for every subject.  Otherwise only observers with slot < subj_limit[s] are counted: with the slots in
+ *                  load order, subj_limit[k] = k + 1 gives the counter keyframe k sees in Osmap's rebuild (src/Osmap.cpp:569-579),
+ *                  where only keyframes 0..k have added their observations when k calls UpdateConnections.
+ * Output: a compact CSR.  Subject s owns [out_offsets[s], out_offsets[s+1]) of out_kf / out_count: its non-zero counters in
+ * ascending slot order.  *n_needed = the total number of entries; if it exceeds cap the call returns ORBFE_ERR_OVERFLOW with
+ * *n_needed set, the other outputs unspecified and the matcher usable.  No call needs more than the sum over the subjects of
+ * min(subj_limit[s], observations reachable from s).
+ * ORBFE_ERR_INVALID before anything is sent: a null pointer (out_kf / out_count may be NULL with cap 0, obs_kf / subj_mp where
+ * their CSR is empty); a negative size; offsets that decrease; an obs_kf outside [0, n_kf); a subj_mp outside [-1, n_mp); a
+ * subj_self outside [-1, n_kf); a subj_limit outside [0, n_kf]; a bound above 2^31 - 1 entries.  n_subj == 0: ORBFE_OK.
+ * The call runs on the matcher's stream and returns when the host outputs are written.  It takes no resident frames: only
+ * indices cross PCIe.  Integer counting: the result is exact, whatever the order of the additions. */
+int orbfe_covisibility_counts(orbfe_matcher* m,
+      int n_kf,                                   /* keyframe slots 0..n_kf-1 */
+      int n_mp, const int32_t* obs_offsets /* n_mp+1 */, const int32_t* obs_kf /* observer slot per observation */,
+      int n_subj, const int32_t* subj_self /* slot of the subject, or -1 for a Frame */,
+      const int32_t* subj_limit /* NULL = n_kf for all: only observers with slot < limit are counted */,
+      const int32_t* subj_offsets /* n_subj+1 */, const int32_t* subj_mp /* MapPoint index per keypoint entry, -1 = skipped */,
+      int32_t* out_offsets /* n_subj+1 */, int32_t* out_kf, int32_t* out_count, int cap, int* n_needed);
+/* Observer slots one pass of the kernel counts (the bins of its histogram in LDS); a map of more keyframes takes several passes. */
+int orbfe_debug_covis_slots_per_pass(void);
+/* The last orbfe_covisibility_counts of this matcher, ms: [0] argument check and staging on the host, [1] the kernel (events on
+ * the stream), [2] the whole call. */
+int orbfe_debug_covis_ms(const orbfe_matcher* m, double out[3]);
+
+/* ---------------------------------------------------------------------------------------------
+ * Bag of words. Replaces the DBoW2 calls on the path: Frame::ComputeBoW (src/Frame.cc:277-284) ->
  * TemplatedVocabulary<FORB>::transform(features, BowVector&, FeatureVector&, levelsup)
  * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1136-1204, descent :1306-1347), and the two
  * ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cc:154-283, 517-650).

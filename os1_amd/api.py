@@ -212,6 +212,9 @@ def load_library():
     L.orbfe_local_map_set_rows.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.orbfe_local_map_refresh_rows.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci] + [vp] * 11
     L.orbfe_local_map_download_rows.argtypes = [vp, ci, vp, vp]
+    L.orbfe_covisibility_counts.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(ci)]
+    L.orbfe_debug_covis_slots_per_pass.argtypes = []
+    L.orbfe_debug_covis_ms.argtypes = [vp, vp]
     L.orbfe_project_local_map.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_search_local_points_frame.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, ci, vp, cf, cf, vp, vp, vp, vp, vp,
                                                   C.POINTER(ci), C.POINTER(ci)]
@@ -1172,6 +1175,12 @@ class Matcher:
         _check(self.L.orbfe_debug_matcher_ms(self.h, _p(out)))
         return out
 
+    def covis_ms(self):
+        """The last covisibility_counts call, ms: host check + staging, kernel, whole call."""
+        out = np.zeros(3, np.float64)
+        _check(self.L.orbfe_debug_covis_ms(self.h, _p(out)))
+        return out
+
     def get_features_in_area(self, kps, bounds, x, y, r, min_level, max_level):
         kps = np.ascontiguousarray(kps, KP_DTYPE)
         b = np.asarray(bounds, np.float32)
@@ -1229,6 +1238,64 @@ def logf_host_mismatches(lo_bits, hi_bits, step=1):
     bad = C.c_longlong(0)
     _check(load_library().orbfe_debug_logf_host_check(lo_bits, hi_bits, step, C.byref(bad)))
     return bad.value
+
+
+def covis_slots_per_pass():
+    """Observer slots one pass of k_covisibility counts (the bins of its LDS histogram)."""
+    return load_library().orbfe_debug_covis_slots_per_pass()
+
+
+def covisibility_bound(n_kf, obs_offsets, subj_offsets, subj_mp, subj_limit=None):
+    """Sum over the subjects of min(limit, observations reachable from the subject): no covisibility_counts call needs more
+    output entries.  (Entries outside [0, n_mp) count as skipped here; the library refuses them.)"""
+    oo = np.asarray(obs_offsets, np.int64)
+    so = np.asarray(subj_offsets, np.int64)
+    mp = np.asarray(subj_mp, np.int64)
+    n_subj = len(so) - 1
+    if n_subj <= 0:
+        return 0
+    per_mp = np.diff(oo)
+    ok = (mp >= 0) & (mp < len(per_mp))
+    per_entry = np.zeros(len(mp) + 1, np.int64)
+    per_entry[1:][ok] = np.maximum(per_mp[mp[ok]], 0)
+    run = np.cumsum(per_entry)
+    at = np.clip(so, 0, len(mp))
+    reach = np.maximum(run[at[1:]] - run[at[:-1]], 0)
+    limit = np.full(n_subj, n_kf, np.int64) if subj_limit is None else np.clip(np.asarray(subj_limit, np.int64), 0, max(n_kf, 0))
+    return int(np.minimum(reach, limit).sum())
+
+
+def covisibility_counts(matcher, n_kf, obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp, subj_limit=None, cap=None):
+    """The counters of KeyFrame::UpdateConnections / Tracking::UpdateLocalKeyFrames for a batch of subjects
+    (orbfe_covisibility_counts): MapPoint p is observed by the keyframe slots obs_kf[obs_offsets[p]:obs_offsets[p+1]]; subject s
+    names the MapPoints subj_mp[subj_offsets[s]:subj_offsets[s+1]] (-1: skipped), excludes its own slot subj_self[s] (-1: nobody)
+    and every slot >= subj_limit[s] (None: no limit).  Returns (out_offsets, out_kf, out_count): subject s owns
+    [out_offsets[s], out_offsets[s+1]) of the non-zero counters in ascending slot order.  cap (None: covisibility_bound, which
+    always suffices) is the room for entries; a call that needs more raises OrbfeError with code -5 and .n_needed set.
+    matcher None reaches the library's argument check only (every call is then refused, with the reason)."""
+    oo = np.ascontiguousarray(obs_offsets, np.int32)
+    ok = np.ascontiguousarray(obs_kf, np.int32)
+    ss = np.ascontiguousarray(subj_self, np.int32)
+    so = np.ascontiguousarray(subj_offsets, np.int32)
+    sm = np.ascontiguousarray(subj_mp, np.int32)
+    sl = None if subj_limit is None else np.ascontiguousarray(subj_limit, np.int32)
+    n_mp, n_subj = len(oo) - 1, len(ss)
+    if len(so) != n_subj + 1 or (sl is not None and len(sl) != n_subj) or n_mp < 0:
+        raise ValueError('covisibility_counts: obs_offsets needs n_mp + 1 entries, subj_offsets n_subj + 1, subj_limit n_subj')
+    if cap is None:
+        cap = covisibility_bound(n_kf, oo, so, sm, sl)
+    out_offsets = np.zeros(n_subj + 1, np.int32)
+    out_kf = np.zeros(max(cap, 1), np.int32)
+    out_count = np.zeros(max(cap, 1), np.int32)
+    needed = C.c_int(0)
+    rc = load_library().orbfe_covisibility_counts(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _p(ok) if len(ok) else None, n_subj,
+                                                  _p(ss) if n_subj else None, None if sl is None else _p(sl), _p(so), _p(sm) if len(sm) else None,
+                                                  _p(out_offsets), _p(out_kf), _p(out_count), cap, C.byref(needed))
+    if rc != 0:
+        e = OrbfeError(rc, load_library().orbfe_last_error().decode('utf-8', 'replace'))
+        e.n_needed = needed.value if rc == -5 else None
+        raise e
+    return out_offsets, out_kf[:needed.value].copy(), out_count[:needed.value].copy()
 
 
 class Vocabulary:
