@@ -16,31 +16,9 @@
 #include <vector>
 
 #include "TemplatedVocabulary.h"
+#include "row32.h"   // Row32 / Row32Ops
 
 namespace {
-
-struct Row32 {
-  unsigned char b[32];
-};
-
-struct Row32Ops {
-  typedef Row32 TDescriptor;
-  typedef const TDescriptor* pDescriptor;
-  static const int L = 32;
-  static int distance(const TDescriptor& a, const TDescriptor& b) {
-    int d = 0;
-    for (int i = 0; i < 32; i++) d += __builtin_popcount((unsigned)(a.b[i] ^ b.b[i]));
-    return d;
-  }
-  static void fromArray(TDescriptor& a, const unsigned char* p) { memcpy(a.b, p, 32); }
-  // the three below are named by the template's training and text-file code only, which nothing here calls
-  static void meanValue(const std::vector<pDescriptor>& rows, TDescriptor& mean) {
-    memset(mean.b, 0, 32);
-    if (!rows.empty()) mean = *rows[0];
-  }
-  static std::string toString(const TDescriptor&) { return std::string(); }
-  static void fromString(TDescriptor& a, const std::string&) { memset(a.b, 0, 32); }
-};
 
 // the single-feature transform with the node id is a protected member
 struct Voc : public DBoW2::TemplatedVocabulary<Row32, Row32Ops> {

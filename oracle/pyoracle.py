@@ -521,3 +521,165 @@ class OracleExtractor:
         out = np.zeros(max(n, 1), KP_DTYPE)
         self.o.L.orc_level_candidates(self.h, level, _p(out), n)
         return out[:n].copy()
+
+
+# ---- the reference's own KeyFrameDatabase.cc and Initializer.cc (oracle/_ref/, built by oracle/Makefile where the reference exists) ----
+OS1_KFDB_SO = os.path.join(_HERE, '_ref', 'libos1_kfdb.so')
+OS1_INITIALIZER_SO = os.path.join(_HERE, '_ref', 'libos1_initializer.so')
+_OS1_KFDB_LIB = None
+_OS1_INITIALIZER_LIB = None
+
+
+def have_os1_kfdb():
+    return os.path.exists(OS1_KFDB_SO)
+
+
+def have_os1_initializer():
+    return os.path.exists(OS1_INITIALIZER_SO)
+
+
+def _os1_kfdb_lib():
+    global _OS1_KFDB_LIB
+    if _OS1_KFDB_LIB is None:
+        L = C.CDLL(OS1_KFDB_SO)
+        assert L.os1kfdb_is_reference_build() == 1
+        vp, ci, u64 = C.c_void_p, C.c_int, C.c_uint64
+        L.os1kfdb_create.argtypes = [ci, ci]
+        L.os1kfdb_create.restype = vp
+        L.os1kfdb_destroy.argtypes = [vp]
+        L.os1kfdb_destroy.restype = None
+        L.os1kfdb_voc_size.argtypes = [vp]
+        L.os1kfdb_new_kf.argtypes = [vp, u64, vp, vp, ci]
+        L.os1kfdb_set_connected.argtypes = [vp, ci, vp, ci]
+        L.os1kfdb_set_covisible.argtypes = [vp, ci, vp, ci]
+        L.os1kfdb_set_bad.argtypes = [vp, ci, ci]
+        for f in (L.os1kfdb_add, L.os1kfdb_erase):
+            f.argtypes = [vp, ci]
+            f.restype = None
+        L.os1kfdb_clear.argtypes = [vp]
+        L.os1kfdb_clear.restype = None
+        L.os1kfdb_detect_loop.argtypes = [vp, ci, C.c_float, vp, ci]
+        L.os1kfdb_detect_reloc.argtypes = [vp, u64, vp, vp, ci, vp, ci]
+        L.os1kfdb_min_covisible_score.argtypes = [vp, ci]
+        L.os1kfdb_min_covisible_score.restype = C.c_float
+        L.os1kfdb_score.argtypes = [vp, vp, vp, ci, ci]
+        L.os1kfdb_score.restype = C.c_double
+        L.os1kfdb_members.argtypes = [vp, ci, vp, vp, vp]
+        L.os1kfdb_members.restype = None
+        _OS1_KFDB_LIB = L
+    return _OS1_KFDB_LIB
+
+
+class Os1KeyFrameDatabase:
+    """The REFERENCE'S OWN src/KeyFrameDatabase.cc (oracle/_ref/libos1_kfdb.so <- oracle/os1_kfdb_wrap.cpp) loaded with a scene of
+    tests/kfdb_util.py; the interface of kfdb_util.Ref.  mpVoc is the reference's TemplatedVocabulary with scene['n_words'] words."""
+
+    def __init__(self, scene):
+        self.L, self.scene = _os1_kfdb_lib(), scene
+        L = self.L
+        self.h = L.os1kfdb_create(scene['n_words'], scene['scoring'])
+        assert self.h and L.os1kfdb_voc_size(self.h) == scene['n_words']
+        for k in scene['kfs']:
+            w, v = np.ascontiguousarray(k['words'], np.uint32), np.ascontiguousarray(k['values'], np.float64)
+            assert L.os1kfdb_new_kf(self.h, k['id'], _p(w), _p(v), len(w)) == k['index']
+        for k in scene['kfs']:
+            conn = np.asarray(sorted(k['connected']), np.int32)
+            cov = np.asarray(k['covisible'], np.int32)
+            L.os1kfdb_set_connected(self.h, k['index'], _p(conn), len(conn))
+            L.os1kfdb_set_covisible(self.h, k['index'], _p(cov), len(cov))
+            L.os1kfdb_set_bad(self.h, k['index'], int(k['bad']))
+
+    def close(self):
+        if self.h:
+            self.L.os1kfdb_destroy(self.h)
+            self.h = None
+
+    def min_covisible_score(self, kf):
+        return float(self.L.os1kfdb_min_covisible_score(self.h, kf))
+
+    def score(self, words, values, kf):
+        w, v = np.ascontiguousarray(words, np.uint32), np.ascontiguousarray(values, np.float64)
+        return float(self.L.os1kfdb_score(self.h, _p(w), _p(v), len(w), kf))
+
+    def step(self, st):
+        """-> None for a mutation, the candidate list (keyframe indices) for a query"""
+        L, cap = self.L, len(self.scene['kfs'])
+        out = np.zeros(max(cap, 1), np.int32)
+        if st[0] == 'add':
+            L.os1kfdb_add(self.h, st[1])
+        elif st[0] == 'erase':
+            L.os1kfdb_erase(self.h, st[1])
+        elif st[0] == 'clear':
+            L.os1kfdb_clear(self.h)
+        elif st[0] == 'loop':
+            ms = st[2] if st[2] is not None else self.min_covisible_score(st[1])
+            n = L.os1kfdb_detect_loop(self.h, st[1], C.c_float(ms), _p(out), cap)
+            return [int(v) for v in out[:n]]
+        elif st[0] == 'reloc':
+            w, v = np.ascontiguousarray(st[2], np.uint32), np.ascontiguousarray(st[3], np.float64)
+            n = L.os1kfdb_detect_reloc(self.h, st[1], _p(w), _p(v), len(w), _p(out), cap)
+            return [int(v) for v in out[:n]]
+        return None
+
+    def members(self):
+        """[(mnLoopQuery, mnLoopWords, mLoopScore bits, mnRelocQuery, mnRelocWords, mRelocScore bits)] of every keyframe"""
+        res = []
+        q, w, s = np.zeros(2, np.uint64), np.zeros(2, np.int32), np.zeros(2, np.float32)
+        for k in self.scene['kfs']:
+            self.L.os1kfdb_members(self.h, k['index'], _p(q), _p(w), _p(s))
+            b = s.view(np.uint32)
+            res.append((int(q[0]), int(w[0]), int(b[0]), int(q[1]), int(w[1]), int(b[1])))
+        return res
+
+
+def _os1_initializer_lib():
+    global _OS1_INITIALIZER_LIB
+    if _OS1_INITIALIZER_LIB is None:
+        L = C.CDLL(OS1_INITIALIZER_SO)
+        assert L.os1init_is_reference_build() == 1
+        vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+        L.os1init_check_homography.argtypes = [vp, ci, vp, vp, cf, vp]
+        L.os1init_check_homography.restype = cf
+        L.os1init_check_fundamental.argtypes = [vp, ci, vp, cf, vp]
+        L.os1init_check_fundamental.restype = cf
+        L.os1init_check_many.argtypes = [vp, ci, cf, ci] + [vp] * 5 + [ci, ci, vp, vp]
+        L.os1init_check_many.restype = None
+        _OS1_INITIALIZER_LIB = L
+    return _OS1_INITIALIZER_LIB
+
+
+class Os1Initializer:
+    """The REFERENCE'S OWN Initializer::CheckHomography / CheckFundamental (oracle/_ref/libos1_initializer.so <-
+    oracle/os1_initializer_wrap.cpp).  pts is (n, 4) float32 = (u1, v1, u2, v2) per match; matrices are 9 float32, row-major."""
+
+    def __init__(self):
+        self.L = _os1_initializer_lib()
+
+    def stub_calls(self):
+        """how often any stubbed OpenCV operation of the unreached members ran: must stay 0"""
+        return int(self.L.os1init_stub_counter())
+
+    def check_homography(self, pts, H21, H12, sigma):
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        a, b = np.ascontiguousarray(H21, np.float32).reshape(9), np.ascontiguousarray(H12, np.float32).reshape(9)
+        inl = np.zeros(max(len(pts), 1), np.uint8)
+        s = self.L.os1init_check_homography(_p(pts), len(pts), _p(a), _p(b), sigma, _p(inl))
+        return np.float32(s), inl[:len(pts)].astype(bool)
+
+    def check_fundamental(self, pts, F21, sigma):
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        a = np.ascontiguousarray(F21, np.float32).reshape(9)
+        inl = np.zeros(max(len(pts), 1), np.uint8)
+        s = self.L.os1init_check_fundamental(_p(pts), len(pts), _p(a), sigma, _p(inl))
+        return np.float32(s), inl[:len(pts)].astype(bool)
+
+    def check_many(self, pts, sigma, H21=None, H12=None, F21=None):
+        """-> (scores_h or None, scores_f or None): one call of the member per hypothesis"""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        mats = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 9) for a in (H21, H12, F21)]
+        K = max(len(a) for a in mats if a is not None)
+        sh, sf = np.zeros(K, np.float32), np.zeros(K, np.float32)
+        inl = np.zeros(max(len(pts), 1), np.uint8)
+        q = lambda a: None if a is None else _p(a)
+        self.L.os1init_check_many(_p(pts), len(pts), sigma, K, q(mats[0]), q(mats[1]), q(mats[2]), _p(sh), _p(sf), -1, -1, _p(inl), _p(inl))
+        return (sh if mats[0] is not None else None), (sf if mats[2] is not None else None)

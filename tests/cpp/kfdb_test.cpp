@@ -3,13 +3,17 @@
 // tests/kfdb_util.py writes (argv[1..]: scene files).  The stand-in KeyFrame / Frame expose the member names
 // KeyFrameDatabase.cc and LoopClosing.cc:125-140 use.  After EVERY step -- add, erase, clear, DetectLoopCandidates,
 // DetectRelocalizationCandidates -- the returned vector and all six members of every keyframe are compared with the
-// restatement's.  Prints the restatement's counters and PASS; exit code 0 iff every comparison is exact.
+// restatement's.  Where a file <scene file>.expect lies beside a scene file (tests/kfdb_util.py write_expected: the recorded
+// outputs of the reference's own compiled KeyFrameDatabase.cc, tests/golden/os1_kfdb_outputs.npz), the returned vector and the
+// members are compared with that recording as well.  Prints the restatement's counters and PASS; exit code 0 iff every
+// comparison is exact.
 //   build: g++ -std=c++17 -O1 -ffp-contract=off -Iinclude tests/cpp/kfdb_test.cpp tests/cpp/kfdb_ref.cpp os1_amd/liborbfe.so
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <set>
+#include <string>
 #include <vector>
 
 #include "orbfe/orb_shim.hpp"
@@ -72,7 +76,50 @@ static std::vector<T> rdv(int n) {
   return v;
 }
 
-static long g_checks = 0;
+static long g_checks = 0, g_refChecks = 0, g_refQueries = 0;
+
+// The recording of the reference object for one scene: per step the candidate count (-1: a mutation) and indices, then
+// {mnLoopQuery u64, mnLoopWords i32, mLoopScore bits u32, mnRelocQuery u64, mnRelocWords i32, mRelocScore bits u32} per keyframe.
+struct Expected {
+  FILE* f = nullptr;
+  bool open(const char* scene, int nSteps, int nKf) {
+    f = fopen((std::string(scene) + ".expect").c_str(), "rb");
+    if (!f) return true;   // no recording beside this scene
+    int h[2];
+    if (fread(h, 4, 2, f) != 2 || h[0] != nSteps || h[1] != nKf) { printf("FAIL: %s.expect does not belong to the scene\n", scene); return false; }
+    return true;
+  }
+  template <class KF>
+  bool step(int s, const char* what, bool isQuery, const std::vector<KF*>& got, const std::vector<KF>& kfs) {
+    if (!f) return true;
+    int n;
+    if (fread(&n, 4, 1, f) != 1) { printf("FAIL: short .expect file\n"); return false; }
+    std::vector<int> want(n > 0 ? n : 0);
+    if (n > 0 && fread(want.data(), 4, n, f) != (size_t)n) { printf("FAIL: short .expect file\n"); return false; }
+    if ((n >= 0) != isQuery) { printf("FAIL: step %d (%s): the recording has another kind of step\n", s, what); return false; }
+    if (isQuery) {
+      g_refQueries++;
+      bool ok = (int)got.size() == n;
+      for (int i = 0; ok && i < n; i++) ok = got[i]->index == want[i];
+      if (!ok) { printf("FAIL: step %d (%s): %zu candidates vs %d of the reference object\n", s, what, got.size(), n); return false; }
+    }
+    for (const KF& k : kfs) {
+      uint64_t q[2]; int32_t w[2]; uint32_t b[2];
+      if (fread(&q[0], 8, 1, f) != 1 || fread(&w[0], 4, 1, f) != 1 || fread(&b[0], 4, 1, f) != 1 || fread(&q[1], 8, 1, f) != 1 ||
+          fread(&w[1], 4, 1, f) != 1 || fread(&b[1], 4, 1, f) != 1) { printf("FAIL: short .expect file\n"); return false; }
+      g_refChecks++;
+      if (q[0] != k.mnLoopQuery || q[1] != k.mnRelocQuery || w[0] != k.mnLoopWords || w[1] != k.mnRelocWords ||
+          memcmp(&b[0], &k.mLoopScore, 4) || memcmp(&b[1], &k.mRelocScore, 4)) {
+        printf("FAIL: step %d (%s): members of keyframe %d differ from the reference object's: loop %lu/%d/%.9g vs %llu/%d/%08x, reloc "
+               "%lu/%d/%.9g vs %llu/%d/%08x\n", s, what, k.index, k.mnLoopQuery, k.mnLoopWords, k.mLoopScore, (unsigned long long)q[0], w[0],
+               b[0], k.mnRelocQuery, k.mnRelocWords, k.mRelocScore, (unsigned long long)q[1], w[1], b[1]);
+        return false;
+      }
+    }
+    return true;
+  }
+  ~Expected() { if (f) fclose(f); }
+};
 static bool same_members(void* ref, std::vector<KeyFrame>& kfs, const char* what, int step) {
   for (KeyFrame& k : kfs) {
     uint64_t q[2]; int32_t w[2]; float s[2];
@@ -118,6 +165,8 @@ static int run_scene(const char* path, long totals[8]) {
   orbfe::KeyFrameDatabaseT<KeyFrame> db(0, (size_t)nWords, scoring, capK, capE);
   std::vector<int> want(nKf);
   int queries = 0;
+  Expected expected;
+  if (!expected.open(path, nSteps, nKf)) return 1;
   for (int s = 0; s < nSteps; s++) {
     const int type = rd<int>(), kf = rd<int>();
     const uint64_t fid = rd<uint64_t>();
@@ -153,6 +202,7 @@ static int run_scene(const char* path, long totals[8]) {
       if (!ok) { printf("FAIL: step %d (%s): %zu candidates vs %d\n", s, what, got.size(), nWant); return 1; }
     }
     if (!same_members(ref, kfs, what, s)) return 1;
+    if (!expected.step(s, what, nWant >= 0, got, kfs)) return 1;
   }
   long c[8];
   kref_counters(ref, c);
@@ -172,8 +222,8 @@ int main(int argc, char** argv) {
     printf("FAIL: %s\n", e.what());
     return 1;
   }
-  printf("scenes %d candidates %ld duplicates %ld stale %ld connected_skips %ld best_other %ld queries %ld checks %ld\n", argc - 1, totals[0],
-         totals[1], totals[2], totals[3], totals[4], totals[5], g_checks);
+  printf("scenes %d candidates %ld duplicates %ld stale %ld connected_skips %ld best_other %ld queries %ld checks %ld ref_queries %ld "
+         "ref_checks %ld\n", argc - 1, totals[0], totals[1], totals[2], totals[3], totals[4], totals[5], g_checks, g_refQueries, g_refChecks);
   printf("PASS\n");
   return 0;
 }

@@ -390,3 +390,249 @@ def run_facade(exe, scene_files):
     lines = r.stdout.strip().splitlines()
     assert r.returncode == 0 and lines and lines[-1] == 'PASS', r.stdout[-3000:] + r.stderr[-2000:]
     return lines
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Boundary inputs: chiSquare == th exactly, one ulp either side, an inlier in one direction only, den / w of exactly 0.
+# The reference tests `chiSquare > th`: a match AT th is an inlier that adds th - chi (+0 for H, 5.991f - 3.841f for F).
+# ---------------------------------------------------------------------------------------------------------------------
+TH_H, TH_F = f32(5.991), f32(3.841)
+IDENTITY = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], f32)
+# x2' F x1 = s * (v1 - v2): a camera that moved along x.  l2 = (0, -s, s v1), l1 = (0, s, -s v2)
+F_SIDEWAYS = np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], f32)
+
+
+def _ulp_walk(x, n):
+    x = f32(x)
+    for _ in range(abs(n)):
+        x = np.nextafter(x, f32(np.inf if n > 0 else -np.inf), dtype=f32)
+    return x
+
+
+def search_h_boundary(span=4096):
+    """(dx, dy) with fl(fl(dx*dx) + fl(dy*dy)) == 5.991f: with H21 = H12 = identity and sigma 1 the match (dx, dy, 0, 0) has
+    chiSquare1 == chiSquare2 == th.  The search: dx walks the floats upward from 2.0f, dy the 64 floats around sqrt(th - dx*dx); the
+    first hit is taken.  -> (dx, dy, number of (dx, dy) pairs tried)"""
+    tried = 0
+    for i in range(span):
+        dx = _ulp_walk(2.0, i) if i < 8 else f32(2.0) + f32(i) * f32(2.0 ** -22)
+        dy0 = f32(np.sqrt(float(TH_H) - float(dx) * float(dx)))
+        for j in range(-32, 33):
+            dy = dy0 + f32(j) * f32(2.0 ** -23)
+            tried += 1
+            if f32(f32(dx * dx) + f32(dy * dy)) == TH_H:
+                return f32(dx), f32(dy), tried
+    return None, None, tried
+
+
+def search_f_boundary(span=1 << 16):
+    """d with fl(d*d) == 3.841f: with F_SIDEWAYS and sigma 1 the match (0, d, 0, 0) has num = d, den = 1 and chiSquare == th in both
+    directions.  Around sqrt(3.841) consecutive floats d are 2^-23 apart and their squares about 1.96 ulp of 3.841f apart, so only
+    about every second float of that range is a square of a float at all.  All floats d within `span` ulps of sqrt(3.841) are tried.
+    -> (d or None, the largest d with fl(d*d) < th, the smallest d with fl(d*d) > th)"""
+    d0 = f32(np.sqrt(float(TH_F)))
+    d = d0 + np.arange(-span, span + 1, dtype=np.float64).astype(f32) * f32(2.0 ** -23)
+    sq = (d * d).astype(f32)
+    hit = d[sq == TH_F]
+    return (f32(hit[0]) if len(hit) else None), f32(d[sq < TH_F].max()), f32(d[sq > TH_F].min())
+
+
+I_B_IDENT, I_B_ONE_DIR, I_B_W0_H21, I_B_W0_H12 = 0, 1, 2, 3          # the H hypotheses of the boundary set
+I_B_SIDE, I_B_ASYM, I_B_DEN0, I_B_ZERO = 0, 1, 2, 3                  # the F hypotheses
+M_H_AT, M_H_ABOVE, M_H_BELOW, M_F_BELOW, M_F_ABOVE, M_F_AT, M_F_ONE_DIR, M_W0_A, M_W0_B, M_DEN0 = range(10)
+_boundary = {}
+
+
+def boundary_set():
+    """-> dict(pts (12, 4), H21 (4, 9), H12 (4, 9), F21 (4, 9), facts).  Matches by index (M_*): the H threshold hit and its two
+    neighbours (dy one ulp up / down changes chiSquare by at least one ulp; the walk goes on until it does), the F threshold's two
+    neighbours and its hit where one exists, a match that is an inlier of I_B_ASYM in one direction only, two matches that put a w of
+    exactly 0 under I_B_W0_H21 / I_B_W0_H12, one that gives I_B_DEN0 a*a + b*b == 0, two ordinary ones."""
+    if _boundary:
+        return _boundary
+    dx, dy, tried = search_h_boundary()
+    assert dx is not None
+    chi = lambda a, b: f32(f32(a * a) + f32(b * b))
+    up = next(_ulp_walk(dy, k) for k in range(1, 64) if chi(dx, _ulp_walk(dy, k)) > TH_H)
+    dn = next(_ulp_walk(dy, -k) for k in range(1, 64) if chi(dx, _ulp_walk(dy, -k)) < TH_H)
+    assert chi(dx, up) == _ulp_walk(TH_H, 1) and chi(dx, dn) == _ulp_walk(TH_H, -1)
+    d_at, d_below, d_above = search_f_boundary()
+    pts = np.zeros((12, 4), f32)
+    pts[M_H_AT], pts[M_H_ABOVE], pts[M_H_BELOW] = (dx, dy, 0, 0), (dx, up, 0, 0), (dx, dn, 0, 0)
+    pts[M_F_BELOW], pts[M_F_ABOVE] = (0, d_below, 0, 0), (0, d_above, 0, 0)
+    pts[M_F_AT] = (0, d_at if d_at is not None else d_below, 0, 0)
+    # I_B_ASYM: l2 = (0, -1, u1/2 + v1) with a*a + b*b = 1, l1 = (1/2, 1, -v2) with 1.25: num = 2.125 both ways, 4.515625 > th >= 3.6125
+    pts[M_F_ONE_DIR] = (0.25, 2, 0, 0)
+    pts[M_W0_A], pts[M_W0_B] = (7, 3, 7.5, 3.25), (9, 4, 9.5, 4.25)
+    pts[M_DEN0] = (11, 5, 11.25, 5.5)
+    pts[10], pts[11] = (100, 50, 100.5, 50.25), (200, 80, 199.5, 80.5)
+    shift = np.array([1, 0, 10, 0, 1, 0, 0, 0, 1], f32)
+    w0_h21 = np.array([1, 0, 0, 0, 1, 0, 1, 0, -pts[M_W0_A, 0]], f32)      # h31 u1 + h32 v1 + h33 == 0 for M_W0_A
+    w0_h12 = np.array([1, 0, 0, 0, 1, 0, 1, 0, -pts[M_W0_B, 2]], f32)      # the same under H12 for M_W0_B's second point
+    H21 = np.stack([IDENTITY, IDENTITY, w0_h21, IDENTITY])
+    H12 = np.stack([IDENTITY, shift, IDENTITY, w0_h12])
+    asym = np.array([0, 0, 0, 0, 0, -1, 0.5, 1, 0], f32)
+    den0 = np.array([1, 0, -pts[M_DEN0, 0], 0, 1, -pts[M_DEN0, 1], 0, 0, 1], f32)   # a2 = u1 - u1, b2 = v1 - v1 for M_DEN0
+    F21 = np.stack([F_SIDEWAYS, asym, den0, np.zeros(9, f32)])
+    _boundary.update(pts=pts, H21=H21, H12=H12, F21=F21,
+                     facts=dict(h_pair=(dx, dy), h_tried=tried, f_at=d_at, f_below=d_below, f_above=d_above))
+    return _boundary
+
+
+# ---- the recorded outputs of the reference's own Initializer.cc (oracle/_ref/libos1_initializer.so) -------------------------------
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'os1_initializer_outputs.npz')
+
+
+def have_os1():
+    from oracle import pyoracle
+    return pyoracle.have_os1_initializer()
+
+
+_os1 = []
+
+
+def os1():
+    from oracle import pyoracle
+    if not _os1:
+        _os1.append(pyoracle.Os1Initializer())
+    return _os1[0]
+
+
+def os1_find(pts, sigma, H21=None, H12=None, F21=None):
+    """FindHomography / FindFundamental's selection (`currentScore > score`, from 0) over the given hypotheses, every score and the
+    winner's mask computed by the reference object's CheckHomography / CheckFundamental.  Asserts that no stub ran."""
+    o = os1()
+    pts = np.ascontiguousarray(pts, f32).reshape(-1, 4)
+    sh, sf = o.check_many(pts, sigma, H21, H12, F21)
+    r = Result()
+
+    def pick(scores):
+        score, best = f32(0), -1
+        for k, s in enumerate(scores):
+            if s > score:
+                score, best = s, k
+        return score, best
+
+    if sh is not None:
+        r.scores_h = sh
+        r.score_h, r.best_h = pick(sh)
+        r.inliers_h = np.zeros(len(pts), bool)
+        if r.best_h >= 0:
+            s, r.inliers_h = o.check_homography(pts, np.reshape(H21, (-1, 9))[r.best_h], np.reshape(H12, (-1, 9))[r.best_h], sigma)
+            assert same_scores(s, r.score_h)
+    if sf is not None:
+        r.scores_f = sf
+        r.score_f, r.best_f = pick(sf)
+        r.inliers_f = np.zeros(len(pts), bool)
+        if r.best_f >= 0:
+            s, r.inliers_f = o.check_fundamental(pts, np.reshape(F21, (-1, 9))[r.best_f], sigma)
+            assert same_scores(s, r.score_f)
+    assert o.stub_calls() == 0, 'an unreached member of Initializer.cc ran'
+    return r
+
+
+def boundary_masks(o, b):
+    """per hypothesis of the boundary set: (scores_h, masks_h, scores_f, masks_f) by the object o with check_homography / check_fundamental"""
+    K = len(b['H21'])
+    hs = [o.check_homography(b['pts'], b['H21'][k], b['H12'][k], SIGMA) for k in range(K)]
+    fs = [o.check_fundamental(b['pts'], b['F21'][k], SIGMA) for k in range(K)]
+    return (np.asarray([s for s, _ in hs], f32), np.stack([m for _, m in hs]), np.asarray([s for s, _ in fs], f32),
+            np.stack([m for _, m in fs]))
+
+
+class RefChecks:
+    """check_homography / check_fundamental of one hypothesis by the C++ restatement (its entries of the same shape)"""
+
+    def __init__(self, L):
+        self.L = L
+
+    def check_homography(self, pts, H21, H12, sigma):
+        pts = np.ascontiguousarray(pts, f32)
+        inl = np.zeros(max(len(pts), 1), np.uint8)
+        s = self.L.isr_check_homography(_p(pts), len(pts), _p(np.ascontiguousarray(H21, f32)), _p(np.ascontiguousarray(H12, f32)), sigma, _p(inl))
+        return f32(s), inl[:len(pts)].astype(bool)
+
+    def check_fundamental(self, pts, F21, sigma):
+        pts = np.ascontiguousarray(pts, f32)
+        inl = np.zeros(max(len(pts), 1), np.uint8)
+        s = self.L.isr_check_fundamental(_p(pts), len(pts), _p(np.ascontiguousarray(F21, f32)), sigma, _p(inl))
+        return f32(s), inl[:len(pts)].astype(bool)
+
+
+class NumpyChecks:
+    """the same by the numpy restatement"""
+
+    def check_homography(self, pts, H21, H12, sigma):
+        c1, c2, inl = np_terms_h(np.ascontiguousarray(pts, f32), H21, H12, sigma)
+        return ordered_sum(interleave(c1, c2)), inl
+
+    def check_fundamental(self, pts, F21, sigma):
+        c1, c2, inl = np_terms_f(np.ascontiguousarray(pts, f32), F21, sigma)
+        return ordered_sum(interleave(c1, c2)), inl
+
+
+def result_fields(r, n):
+    """a Result as arrays for the recording (absent model: nothing)"""
+    out = {}
+    for sfx in ('h', 'f'):
+        sc = getattr(r, 'scores_' + sfx)
+        if sc is None:
+            continue
+        out['scores_' + sfx] = np.asarray(sc, f32)
+        out['best_' + sfx] = np.asarray([getattr(r, 'best_' + sfx)], np.int32)
+        out['score_' + sfx] = np.asarray([getattr(r, 'score_' + sfx)], f32)
+        out['inliers_' + sfx] = np.packbits(np.asarray(getattr(r, 'inliers_' + sfx), bool))
+    return out
+
+
+def result_from_fields(d, n):
+    r = Result()
+    for sfx in ('h', 'f'):
+        if 'scores_' + sfx not in d:
+            continue
+        setattr(r, 'scores_' + sfx, d['scores_' + sfx])
+        setattr(r, 'best_' + sfx, int(d['best_' + sfx][0]))
+        setattr(r, 'score_' + sfx, f32(d['score_' + sfx][0]))
+        setattr(r, 'inliers_' + sfx, np.unpackbits(d['inliers_' + sfx])[:n].astype(bool))
+    return r
+
+
+def sweep_cases(L):
+    """[(key, pts, H21, H12, F21)]: the existing crafted hypotheses over the N / K sweep on both scenes, unchanged"""
+    out = []
+    for s, sets in scenes(L):
+        for n in SWEEP_N:
+            for name in ('k1', 'k3', 'k200', 'nothing'):
+                out.append(('%s/n%d/%s' % (s['name'], n, name), s['pts'][:n]) + tuple(sets[name]))
+    return out
+
+
+def golden_records(L):
+    """{'<case>|<field>': array} computed by the reference object now"""
+    out = {}
+    for key, pts, H21, H12, F21 in sweep_cases(L):
+        for f, a in result_fields(os1_find(pts, SIGMA, H21, H12, F21), len(pts)).items():
+            out['%s|%s' % (key, f)] = a
+    b = boundary_set()
+    sh, mh, sf, mf = boundary_masks(os1(), b)
+    assert os1().stub_calls() == 0
+    out.update({'boundary|scores_h': sh, 'boundary|masks_h': mh, 'boundary|scores_f': sf, 'boundary|masks_f': mf,
+                'boundary|pts': b['pts']})
+    return out
+
+
+_golden = []
+
+
+def golden():
+    """{case: {field: array}} of the recording, or None where the file is absent"""
+    if not _golden:
+        if not os.path.exists(GOLDEN):
+            return None
+        z = np.load(GOLDEN)
+        d = {}
+        for k in z.files:
+            case, f = k.rsplit('|', 1)
+            d.setdefault(case, {})[f] = z[k]
+        _golden.append(d)
+    return _golden[0]

@@ -156,6 +156,12 @@ def py_score_pairwise(v1, v2):
     return -(t[0] if t else 0.0) / 2.0
 
 
+# the comparisons PyRef can get wrong on purpose
+FLIPS = frozenset(['minc_ge', 'minc_round', 'si_gt', 'retain_ge', 'retain_double', 'loop_best0', 'best_ge', 'neigh11', 'acc_reorder',
+                   'loop_neigh_no_minc', 'reloc_neigh_minc', 'loop_neigh_no_query', 'ignore_query_id', 'connected_first', 'no_dedup',
+                   'order_by_index'])
+
+
 class PyKF:
     def __init__(self, k):
         self.index, self.mnId = k['index'], k['id']
@@ -167,8 +173,13 @@ class PyKF:
 
 
 class PyRef:
-    def __init__(self, scene):
+    """flip: names of comparisons to get WRONG on purpose (FLIPS below).  The crafted scenes' witnesses: a scene built for a boundary
+    must change its result when that boundary's comparison is flipped."""
+
+    def __init__(self, scene, flip=()):
         self.scene, self.scoring = scene, scene['scoring']
+        self.flip = frozenset(flip)
+        assert self.flip <= FLIPS, self.flip - FLIPS
         self.kfs = [PyKF(k) for k in scene['kfs']]
         for k, m in zip(scene['kfs'], self.kfs):
             m.connected = {self.kfs[i] for i in k['connected']}
@@ -222,34 +233,55 @@ class PyRef:
                 keys.setdefault(k.index, (w, add_seq[k.index]))
         return [i for i, _ in sorted(keys.items(), key=lambda e: e[1])]
 
-    @staticmethod
-    def _select(lScoreAndMatch, qid, query_attr, words_attr, score_attr, min_common, best0):
+    def _min_common(self, max_common):
+        x = np.float32(max_common) * np.float32(0.8)
+        return int(np.rint(x)) if 'minc_round' in self.flip else int(x)
+
+    def _above(self, words, min_common):
+        return words >= min_common if 'minc_ge' in self.flip else words > min_common
+
+    def _select(self, lScoreAndMatch, qid, query_attr, words_attr, score_attr, min_common, best0):
+        flip = self.flip
         lAcc, best_acc = [], np.float32(best0)
         for si, k in lScoreAndMatch:
             best_score, acc, best_kf = si, si, k
-            for k2 in k.covisible[:10]:
-                if getattr(k2, query_attr) != qid:
+            used = []
+            for k2 in k.covisible[:11 if 'neigh11' in flip else 10]:
+                if getattr(k2, query_attr) != qid and not (min_common is not None and 'loop_neigh_no_query' in flip):
                     continue
-                if min_common is not None and not getattr(k2, words_attr) > min_common:
+                if min_common is not None and 'loop_neigh_no_minc' not in flip and not getattr(k2, words_attr) > min_common:
+                    continue
+                if min_common is None and 'reloc_neigh_minc' in flip and not getattr(k2, words_attr) > self._reloc_min_common:
                     continue
                 acc = np.float32(acc + getattr(k2, score_attr))
-                if getattr(k2, score_attr) > best_score:
+                used.append(getattr(k2, score_attr))
+                if getattr(k2, score_attr) >= best_score if 'best_ge' in flip else getattr(k2, score_attr) > best_score:
                     best_kf, best_score = k2, getattr(k2, score_attr)
+            if 'acc_reorder' in flip and used:      # the neighbours first, the keyframe's own score last
+                acc = used[0]
+                for s2 in used[1:]:
+                    acc = np.float32(acc + s2)
+                acc = np.float32(acc + si)
             lAcc.append((acc, best_kf))
             if acc > best_acc:
                 best_acc = acc
-        retain = np.float32(np.float32(0.75) * best_acc)
+        retain = 0.75 * float(best_acc) if 'retain_double' in flip else np.float32(np.float32(0.75) * best_acc)
         out = []
         for acc, k in lAcc:
-            if acc > retain and k not in out:
+            if (acc >= retain if 'retain_ge' in flip else float(acc) > float(retain)) and (k not in out or 'no_dedup' in flip):
                 out.append(k)
+        if 'order_by_index' in flip:
+            out.sort(key=lambda k: k.index)
         return out
 
     def detect_loop(self, q, min_score):
         lst = []
         for w in q.words:
             for k in self.inv.get(w, []):
-                if k.mnLoopQuery != q.mnId:
+                if 'connected_first' in self.flip and k in q.connected:
+                    k.mnLoopWords = 1
+                    continue
+                if k.mnLoopQuery != q.mnId or ('ignore_query_id' in self.flip and k not in lst):
                     k.mnLoopWords = 0
                     if k not in q.connected:
                         k.mnLoopQuery = q.mnId
@@ -258,23 +290,23 @@ class PyRef:
         if not lst:
             return []
         max_common = max(k.mnLoopWords for k in lst)
-        min_common = int(np.float32(max_common) * np.float32(0.8))
+        min_common = self._min_common(max_common)
         sm = []
         for k in lst:
-            if k.mnLoopWords > min_common:
+            if self._above(k.mnLoopWords, min_common):
                 si = np.float32(py_score(self.scoring, q.bow, k.bow))
                 k.mLoopScore = si
-                if si >= min_score:
+                if si > min_score if 'si_gt' in self.flip else si >= min_score:
                     sm.append((si, k))
         if not sm:
             return []
-        return self._select(sm, q.mnId, 'mnLoopQuery', 'mnLoopWords', 'mLoopScore', min_common, min_score)
+        return self._select(sm, q.mnId, 'mnLoopQuery', 'mnLoopWords', 'mLoopScore', min_common, 0 if 'loop_best0' in self.flip else min_score)
 
     def detect_reloc(self, fid, bow):
         lst = []
         for w in sorted(bow):
             for k in self.inv.get(w, []):
-                if k.mnRelocQuery != fid:
+                if k.mnRelocQuery != fid or ('ignore_query_id' in self.flip and k not in lst):
                     k.mnRelocWords = 0
                     k.mnRelocQuery = fid
                     lst.append(k)
@@ -282,10 +314,10 @@ class PyRef:
         if not lst:
             return []
         max_common = max(k.mnRelocWords for k in lst)
-        min_common = int(np.float32(max_common) * np.float32(0.8))
+        min_common = self._reloc_min_common = self._min_common(max_common)
         sm = []
         for k in lst:
-            if k.mnRelocWords > min_common:
+            if self._above(k.mnRelocWords, min_common):
                 si = np.float32(py_score(self.scoring, bow, k.bow))
                 k.mRelocScore = si
                 sm.append((si, k))
@@ -523,3 +555,432 @@ def write_scene(scene, path):
                 fid, w, v = st[1], st[2], st[3]
             f.write(struct.pack('<2iQfi i', code[st[0]], kf, fid, ms, has_ms, len(w)))
             f.write(np.asarray(w, '<u4').tobytes() + np.asarray(v, '<f8').tobytes())
+
+
+# ---- crafted decision-boundary scenes -------------------------------------------------------------------------------------------
+# One scene per comparison of KeyFrameDatabase.cc.  Scores are exact, hand-chosen floats: with L1 scoring and positive values the score
+# of two vectors is the sum over their common words of the smaller value, so a query whose words all carry 1.0 scores a keyframe with
+# the sum of the keyframe's values on the common words.  Those values are dyadic and NOT normalised (orbfe_kfdb_add takes values as
+# given), every partial sum is exact in double and the total is a float.  Each scene carries
+#   scene['literal']   the expected result of every query step, in step order, written from the reference text, and
+#   scene['witness']   names of FLIPS: PyRef with that comparison flipped must NOT reproduce the scene (results or members).
+EPS = 2.0 ** -20
+F32 = np.float32
+N_WORDS_CRAFTED = 1000
+
+
+def ulps(x, n):
+    """the float n ulps above (n < 0: below) the float x"""
+    x = F32(x)
+    for _ in range(abs(n)):
+        x = np.nextafter(x, F32(np.inf if n > 0 else -np.inf), dtype=F32)
+    return x
+
+
+class _Crafted(_Builder):
+    def __init__(self, nq, scoring=L1):
+        super().__init__(N_WORDS_CRAFTED, scoring, 0)
+        self.q = list(range(10, 10 + nq))                 # the query's words, 1.0 each
+        self.fill = 500                                   # words no query has
+        self.scene['literal'], self.scene['witness'] = [], []
+
+    def raw(self, words, values, mnId=None):
+        i = len(self.scene['kfs'])
+        assert list(words) == sorted(set(words)) and len(words) == len(values) <= 64
+        self.scene['kfs'].append(dict(index=i, id=100 + i if mnId is None else mnId, words=np.asarray(words, np.uint32),
+                                      values=np.asarray(values, np.float64), connected=set(), covisible=[], bad=False))
+        return i
+
+    def fillers(self, n, value=0.5):
+        w = list(range(self.fill, self.fill + n))
+        self.fill += n
+        return w, [value] * n
+
+    def shares(self, score, common, nfill=3, fill_value=0.5):
+        """a keyframe whose L1 score with the query is exactly the float `score`, sharing the query words q[i], i in `common`"""
+        common = sorted(self.q[i] for i in common)
+        c = len(common)
+        assert F32(score) == score and score - (c - 1) * EPS > 0
+        fw, fv = self.fillers(nfill, fill_value)
+        return self.raw(common + fw, [float(score) - (c - 1) * EPS] + [EPS] * (c - 1) + fv)
+
+    def query_kf(self, mnId, connected=()):
+        k = self.raw(self.q, [1.0] * len(self.q), mnId)
+        self.scene['kfs'][k]['connected'] = set(connected)
+        return k
+
+    def cov(self, k, others):
+        self.scene['kfs'][k]['covisible'] = list(others)
+
+    def adds(self, *ks):
+        for k in ks:
+            self.step('add', k)
+
+    def reloc(self, fid, literal, words=None, values=None):
+        w = np.asarray(self.q if words is None else words, np.uint32)
+        v = np.ones(len(w)) if values is None else np.asarray(values, np.float64)
+        self.step('reloc', fid, w, v)
+        self.scene['literal'].append(list(literal))
+
+    def loop(self, kf, min_score, literal):
+        self.step('loop', kf, F32(min_score))
+        self.scene['literal'].append(list(literal))
+
+    def done(self, witness, **named):
+        self.scene['witness'] = list(witness)
+        self.scene['named'] = named
+        self.scene['probes'] = [(np.asarray(self.q, np.uint32), np.ones(len(self.q)))]
+        sc = finish(self.scene)
+        assert len(sc['kfs']) <= 32 and all(len(k['words']) <= 64 for k in sc['kfs'])
+        return sc
+
+
+def crafted_min_common(maxc):
+    """A. maxCommonWords = maxc: keyframes with exactly minc, minc + 1 and maxc common words (where those differ and are > 0), each
+    common word worth 1/64.  `> minCommonWords` is strict: the one with minc is listed and never scored."""
+    B = _Crafted(maxc + 2)
+    minc = (4 * maxc) // 5                                # int(maxc * 0.8f), asserted in tests/test_os1_kfdb_ref.py
+    counts = [c for c in (minc + 1, minc) if 0 < c < maxc] + [maxc]
+    ks = {}
+    for c in counts:                                      # added in this order: it is the order of every list they share
+        fw, fv = B.fillers(2)
+        ks[c] = B.raw(B.q[:c] + fw, [1.0 / 64] * c + fv)
+    ql = B.query_kf(9)
+    B.adds(*ks.values())
+    lit = [ks[c] for c in counts if c > minc]             # (minc + 1) / 64 > 0.75f * maxc / 64 for every maxc
+    B.reloc(1, lit)
+    B.loop(ql, 0.0, lit)
+    frac = (4 * maxc) % 5
+    witness = (['minc_ge'] if minc > 0 else []) + (['minc_round'] if frac >= 3 else [])
+    return B.done(witness, maxc=maxc, minc=minc, at_min=ks.get(minc), above_min=ks.get(minc + 1), at_max=ks[maxc])
+
+
+def crafted_min_score():
+    """B. si >= minScore: minScore equal to a keyframe's float score, one ulp above, one ulp below (three query keyframes with their own
+    ids: a repeated id would find every member stale)."""
+    B = _Crafted(4)
+    s = F32(0.3)
+    k = B.shares(s, (0, 1))
+    low = B.shares(F32(0.125), (0, 2))
+    q1, q2, q3 = B.query_kf(201), B.query_kf(202), B.query_kf(203)
+    B.adds(k, low)
+    B.loop(q1, s, [k])
+    B.loop(q2, ulps(s, 1), [])
+    B.loop(q3, ulps(s, -1), [k])
+    return B.done(['si_gt'], k=k, s=s)
+
+
+def crafted_retain():
+    """C. accScore > 0.75f * bestAccScore: 0.75f * 0.5 = 0.375 exactly; keyframes at 0.375 and one ulp either side."""
+    B = _Crafted(6)
+    best, eq, up, dn = B.shares(0.5, (0,)), B.shares(0.375, (1,)), B.shares(ulps(0.375, 1), (2,)), B.shares(ulps(0.375, -1), (3,))
+    ql = B.query_kf(9)
+    B.adds(best, eq, up, dn)
+    B.reloc(1, [best, up])
+    B.loop(ql, 0.0, [best, up])
+    return B.done(['retain_ge'], eq=eq)
+
+
+def crafted_retain_rounds():
+    """C. the float product rounds: best = 0.5 + 2^-24, 0.75 * best = 0.375 + 1.5 ulp, a tie that rounds to even: 0.375 + 2 ulp.  The
+    keyframe AT 0.375 + 2 ulp is not above it (it would be above the unrounded product); the one at + 3 ulp is."""
+    B = _Crafted(6)
+    best, at, above = B.shares(ulps(0.5, 1), (0,)), B.shares(ulps(0.375, 2), (1,)), B.shares(ulps(0.375, 3), (2,))
+    assert F32(0.75) * ulps(0.5, 1) == ulps(0.375, 2) and 0.75 * float(ulps(0.5, 1)) < float(ulps(0.375, 2))
+    ql = B.query_kf(9)
+    B.adds(best, at, above)
+    B.reloc(1, [best, above])
+    B.loop(ql, 0.0, [best, above])
+    return B.done(['retain_double'], at=at)
+
+
+def crafted_best_start():
+    """C. bestAccScore starts at minScore in the loop search and at 0 in relocalisation.  Dot-product scoring with one negative value:
+    k1 scores 0.5 and its neighbour k2 -0.25, so k1 accumulates 0.25, BELOW minScore = 0.5.  Loop: best stays 0.5, 0.25 is not above
+    0.375, nothing returns.  Relocalisation on the same vectors: best is 0.25 and k1 returns."""
+    B = _Crafted(2, scoring=DOT)
+    fw, fv = B.fillers(2)
+    k1 = B.raw(B.q[:1] + fw, [0.5] + fv)
+    fw, fv = B.fillers(2)
+    k2 = B.raw(B.q[1:2] + fw, [-0.25] + fv)
+    B.cov(k1, [k2])
+    ql = B.query_kf(9)
+    B.adds(k1, k2)
+    B.loop(ql, 0.5, [])
+    B.reloc(1, [k1])
+    return B.done(['loop_best0'], k1=k1, k2=k2)
+
+
+def crafted_neighbour_best():
+    """D. `mRelocScore > bestScore` is strict: a neighbour with an EQUAL score leaves pBestKF alone, one with a larger score moves it."""
+    B = _Crafted(5)
+    a, b, c, d = B.shares(0.5, (0,)), B.shares(0.5, (1,)), B.shares(0.5, (2,)), B.shares(0.75, (3,))
+    B.cov(a, [b])
+    B.cov(c, [d])
+    ql = B.query_kf(9)
+    B.adds(a, b, c, d)
+    # accumulated: a 1.0 (elects a), b 0.5, c 1.25 (elects d), d 0.75; retained above 0.9375: a's and c's entries
+    B.reloc(1, [a, d])
+    B.loop(ql, 0.0, [a, d])
+    return B.done(['best_ge'], a=a, d=d)
+
+
+def crafted_eleventh_neighbour():
+    """D. GetBestCovisibilityKeyFrames(10): ten covisibles that are not in the database, then an eleventh whose score would be
+    accumulated and would take pBestKF."""
+    B = _Crafted(3)
+    a, big = B.shares(0.5, (0,)), B.shares(0.625, (1,))
+    out = [B.shares(0.25, (2,)) for _ in range(10)]       # never added
+    B.cov(a, out + [big])
+    ql = B.query_kf(9)
+    B.adds(a, big)
+    B.reloc(1, [a, big])
+    B.loop(ql, 0.0, [a, big])
+    return B.done(['neigh11'], a=a, big=big)
+
+
+def crafted_accumulation_order():
+    """D. accScore is a float and the neighbours are added one at a time: 0.5 + 2^-25 + 2^-25 is 0.5 (each add is a tie that rounds to
+    even); the neighbours first would give 0.5 + 2^-24, the threshold of crafted_retain_rounds, and b would drop out."""
+    B = _Crafted(5)
+    a, n1, n2, b = B.shares(0.5, (0,)), B.shares(2.0 ** -25, (1,)), B.shares(2.0 ** -25, (2,)), B.shares(ulps(0.375, 1), (3,))
+    B.cov(a, [n1, n2])
+    ql = B.query_kf(9)
+    B.adds(a, n1, n2, b)
+    B.reloc(1, [a, b])
+    B.loop(ql, 0.0, [a, b])
+    return B.done(['acc_reorder'], a=a, b=b)
+
+
+def _own_words_query(B, n):
+    """the words of keyframe n that no other vector has (its fillers), 1.0 each: a query about n alone"""
+    k = B.scene['kfs'][n]
+    w = [int(x) for x in k['words'] if int(x) >= 500]
+    return w, [1.0] * len(w)
+
+
+def crafted_loop_neighbour_min_common():
+    """D, loop only.  A neighbour that is listed by this query with exactly minCommonWords words: not scored now, and its mLoopScore of
+    an earlier query (0.25) is NOT accumulated, because the loop search repeats `mnLoopWords > minCommonWords` for neighbours."""
+    B = _Crafted(6)
+    a, b = B.shares(0.5, (0, 1, 2, 3, 4)), B.shares(ulps(0.375, 1), (0, 1, 2, 3, 5))
+    n = B.shares(0.125, (0, 1, 2, 3), nfill=2, fill_value=0.125)
+    B.cov(a, [n])
+    w, v = _own_words_query(B, n)
+    q0 = B.raw(w, v, mnId=300)
+    q1 = B.query_kf(301)
+    B.adds(a, b, n)
+    B.loop(q0, 0.0, [n])                                  # n alone, 2 of 2 words, scored 0.25
+    B.loop(q1, 0.0, [a, b])                               # a accumulates 0.5 only; with n's 0.25 the threshold would pass b
+    return B.done(['loop_neigh_no_minc'], a=a, b=b, n=n)
+
+
+def crafted_reloc_neighbour_stale_score():
+    """D, relocalisation.  The same vectors: relocalisation has no such test, so the neighbour that is listed, not scored, and carries
+    the mRelocScore of the earlier frame (0.25) IS accumulated: a reaches 0.75 and b is no longer above 0.75f of it."""
+    B = _Crafted(6)
+    a, b = B.shares(0.5, (0, 1, 2, 3, 4)), B.shares(ulps(0.375, 1), (0, 1, 2, 3, 5))
+    n = B.shares(0.125, (0, 1, 2, 3), nfill=2, fill_value=0.125)
+    B.cov(a, [n])
+    w, v = _own_words_query(B, n)
+    B.adds(a, b, n)
+    B.reloc(1, [n], w, v)
+    B.reloc(2, [a])
+    return B.done(['reloc_neigh_minc'], a=a, b=b, n=n)
+
+
+def crafted_loop_neighbour_connected():
+    """D, loop.  A neighbour that is connected to the query keyframe is never given this query's id: its mnLoopQuery is that of the
+    earlier query, so its mLoopScore (0.25) is not accumulated although its mnLoopWords (1, reset at every encounter) is above
+    minCommonWords = 0."""
+    B = _Crafted(4)
+    a, n, b = B.shares(0.5, (0,)), B.shares(0.25, (1,)), B.shares(ulps(0.375, 1), (2,))
+    B.cov(a, [n])
+    q0, q1 = B.query_kf(400), B.query_kf(401, connected=[n])
+    B.adds(a, n, b)
+    B.loop(q0, 0.0, [a])                                  # a accumulates n: 0.75; b is not above 0.5625
+    B.loop(q1, 0.0, [a, b])                               # n is connected: a stays at 0.5, b is above 0.375
+    return B.done(['loop_neigh_no_query'], a=a, n=n, b=b)
+
+
+def crafted_same_id_twice():
+    """E. The same mnId / frame id twice in a row: the second query finds every member stale, resets and lists nobody and returns
+    nothing; the word counts double."""
+    B = _Crafted(3)
+    a, b = B.shares(0.5, (0, 1)), B.shares(0.5, (1, 2))
+    ql = B.query_kf(9)
+    B.adds(a, b)
+    B.reloc(5, [a, b])
+    B.reloc(5, [])
+    B.loop(ql, 0.0, [a, b])
+    B.loop(ql, 0.0, [])
+    B.reloc(6, [a, b])
+    return B.done(['ignore_query_id'], a=a, b=b)
+
+
+def crafted_connected_with_stale_id():
+    """E. Two query keyframes with the same mnId.  The first is connected to nobody and leaves its id in k.  The second IS connected to
+    k, but `mnLoopQuery != mnId` is tested before the connected set: k is not reset, and as n's neighbour it is accumulated with its
+    score of the first query and elected: a keyframe connected to the query keyframe is returned."""
+    B = _Crafted(3)
+    k, n = B.shares(0.5, (0,)), B.shares(0.25, (1,))
+    B.cov(n, [k])
+    q1, q2 = B.query_kf(7), B.query_kf(7, connected=[k])
+    B.adds(k)
+    B.loop(q1, 0.0, [k])
+    B.adds(n)
+    B.loop(q2, 0.0, [k])
+    return B.done(['connected_first'], k=k, n=n)
+
+
+def crafted_clear_and_readd():
+    """E. clear() empties the lists and leaves the keyframes' members alone: after a re-add the same frame id finds them stale."""
+    B = _Crafted(3)
+    a, b = B.shares(0.5, (0,)), B.shares(0.5, (1,))
+    ql = B.query_kf(9)
+    B.adds(a, b)
+    B.reloc(9, [a, b])
+    B.loop(ql, 0.0, [a, b])
+    B.step('clear')
+    B.reloc(9, [])                                        # nothing in the lists
+    B.adds(b, a)
+    B.reloc(9, [])                                        # stale
+    B.loop(ql, 0.0, [])
+    B.reloc(10, [a, b])                                   # a new id: a holds the query's first word, whatever the add order
+    return B.done(['ignore_query_id'], a=a, b=b)
+
+
+def crafted_duplicates():
+    """F. Two entries elect the same pBestKF (and its own entry is not retained): it is returned once."""
+    B = _Crafted(4)
+    a, b, c = B.shares(0.5, (0,)), B.shares(0.5, (1,)), B.shares(0.75, (2,))
+    B.cov(a, [c])
+    B.cov(b, [c])
+    ql = B.query_kf(9)
+    B.adds(a, b, c)
+    B.reloc(1, [c])
+    B.loop(ql, 0.0, [c])
+    return B.done(['no_dedup'], c=c)
+
+
+def crafted_tie_order():
+    """F. Two keyframes tied on their first common word come back in the order of that word's list: erase + re-add moves one behind."""
+    B = _Crafted(3)
+    a, b = B.shares(0.5, (0, 1)), B.shares(0.5, (0, 2))
+    B.adds(b, a)
+    B.reloc(1, [b, a])
+    B.step('erase', b)
+    B.adds(b)
+    B.reloc(2, [a, b])
+    return B.done(['order_by_index'], a=a, b=b)
+
+
+MAXC_RANGE = range(1, 41)
+
+
+def crafted_scenes():
+    sc = {'A_maxc%02d' % m: crafted_min_common(m) for m in MAXC_RANGE}
+    sc.update(B_min_score=crafted_min_score(), C_retain=crafted_retain(), C_retain_rounds=crafted_retain_rounds(),
+              C_best_start=crafted_best_start(), D_neighbour_best=crafted_neighbour_best(), D_eleventh=crafted_eleventh_neighbour(),
+              D_acc_order=crafted_accumulation_order(), D_loop_neigh_minc=crafted_loop_neighbour_min_common(),
+              D_reloc_neigh_stale=crafted_reloc_neighbour_stale_score(), D_loop_neigh_connected=crafted_loop_neighbour_connected(),
+              E_same_id=crafted_same_id_twice(), E_connected_stale_id=crafted_connected_with_stale_id(),
+              E_clear_readd=crafted_clear_and_readd(), F_duplicates=crafted_duplicates(), F_tie_order=crafted_tie_order())
+    return sc
+
+
+_CRAFTED = None
+
+
+def crafted():
+    global _CRAFTED
+    if _CRAFTED is None:
+        _CRAFTED = crafted_scenes()
+    return _CRAFTED
+
+
+def every_scene():
+    """the seeded scenes and the crafted ones, by name"""
+    d = dict(scenes())
+    d.update(crafted())
+    return d
+
+
+def trace(ref, scene):
+    """(results, members): the result of every step (None for a mutation) and all six members of every keyframe after every step"""
+    res, mem = [], []
+    for st in scene['steps']:
+        res.append(ref.step(st))
+        mem.append(ref.members())
+    return res, mem
+
+
+# ---- the recorded outputs of the reference's own KeyFrameDatabase.cc (oracle/_ref/libos1_kfdb.so) ----------------------------------
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'os1_kfdb_outputs.npz')
+
+
+def have_os1():
+    from oracle import pyoracle
+    return pyoracle.have_os1_kfdb()
+
+
+def os1_ref(scene):
+    from oracle import pyoracle
+    return pyoracle.Os1KeyFrameDatabase(scene)
+
+
+def encode_trace(res, mem):
+    """-> {field: array}: results as a flat int32 list (per step: -1 for a mutation, else the count, then the keyframe indices);
+    members as (steps, keyframes, 6) uint64"""
+    flat = []
+    for r in res:
+        flat += [-1] if r is None else [len(r)] + list(r)
+    return {'results': np.asarray(flat, np.int32), 'members': np.asarray(mem, np.uint64).reshape(len(mem), -1, 6)}
+
+
+def decode_trace(rec):
+    flat, res, i = rec['results'].tolist(), [], 0
+    while i < len(flat):
+        if flat[i] < 0:
+            res.append(None)
+            i += 1
+        else:
+            res.append(flat[i + 1:i + 1 + flat[i]])
+            i += 1 + flat[i]
+    return res, [[tuple(int(x) for x in k) for k in step] for step in rec['members']]
+
+
+def golden_records():
+    """{'<scene>|<field>': array} computed by the reference object now"""
+    out = {}
+    for name, scene in every_scene().items():
+        ref = os1_ref(scene)
+        for f, a in encode_trace(*trace(ref, scene)).items():
+            out['%s|%s' % (name, f)] = a
+        ref.close()
+    return out
+
+
+_GOLDEN = None
+
+
+def golden():
+    """{scene: (results, members)} of the recording, or None where the file is absent"""
+    global _GOLDEN
+    if _GOLDEN is None and os.path.exists(GOLDEN):
+        z = np.load(GOLDEN)
+        names = sorted({k.split('|')[0] for k in z.files})
+        _GOLDEN = {n: decode_trace({f: z['%s|%s' % (n, f)] for f in ('results', 'members')}) for n in names}
+    return _GOLDEN
+
+
+def write_expected(scene, res, mem, path):
+    """The file tests/cpp/kfdb_test.cpp reads beside a scene file: per step the recorded candidates and members of the reference."""
+    with open(path, 'wb') as f:
+        f.write(struct.pack('<2i', len(res), len(scene['kfs'])))
+        for r, m in zip(res, mem):
+            f.write(struct.pack('<i', -1 if r is None else len(r)))
+            if r:
+                f.write(np.asarray(r, '<i4').tobytes())
+            for k in m:
+                f.write(struct.pack('<QiIQiI', k[0], k[1], k[2], k[3], k[4], k[5]))
