@@ -214,7 +214,8 @@ int orbfe_extract_batch_collect_matched(orbfe_extractor* h, OrbfeKeyPoint* kps, 
  *   camera_mode 0 with (ndist == 0 or dist[0] == 0): the reference's identity case (Frame.cc:288, whatever the other coefficients
  *     are): the handle behaves exactly like one without a camera -- nothing is launched or allocated, xy_un equals the keypoints.
  *   camera_mode 1 (os1's equidistant fisheye): ORBFE_ERR_UNSUPPORTED, the handle stays as it was.  That model needs the host libm's
- *     double tan bit for bit; undistort those keypoints with orbfe_undistort_equidistant.
+ *     double tan bit for bit; orbfe_extractor_set_camera_equidistant (below) is the GPU route for it, orbfe_undistort_equidistant
+ *     the host function.
  * With a distorting camera set
  *   - orbfe_extract_undistorted / orbfe_extract_batch_collect_undistorted also return mvKeysUn: xy_un [nframes][cap][2] floats, row f
  *     = frame f in keypoint order (matches12 / nmatches of _collect_undistorted: as _collect_matched, or both NULL);
@@ -228,6 +229,22 @@ int orbfe_extract_batch_collect_matched(orbfe_extractor* h, OrbfeKeyPoint* kps, 
 int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, float fy, float cx, float cy, const float* dist,
                                int ndist);
 int orbfe_extractor_undistort(orbfe_extractor* h, float* xy, int n);
+
+/* os1's equidistant fisheye model (Frame::antidistorsionarProyeccionEquidistante, Frame.cc:355-384) on the GPU.  The reference's
+ * std::tan is not correctly rounded and cannot be restated; its result is rounded to float, though.  The kernel encloses tan with a
+ * proved bound and checks whether every double a libm with an error below 1 ULP could return gives the same two floats: it then
+ * writes them (bit for bit the reference's on any such libm).  The few points where they differ (measured 7.3e-8 per point, 3.6e-8 per coordinate) are recomputed
+ * with orbfe_undistort_equidistant on the host when the call returns or the batch is collected, and patched into the results: xy_un,
+ * the arena a resident frame is built from, and -- for a matched batch -- the match rows, which are then searched again on the host.
+ * Otherwise the handle behaves as one with a distorting pinhole camera: orbfe_extractor_undistort, orbfe_extract_undistorted,
+ * _collect_undistorted, _submit_matched and orbfe_frame_create_from_extract work unchanged.  Only while no batch is submitted.  A match
+ * chain whose previous batch was undistorted by another model, or by an equidistant camera with other intrinsics, starts over.
+ *   orbfe_extractor_undistort_verdict: the kernel's raw output for n points, nothing settled -- out [n][2]; undecided[i] = 1: the
+ *     host would settle point i (out holds the lowest candidate's floats, or the input when theta is outside (1e-8, 1.5]).
+ *   orbfe_extractor_equidistant_stats: stats[0] points settled on the host, [1] points whose value changed, [2] match rows redone. */
+int orbfe_extractor_set_camera_equidistant(orbfe_extractor* h, float fx, float fy, float cx, float cy);
+int orbfe_extractor_undistort_verdict(orbfe_extractor* h, const float* xy, int n, float* out, uint8_t* undecided);
+int orbfe_extractor_equidistant_stats(const orbfe_extractor* h, long long stats[3]);
 int orbfe_extract_undistorted(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, size_t stride_bytes, OrbfeKeyPoint* kps,
                               uint8_t* desc, int cap, int* n_out, float* xy_un);
 int orbfe_extract_batch_collect_undistorted(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, float* xy_un,
@@ -343,6 +360,9 @@ int orbfe_stream_bow_raw(orbfe_stream* s, int frame, const uint32_t** leaf_node,
  * nothing).  Streamed frames are then matched on mvKeysUn, and the frame pushed next has no predecessor.  orbfe_stream_xy_un returns
  * mvKeysUn of the LAST POPPED batch, [batch][orbfe_stream_capacity][2] floats, valid until the next pop. */
 int orbfe_stream_set_camera(orbfe_stream* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist);
+/* orbfe_extractor_set_camera_equidistant for every handle of the runner (same rules), and the handles' counters summed. */
+int orbfe_stream_set_camera_equidistant(orbfe_stream* s, float fx, float fy, float cx, float cy);
+int orbfe_stream_equidistant_stats(orbfe_stream* s, long long stats[3]);
 int orbfe_stream_xy_un(orbfe_stream* s, const float** xy_un);
 /* Per-frame output capacity (keypoints) of the arrays returned by orbfe_stream_pop = their row stride.  It grows when a
  * push brings frames of a geometry that can return more keypoints (orbfe_extractor_max_keypoints_for_size); such a push
@@ -1099,6 +1119,8 @@ int orbfe_stream_multi_pop(orbfe_stream_multi* s, const OrbfeKeyPoint** kps, con
 int orbfe_stream_multi_set_camera(orbfe_stream_multi* s, int camera_mode, float fx, float fy, float cx, float cy, const float* dist,
                                   int ndist);
 int orbfe_stream_multi_xy_un(orbfe_stream_multi* s, const float** xy_un);
+int orbfe_stream_multi_set_camera_equidistant(orbfe_stream_multi* s, float fx, float fy, float cx, float cy);
+int orbfe_stream_multi_equidistant_stats(orbfe_stream_multi* s, long long stats[3]);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,11 @@ class ORBextractor {
   std::vector<float> inline GetScaleSigmaSquares() { return impl_.GetScaleSigmaSquares(); }
   std::vector<float> inline GetInverseScaleSigmaSquares() { return impl_.GetInverseScaleSigmaSquares(); }
 
+  // A Frame with camaraModo == 1 (os1's equidistant fisheye): the undistortion of the keypoints runs on the GPU behind the extraction
+  // (orb_shim.hpp, Extractor::SetEquidistantCamera); impl() gives access to extractUndistorted and the resident-frame lookup.
+  void SetEquidistantCamera(float fx, float fy, float cx, float cy) { impl_.SetEquidistantCamera(fx, fy, cx, cy); }
+  orbfe::Extractor& impl() { return impl_; }
+
   std::vector<cv::Mat> mvImagePyramid;  // ORBextractor.h:245; no external reader in the reference
 
  private:

@@ -120,11 +120,22 @@ class Extractor {
   // The camera of the Frames built from this extractor's output (Frame.cc:284-319): with a distorting pinhole model the
   // undistortion runs on the GPU behind the descriptor kernel, extractUndistorted() hands mvKeysUn out with mvKeys, and the
   // resident frame of such a Frame takes its coordinates from the arena (MatcherContext::resident sends none).  camera_mode 1
-  // (equidistant) throws: orbfe_extractor_set_camera refuses it, Frames of such cameras keep orbfe::UndistortKeyPoints.
+  // (equidistant) throws: orbfe_extractor_set_camera refuses it; SetEquidistantCamera is the call for such a camera.
   void SetCamera(int camera_mode, float fx, float fy, float cx, float cy, const float* dist, int ndist) {
     std::lock_guard<std::mutex> g(mu_);
     check(orbfe_extractor_set_camera(h_, camera_mode, fx, fy, cx, cy, dist, ndist));
     camActive_ = ndist > 0 && dist[0] != 0.0f;
+    lastValid_ = false;
+  }
+
+  // The same for os1's equidistant fisheye model (camaraModo == 1, Frame.cc:355-384): orbfe_extractor_set_camera_equidistant.
+  // extractUndistorted() then returns what orbfe::UndistortKeyPoints(.., camaraModo 1, ..) computes on the host, bit for bit (the
+  // kernel certifies the rounding of every point it can, the library settles the rest with the host's tan before the call returns),
+  // and the resident frame takes the coordinates from the arena.  ComputeImageBounds stays the host function.
+  void SetEquidistantCamera(float fx, float fy, float cx, float cy) {
+    std::lock_guard<std::mutex> g(mu_);
+    check(orbfe_extractor_set_camera_equidistant(h_, fx, fy, cx, cy));
+    camActive_ = true;
     lastValid_ = false;
   }
 

@@ -126,6 +126,13 @@ def load_library():
     L.orbfe_extractor_set_blur_variant.argtypes = [vp, ci]
     L.orbfe_extractor_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
     L.orbfe_extractor_undistort.argtypes = [vp, vp, ci]
+    L.orbfe_extractor_set_camera_equidistant.argtypes = [vp, cf, cf, cf, cf]
+    L.orbfe_extractor_undistort_verdict.argtypes = [vp, vp, ci, vp, vp]
+    L.orbfe_extractor_equidistant_stats.argtypes = [vp, vp]
+    L.orbfe_stream_set_camera_equidistant.argtypes = [vp, cf, cf, cf, cf]
+    L.orbfe_stream_equidistant_stats.argtypes = [vp, vp]
+    L.orbfe_stream_multi_set_camera_equidistant.argtypes = [vp, cf, cf, cf, cf]
+    L.orbfe_stream_multi_equidistant_stats.argtypes = [vp, vp]
     L.orbfe_stream_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
     L.orbfe_stream_xy_un.argtypes = [vp, C.POINTER(vp)]
     L.orbfe_stream_multi_set_camera.argtypes = [vp, ci, cf, cf, cf, cf, vp, ci]
@@ -328,8 +335,27 @@ class Extractor:
         d = np.ascontiguousarray(dist, np.float32)
         _check(self.L.orbfe_extractor_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
 
+    def set_camera_equidistant(self, fx, fy, cx, cy):
+        """os1's equidistant fisheye model on the GPU for later calls: certified rounding in the kernel, the few undecided points
+        settled with the host's std::tan (orbfe_extractor_set_camera_equidistant)."""
+        _check(self.L.orbfe_extractor_set_camera_equidistant(self.h, fx, fy, cx, cy))
+
+    def undistort_verdict(self, xy):
+        """The equidistant kernel's raw output on (n, 2) float32 points, nothing settled -> (xy, undecided flags)."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out, flags = np.zeros_like(xy), np.zeros(len(xy), np.uint8)
+        _check(self.L.orbfe_extractor_undistort_verdict(self.h, _p(xy) if len(xy) else None, len(xy), _p(out) if len(xy) else None,
+                                                        _p(flags) if len(xy) else None))
+        return out, flags.astype(bool)
+
+    def equidistant_stats(self):
+        """[points settled on the host, points whose value changed, match rows redone] of this handle."""
+        out = np.zeros(3, np.int64)
+        _check(self.L.orbfe_extractor_equidistant_stats(self.h, _p(out)))
+        return out
+
     def undistort(self, xy):
-        """The undistortion kernel on (n, 2) float32 points, with the camera of set_camera."""
+        """The undistortion kernel on (n, 2) float32 points, with the camera of set_camera / set_camera_equidistant."""
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2).copy()
         _check(self.L.orbfe_extractor_undistort(self.h, _p(xy) if len(xy) else None, len(xy)))
         return xy
@@ -1698,6 +1724,16 @@ class Stream:
         d = np.ascontiguousarray(dist, np.float32)
         _check(self.L.orbfe_stream_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
 
+    def set_camera_equidistant(self, fx, fy, cx, cy):
+        """orbfe_stream_set_camera_equidistant: the fisheye model, same rules as set_camera."""
+        _check(self.L.orbfe_stream_set_camera_equidistant(self.h, fx, fy, cx, cy))
+
+    def equidistant_stats(self):
+        """[points settled on the host, points whose value changed, match rows redone], summed over the runner's handles."""
+        out = np.zeros(3, np.int64)
+        _check(self.L.orbfe_stream_equidistant_stats(self.h, _p(out)))
+        return out
+
     def xy_un(self):
         """mvKeysUn [B, cap, 2] of the last popped batch (a copy)."""
         p = C.c_void_p()
@@ -1795,6 +1831,15 @@ class MultiStream:
         """orbfe_stream_multi_set_camera: every runner and the boundary pairs match on mvKeysUn; only while no batch is in flight."""
         d = np.ascontiguousarray(dist, np.float32)
         _check(self.L.orbfe_stream_multi_set_camera(self.h, mode, fx, fy, cx, cy, _p(d) if len(d) else None, len(d)))
+
+    def set_camera_equidistant(self, fx, fy, cx, cy):
+        """orbfe_stream_multi_set_camera_equidistant: the fisheye model for every runner."""
+        _check(self.L.orbfe_stream_multi_set_camera_equidistant(self.h, fx, fy, cx, cy))
+
+    def equidistant_stats(self):
+        out = np.zeros(3, np.int64)
+        _check(self.L.orbfe_stream_multi_equidistant_stats(self.h, _p(out)))
+        return out
 
     def xy_un(self):
         """mvKeysUn [B, cap, 2] of the last popped batch (a copy)."""

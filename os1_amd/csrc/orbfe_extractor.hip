@@ -55,6 +55,7 @@ int bow_assemble(orbfe_vocabulary* v, const uint2* ln, int n, uint32_t* bow_ids,
 int bow_device(const orbfe_vocabulary* v);
 void launch_sfi(const SfiParams& S, int nframes, hipStream_t st);
 void launch_undistort(const UndistortArgs& A, hipStream_t st);
+void launch_undistort_equidistant(const EquidistantArgs& A, hipStream_t st);
 void launch_sfi_carry(const SfiParams& S, int lastFrame, SelKp* cSel, float* cAngle, uint8_t* cDesc, uint32_t* cCount, float* cXyUn,
                       hipStream_t st);
 
@@ -143,6 +144,13 @@ struct orbfe_sfi_chain {
   std::vector<OrbfeKeyPoint> hostPrevKps;
   std::vector<uint8_t> hostPrevDesc;
   bool hostPrevValid = false;
+  // equidistant camera, GPU route: the settled predecessor on the host (a collect that patched a point redoes match rows there), and
+  // "the device carry holds a value the settle changed": the next collected batch redoes its row 0 on the host
+  std::vector<OrbfeKeyPoint> eqPrevKps;   // coordinates = mvKeysUn
+  std::vector<uint8_t> eqPrevDesc;
+  bool eqPrevValid = false, eqCarryStale = false;
+  bool equi = false;                      // the last batch was undistorted by the equidistant model, with these intrinsics: a batch
+  float eqCam[4] = {0, 0, 0, 0};          // of another model, or of another equidistant camera, starts the chain over
   ~orbfe_sfi_chain() {
     (void)hipSetDevice(device);
     if (hostMatcher) orbfe_matcher_destroy(hostMatcher);
@@ -245,6 +253,24 @@ struct orbfe_extractor {
   bool lastCam = false, submitCam = false;   // the last collected / submitted batch carries mvKeysUn
   DevBuf<float> d_unTmp;                     // orbfe_extractor_undistort and the host-quadtree route: points of the caller
   PinBuf<float> h_unTmp;
+  // orbfe_extractor_set_camera_equidistant: k_undistort_equidistant in k_undistort's place (camActive is then set too).  The
+  // kernel's undecided points (equidistant_tan.h) are settled on the host with orbfe_undistort_equidistant when the batch is
+  // collected: in the host arena, in the device arena (resident frames read it) and, for a matched batch, in the match rows.
+  bool camEqui = false, submitEqui = false;
+  EquidistantCamera camE{};
+  float camF[4] = {0, 0, 0, 0};              // fx fy cx cy as given
+  View<uint32_t> d_undec, h_undec;           // [1 + kUndecidedCap] counter and list of the submitted batch, in the arena
+  DevBuf<uint32_t> d_undecTmp;               // the same for undistortPoints
+  PinBuf<uint32_t> h_undecTmp;
+  DevBuf<uint8_t> d_flagTmp;
+  PinBuf<uint8_t> h_flagTmp;
+  long long eqStats[3] = {0, 0, 0};          // points settled, points whose value changed, match rows redone
+  std::vector<uint8_t> eqFrameChanged;
+  std::vector<float> eqXy;
+  std::vector<OrbfeKeyPoint> eqUn;
+  std::vector<int32_t> eqRow;
+  orbfe_sfi_chain* submitChain = nullptr;
+  bool submitHasPred = false;
   DevBuf<uint16_t> d_sfiOrder;
   DevBuf<int> d_sfiOrderCount;
   DevBuf<uint32_t> d_sfiPool, d_sfiPcount;
@@ -573,7 +599,8 @@ struct orbfe_extractor {
                      oSel = oSc + al256(sizeof(uint32_t) * kMaxLevels * nframes), oAng = oSel + al256(sizeof(SelKp) * maxKp),
                      oDesc = oAng + al256(sizeof(float) * maxKp), oM12 = oDesc + al256(32 * maxKp),
                      oNm = oM12 + al256(sizeof(int32_t) * (size_t)(selOff[1] - selOff[0]) * nframes), oXy = oNm + al256(sizeof(int32_t) * nframes),
-                     total = oXy + (camActive ? al256(2 * sizeof(float) * maxKp) : 0);
+                     oUd = oXy + (camActive ? al256(2 * sizeof(float) * maxKp) : 0),
+                     total = oUd + (camEqui ? al256(sizeof(uint32_t) * (1 + kUndecidedCap)) : 0);
         if ((rc = d_outArena.ensure(total))) return rc;
         if ((rc = h_outArena.ensure(total))) return rc;
         outArenaBytes = total;
@@ -586,6 +613,7 @@ struct orbfe_extractor {
         d_m12.p = (int32_t*)(D + oM12); h_m12.p = (int32_t*)(Hh + oM12);
         d_nm.p = (int32_t*)(D + oNm); h_nm.p = (int32_t*)(Hh + oNm);
         d_xyUn.p = camActive ? (float*)(D + oXy) : nullptr; h_xyUn.p = camActive ? (float*)(Hh + oXy) : nullptr;
+        d_undec.p = camEqui ? (uint32_t*)(D + oUd) : nullptr; h_undec.p = camEqui ? (uint32_t*)(Hh + oUd) : nullptr;
       }
       if (gpuQuadtree) {
         if ((rc = d_own.ensure((size_t)P.candCap * nframes))) return rc;
@@ -683,6 +711,7 @@ struct orbfe_extractor {
   // assembled on the host.  Runs the stored coefficients whatever they are (the identity case is the CALLERS' to skip).
   int undistortPoints(float* xy, int n) {
     if (n <= 0) return ORBFE_OK;
+    if (camEqui) return equidistantPoints(xy, n, nullptr, nullptr);
     int rc;
     if ((rc = d_unTmp.ensure(2 * (size_t)n)) || (rc = h_unTmp.ensure(2 * (size_t)n))) return rc;
     hipStream_t st = streams[0];
@@ -698,12 +727,128 @@ struct orbfe_extractor {
     return ORBFE_OK;
   }
 
+  // k_undistort_equidistant on n points of the caller.  flags == nullptr: in place, undecided points settled on the host (what
+  // orbfe_extractor_undistort returns).  flags != nullptr: the kernel's raw output into `out`, nothing settled.
+  int equidistantPoints(float* xy, int n, float* out, uint8_t* flags) {
+    if (n <= 0) return ORBFE_OK;
+    int rc;
+    const size_t words = 1 + kUndecidedCap;
+    if ((rc = d_unTmp.ensure(2 * (size_t)n)) || (rc = h_unTmp.ensure(2 * (size_t)n)) || (rc = d_undecTmp.ensure(words)) ||
+        (rc = h_undecTmp.ensure(words)) || (rc = d_flagTmp.ensure((size_t)n)) || (rc = h_flagTmp.ensure((size_t)n)))
+      return rc;
+    hipStream_t st = streams[0];
+    memcpy(h_unTmp.p, xy, 2 * sizeof(float) * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(d_unTmp.p, h_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_undecTmp.p, 0, sizeof(uint32_t) * words, st));
+    EquidistantArgs U{};
+    U.cam = camE; U.in = d_unTmp.p; U.sel = nullptr; U.selCount = nullptr; U.out = d_unTmp.p; U.n = n;
+    U.undecided = d_undecTmp.p; U.flags = d_flagTmp.p;
+    launch_undistort_equidistant(U, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_unTmp.p, d_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_undecTmp.p, d_undecTmp.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_flagTmp.p, d_flagTmp.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (flags) {
+      memcpy(out, h_unTmp.p, 2 * sizeof(float) * (size_t)n);
+      memcpy(flags, h_flagTmp.p, (size_t)n);
+      return ORBFE_OK;
+    }
+    const uint32_t cnt = h_undecTmp.p[0];
+    const bool all = cnt > (uint32_t)kUndecidedCap;   // the list overflowed: settle the whole launch
+    for (uint32_t k = 0; k < (all ? (uint32_t)n : cnt); k++) {
+      const uint32_t i = all ? k : h_undecTmp.p[1 + k];
+      float p[2] = {xy[2 * (size_t)i], xy[2 * (size_t)i + 1]};
+      if ((rc = orbfe_undistort_equidistant(p, 1, camF[0], camF[1], camF[2], camF[3]))) return rc;
+      eqStats[0]++;
+      if (memcmp(p, h_unTmp.p + 2 * (size_t)i, sizeof p)) { memcpy(h_unTmp.p + 2 * (size_t)i, p, sizeof p); eqStats[1]++; }
+    }
+    memcpy(xy, h_unTmp.p, 2 * sizeof(float) * (size_t)n);
+    return ORBFE_OK;
+  }
+
+  // The submitted batch's undecided slots, after the wait: the host's own std::tan decides them.
+  int settleEquidistant(int nframes) {
+    eqFrameChanged.assign(nframes, 0);
+    const uint32_t cnt = h_undec.p[0];
+    if (!cnt) return ORBFE_OK;
+    const uint32_t nslots = (uint32_t)nframes * (uint32_t)selPerFrame;
+    const bool all = cnt > (uint32_t)kUndecidedCap;
+    bool patched = false;
+    for (uint32_t k = 0; k < (all ? nslots : cnt); k++) {
+      const uint32_t i = all ? k : h_undec.p[1 + k];
+      if (i >= nslots) continue;
+      const int f = (int)(i / (uint32_t)selPerFrame), sl = (int)(i - (uint32_t)f * (uint32_t)selPerFrame);
+      int l = 0;
+      for (int q = 1; q < nlevels; q++) l += sl >= selOff[q];
+      if ((uint32_t)(sl - selOff[l]) >= h_selCount.p[(size_t)f * kMaxLevels + l]) continue;   // dead slot
+      const SelKp s = h_sel.p[i];
+      float p[2] = {(float)(s.xy & 0xffff), (float)(s.xy >> 16)};
+      if (l != 0) { p[0] *= sf[l]; p[1] *= sf[l]; }
+      int rc;
+      if ((rc = orbfe_undistort_equidistant(p, 1, camF[0], camF[1], camF[2], camF[3]))) return rc;
+      eqStats[0]++;
+      float* slot = h_xyUn.p + 2 * (size_t)i;
+      if (!memcmp(p, slot, sizeof p)) continue;
+      memcpy(slot, p, sizeof p);   // (the latency route's arena IS this page-locked memory)
+      eqStats[1]++;
+      eqFrameChanged[f] = 1;
+      if (!submitZeroCopy) { HIP_TRY(hipMemcpyAsync(d_xyUn.p + 2 * (size_t)i, slot, sizeof p, hipMemcpyHostToDevice, streams[0])); patched = true; }
+    }
+    if (patched) HIP_TRY(hipStreamSynchronize(streams[0]));
+    return ORBFE_OK;
+  }
+
+  // A matched batch of an equidistant handle, after output assembly.  The GPU searched on the kernel's provisional values: when the
+  // settle changed a point of frame f, rows f and f + 1 are searched again on the host (pairs are independent: vbPrevMatched := F1's
+  // mvKeysUn each time), and when it changed one of the PREVIOUS batch's last frame (eqCarryStale: the device carry this batch read)
+  // row 0 is.  kps / xy: the assembled frames ([nframes][cap]).
+  int rematchEquidistant(int nframes, const OrbfeKeyPoint* kps, const uint8_t* desc, int cap, const int* n_out, const float* xy,
+                         int32_t* matches12, int* nmatches) {
+    orbfe_sfi_chain& ch = *submitChain;
+    bool any = false;
+    for (int f = 0; f < nframes; f++) any = any || eqFrameChanged[f];
+    const bool stale = ch.eqCarryStale;
+    ch.eqCarryStale = eqFrameChanged[nframes - 1] != 0 && !ch.isolated;
+    eqUn.assign(kps, kps + (size_t)nframes * cap);
+    for (int f = 0; f < nframes; f++)
+      for (int j = 0; j < n_out[f]; j++) { eqUn[(size_t)f * cap + j].x = xy[((size_t)f * cap + j) * 2]; eqUn[(size_t)f * cap + j].y = xy[((size_t)f * cap + j) * 2 + 1]; }
+    int rc = ORBFE_OK;
+    if ((any || stale) && matches12 && nmatches) {
+      if (!ch.hostMatcher && (rc = orbfe_matcher_create(device, &ch.hostMatcher))) return rc;
+      for (int f = 0; f < nframes; f++) {   // a row takes part when one of its two frames changed
+        if (f == 0 && !((stale || eqFrameChanged[0]) && submitHasPred && ch.eqPrevValid)) continue;
+        if (f > 0 && !(eqFrameChanged[f - 1] || eqFrameChanged[f])) continue;
+        const OrbfeKeyPoint* k1 = f ? eqUn.data() + (size_t)(f - 1) * cap : ch.eqPrevKps.data();
+        const uint8_t* d1 = f ? desc + (size_t)(f - 1) * cap * 32 : ch.eqPrevDesc.data();
+        const int n1 = f ? n_out[f - 1] : (int)ch.eqPrevKps.size();
+        eqXy.resize((size_t)std::max(n1, 1) * 2);
+        for (int j = 0; j < n1; j++) { eqXy[2 * j] = k1[j].x; eqXy[2 * j + 1] = k1[j].y; }
+        eqRow.assign((size_t)std::max(n1, 1), -1);
+        int nm = 0;
+        if ((rc = orbfe_search_for_initialization(ch.hostMatcher, k1, d1, n1, eqUn.data() + (size_t)f * cap, desc + (size_t)f * cap * 32, n_out[f],
+                                                  submitMs.bounds, eqXy.data(), eqRow.data(), submitMs.window, submitMs.nnratio, submitMs.checkOri, &nm)))
+          return rc;
+        int32_t* row = matches12 + (size_t)f * cap;
+        for (int i = 0; i < cap; i++) row[i] = i < n1 ? eqRow[i] : -1;
+        nmatches[f] = nm;
+        eqStats[2]++;
+      }
+    }
+    const int last = nframes - 1;
+    ch.eqPrevKps.assign(eqUn.begin() + (size_t)last * cap, eqUn.begin() + (size_t)last * cap + n_out[last]);
+    ch.eqPrevDesc.assign(desc + (size_t)last * cap * 32, desc + ((size_t)last * cap + n_out[last]) * 32);
+    ch.eqPrevValid = !ch.isolated;
+    return rc;
+  }
+
   bool submitProfiled = false, fastTimed = false;
   std::vector<const uint8_t*> devAt;   // device address of every uploaded host frame (uploadFrames)
   int pendingFrames = 0;   // frames of the submitted, not yet collected batch (0 = none)
   double tSubmit0 = 0, tSubmit1 = 0;
 
   struct MatchSpec { orbfe_sfi_chain* chain; float bounds[4]; int window; float nnratio; int checkOri; };
+  MatchSpec submitMs{};
 
   int submitGpuQt(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride,
                   const MatchSpec* ms = nullptr) {
@@ -852,14 +997,28 @@ struct orbfe_extractor {
     }
     const int nslots = nframes * selPerFrame;
     submitCam = camActive;
+    submitEqui = camEqui;
     if (camActive) {   // mvKeysUn of every live slot (Frame.cc:284-319), where the other results go
-      UndistortArgs U{};
-      U.cam = cam; U.in = nullptr; U.sel = d_sel.p; U.selCount = d_selCount.p;
-      U.out = zeroCopy ? h_xyUn.p : d_xyUn.p;
-      U.n = nslots; U.selPerFrame = selPerFrame; U.nlevels = nlevels;
-      for (int l = 0; l <= nlevels; l++) U.selOff[l] = selOff[l];
-      for (int l = 0; l < nlevels; l++) U.sf[l] = sf[l];
-      launch_undistort(U, st);
+      UndistortSlots S{};
+      S.in = nullptr; S.sel = d_sel.p; S.selCount = d_selCount.p;
+      S.out = zeroCopy ? h_xyUn.p : d_xyUn.p;
+      S.n = nslots; S.selPerFrame = selPerFrame; S.nlevels = nlevels;
+      for (int l = 0; l <= nlevels; l++) S.selOff[l] = selOff[l];
+      for (int l = 0; l < nlevels; l++) S.sf[l] = sf[l];
+      if (camEqui) {
+        HIP_TRY(hipMemsetAsync(d_undec.p, 0, sizeof(uint32_t) * (1 + kUndecidedCap), st));
+        EquidistantArgs E{};
+        static_cast<UndistortSlots&>(E) = S;
+        E.cam = camE; E.undecided = d_undec.p; E.flags = nullptr;
+        launch_undistort_equidistant(E, st);
+        // (the counter and the list are always written in HBM; the routes that skip the arena copy fetch them on their own)
+        if (zeroCopy || kernelOut) HIP_TRY(hipMemcpyAsync(h_undec.p, d_undec.p, sizeof(uint32_t) * (1 + kUndecidedCap), hipMemcpyDeviceToHost, st));
+      } else {
+        UndistortArgs U{};
+        static_cast<UndistortSlots&>(U) = S;
+        U.cam = cam;
+        launch_undistort(U, st);
+      }
       HIP_TRY(hipGetLastError());
       if (kernelOut) HIP_TRY(hipMemcpyAsync(h_xyUn.p, d_xyUn.p, 2 * sizeof(float) * (size_t)nslots, hipMemcpyDeviceToHost, st));
     }
@@ -871,7 +1030,20 @@ struct orbfe_extractor {
       pendingBow = true;
     }
     pendingMatched = false;
+    submitChain = nullptr;
     if (ms && ms->chain) {
+      submitChain = ms->chain;
+      submitMs = *ms;
+      {   // a carry written under another model, or under another equidistant camera, is no predecessor
+        orbfe_sfi_chain& c = *ms->chain;
+        if (c.equi != camEqui || (camEqui && memcmp(c.eqCam, camF, sizeof camF))) {
+          if (c.seq > 0) c.restart = true;
+          c.eqPrevValid = c.eqCarryStale = false;
+        }
+        c.equi = camEqui;
+        memcpy(c.eqCam, camF, sizeof camF);
+      }
+      submitHasPred = !(ms->chain->seq == 0 || ms->chain->isolated || ms->chain->restart);
       // SearchForInitialization of every frame against its predecessor, on the data that is already in HBM
       orbfe_sfi_chain& ch = *ms->chain;
       const int n0cap = selOff[1] - selOff[0];
@@ -969,6 +1141,12 @@ struct orbfe_extractor {
       }
     }
     int status = ORBFE_OK;
+    if (submitEqui && (status = settleEquidistant(nframes))) return status;
+    std::vector<float> xyOwn;
+    if (submitEqui && pendingMatched && !xy_un) {   // the re-match below needs mvKeysUn of the assembled keypoints
+      xyOwn.resize((size_t)nframes * cap * 2);
+      xy_un = xyOwn.data();
+    }
     if (pendingBow) bowKp.resize(nframes);
     else bowKp.clear();
     for (int f = 0; f < nframes; f++) {
@@ -1023,6 +1201,10 @@ struct orbfe_extractor {
         }
         for (int i = pendingMatched ? m : 0; i < cap; i++) row[i] = -1;
       }
+    }
+    if (submitEqui && pendingMatched && status == ORBFE_OK) {
+      const int rc = rematchEquidistant(nframes, kps, desc, cap, n_out, xy_un, matches12, nmatches);
+      if (rc) return rc;
     }
     const double t3 = now_ms();
     stageMs[0] = (float)(t1 - t0);   // enqueue
@@ -1722,7 +1904,8 @@ int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, fl
   if (!h || ndist < 0 || ndist > 8 || (ndist && !dist) || (camera_mode != 0 && camera_mode != 1)) { set_err("bad camera"); return ORBFE_ERR_INVALID; }
   if (camera_mode == 1) {
     set_err("the equidistant model needs the host libm's double tan bit for bit, which no GPU restatement reproduces: "
-            "undistort those keypoints with orbfe_undistort_equidistant on the host");
+            "orbfe_extractor_set_camera_equidistant certifies the rounding on the GPU and settles the rest on the host "
+            "(or undistort those keypoints with orbfe_undistort_equidistant on the host)");
     return ORBFE_ERR_UNSUPPORTED;
   }
   if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
@@ -1731,10 +1914,35 @@ int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, fl
   C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy;
   C.ifx = 1. / C.fx; C.ify = 1. / C.fy;
   const bool active = ndist > 0 && dist[0] != 0.0f;
-  if (active != h->camActive) h->batchCap = 0;   // the result arena is carved again, with or without mvKeysUn
+  if (active != h->camActive || h->camEqui) h->batchCap = 0;   // the result arena is carved again, with or without mvKeysUn
+  h->camEqui = false;
   h->cam = C;
   h->camSet = true;
   h->camActive = active;
+  return ORBFE_OK;
+}
+
+int orbfe_extractor_set_camera_equidistant(orbfe_extractor* h, float fx, float fy, float cx, float cy) {
+  if (!h) { set_err("bad camera"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  if (!h->camActive || !h->camEqui) h->batchCap = 0;   // the result arena is carved again: mvKeysUn and the undecided list
+  h->camE = EquidistantCamera{fx, fy, cx, cy};
+  h->camF[0] = fx; h->camF[1] = fy; h->camF[2] = cx; h->camF[3] = cy;
+  h->camSet = h->camActive = h->camEqui = true;
+  return ORBFE_OK;
+}
+
+int orbfe_extractor_undistort_verdict(orbfe_extractor* h, const float* xy, int n, float* out, uint8_t* undecided) {
+  if (!h || n < 0 || (n && (!xy || !out || !undecided))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  if (!h->camEqui) { set_err("the extractor has no equidistant camera (orbfe_extractor_set_camera_equidistant)"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(h->device));
+  return h->equidistantPoints(const_cast<float*>(xy), n, out, undecided);
+}
+
+int orbfe_extractor_equidistant_stats(const orbfe_extractor* h, long long stats[3]) {
+  if (!h || !stats) { set_err("NULL argument"); return ORBFE_ERR_INVALID; }
+  for (int i = 0; i < 3; i++) stats[i] = h->eqStats[i];
   return ORBFE_OK;
 }
 
@@ -1908,6 +2116,9 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
     const bool cam = h->camActive;
     if (cam != chain->camera) chain->hostPrevValid = false;   // the carry holds the other kind of coordinates
     chain->camera = cam;
+    if (chain->equi != h->camEqui || (h->camEqui && memcmp(chain->eqCam, h->camF, sizeof h->camF))) chain->hostPrevValid = false;
+    chain->equi = h->camEqui;
+    memcpy(chain->eqCam, h->camF, sizeof h->camF);
     std::vector<OrbfeKeyPoint> unKps, unPrev;
     if (cam) {
       unKps = h->defKps;

@@ -3,6 +3,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "equidistant_tan.h"
+
 namespace orbfe {
 
 constexpr int kMaxLevels = 12;
@@ -164,8 +166,7 @@ struct CameraModel {
 // One lane per point.  Slot mode (sel != nullptr): point i is slot i of the result arena -- its level follows from selOff, it is live
 // iff its index inside the level is below selCount, and its distorted position is the level-scaled pt of the collect path
 // (ORBextractor.cc:959-965).  Point mode (sel == nullptr): `in` holds n float pairs.
-struct UndistortArgs {
-  CameraModel cam;
+struct UndistortSlots {
   const float* in;
   const SelKp* sel;
   const uint32_t* selCount;   // [nframes][kMaxLevels]
@@ -173,6 +174,17 @@ struct UndistortArgs {
   int n, selPerFrame, nlevels;
   int selOff[kMaxLevels + 1];
   float sf[kMaxLevels];       // mvScaleFactor
+};
+struct UndistortArgs : UndistortSlots {
+  CameraModel cam;
+};
+// k_undistort_equidistant: the same two input forms.  `undecided` (device memory, zeroed before the launch): word 0 counts the
+// undecided points of the launch, words 1 .. kUndecidedCap list the first of them (point indices, in no particular order).
+constexpr int kUndecidedCap = 63;
+struct EquidistantArgs : UndistortSlots {
+  EquidistantCamera cam;
+  uint32_t* undecided;
+  uint8_t* flags;             // optional, n bytes: 1 = undecided (orbfe_extractor_undistort_verdict)
 };
 
 // ---- GPU quadtree (orbfe_quadtree.hip) -------------------------------------------------------------

@@ -404,6 +404,34 @@ int orbfe_stream_set_camera(orbfe_stream* s, int camera_mode, float fx, float fy
   return orbfe_sfi_chain_restart(s->chain);
 }
 
+// The equidistant (fisheye) model for every handle of the runner: as orbfe_stream_set_camera.
+int orbfe_stream_set_camera_equidistant(orbfe_stream* s, float fx, float fy, float cx, float cy) {
+  if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->idle()) { set_err("batches are still in flight or held"); return ORBFE_ERR_INVALID; }
+  for (orbfe_extractor* e : s->ext) {
+    const int rc = orbfe_extractor_set_camera_equidistant(e, fx, fy, cx, cy);
+    if (rc) return rc;
+  }
+  s->camera = true;
+  s->lastN = -1;
+  s->chainRows = s->chainCols = 0;
+  return orbfe_sfi_chain_restart(s->chain);
+}
+
+// orbfe_extractor_equidistant_stats summed over the runner's handles (batches popped so far)
+int orbfe_stream_equidistant_stats(orbfe_stream* s, long long stats[3]) {
+  if (!s || !stats) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  stats[0] = stats[1] = stats[2] = 0;
+  for (orbfe_extractor* e : s->ext) {
+    long long one[3];
+    const int rc = orbfe_extractor_equidistant_stats(e, one);
+    if (rc) return rc;
+    for (int i = 0; i < 3; i++) stats[i] += one[i];
+  }
+  return ORBFE_OK;
+}
+
 int orbfe_stream_xy_un(orbfe_stream* s, const float** xy_un) {
   if (!s || !xy_un) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
   if (s->popped < 0 || !s->slots[s->popped].camera || s->slots[s->popped].xyUn.empty()) {

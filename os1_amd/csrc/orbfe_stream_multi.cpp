@@ -314,6 +314,38 @@ int orbfe_stream_multi_set_camera(orbfe_stream_multi* s, int camera_mode, float 
   return ORBFE_OK;
 }
 
+int orbfe_stream_multi_set_camera_equidistant(orbfe_stream_multi* s, float fx, float fy, float cx, float cy) {
+  if (!s) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  long long next;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->pushSeq != s->popSeq) { set_err("batches are still in flight"); return ORBFE_ERR_INVALID; }
+    next = s->pushSeq;
+  }
+  release_held_batch(s);
+  for (auto* q : s->sub) {
+    int rc = orbfe_stream_set_camera_equidistant(q, fx, fy, cx, cy);
+    if (rc == ORBFE_OK) rc = orbfe_stream_set_isolated_batches(q, 1);
+    if (rc != ORBFE_OK) return rc;
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  s->noPredSeq = next;
+  return ORBFE_OK;
+}
+
+// orbfe_stream_equidistant_stats summed over the runners (the boundary pairs are matched on settled coordinates in the first place)
+int orbfe_stream_multi_equidistant_stats(orbfe_stream_multi* s, long long stats[3]) {
+  if (!s || !stats) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
+  stats[0] = stats[1] = stats[2] = 0;
+  for (auto* q : s->sub) {
+    long long one[3];
+    const int rc = orbfe_stream_equidistant_stats(q, one);
+    if (rc) return rc;
+    for (int i = 0; i < 3; i++) stats[i] += one[i];
+  }
+  return ORBFE_OK;
+}
+
 // mvKeysUn of the batch the caller holds (the last popped one): [batch][orbfe_stream_multi_capacity][2]
 int orbfe_stream_multi_xy_un(orbfe_stream_multi* s, const float** xy_un) {
   if (!s || !xy_un) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }

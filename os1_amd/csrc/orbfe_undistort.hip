@@ -13,20 +13,19 @@
 // the descriptor kernel would cost every caller occupancy.
 #include <hip/hip_runtime.h>
 
+#include "equidistant_tan.h"
 #include "orbfe_internal.h"
 
 namespace orbfe {
 
-__global__ __launch_bounds__(64) void k_undistort(UndistortArgs A) {
+// The distorted position of point i in either input form (UndistortSlots); false: a dead slot, nothing to write.
+__device__ __forceinline__ bool undistort_input(const UndistortSlots& A, int i, float& fu, float& fv) {
 #pragma clang fp contract(off)
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= A.n) return;
-  float fu, fv;
   if (A.sel) {
     const int f = i / A.selPerFrame, s = i - f * A.selPerFrame;
     int l = 0;
     for (int q = 1; q < A.nlevels; q++) l += s >= A.selOff[q];
-    if ((uint32_t)(s - A.selOff[l]) >= A.selCount[(long long)f * kMaxLevels + l]) return;   // dead slot
+    if ((uint32_t)(s - A.selOff[l]) >= A.selCount[(long long)f * kMaxLevels + l]) return false;   // dead slot
     const uint32_t xy = A.sel[i].xy;
     fu = (float)(xy & 0xffff);
     fv = (float)(xy >> 16);
@@ -35,6 +34,15 @@ __global__ __launch_bounds__(64) void k_undistort(UndistortArgs A) {
     fu = A.in[2 * (long long)i];
     fv = A.in[2 * (long long)i + 1];
   }
+  return true;
+}
+
+__global__ __launch_bounds__(64) void k_undistort(UndistortArgs A) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  float fu, fv;
+  if (!undistort_input(A, i, fu, fv)) return;
   const CameraModel& C = A.cam;
   const double u = fu, v = fv;
   double x = (u - C.cx) * C.ifx, y = (v - C.cy) * C.ify;
@@ -55,6 +63,32 @@ __global__ __launch_bounds__(64) void k_undistort(UndistortArgs A) {
   const double xx = C.fx * x + 0 * y + C.cx, yy = 0 * x + C.fy * y + C.cy, ww = 1. / (0 * x + 0 * y + 1);
   A.out[2 * (long long)i] = (float)(xx * ww);
   A.out[2 * (long long)i + 1] = (float)(yy * ww);
+}
+
+// The equidistant (fisheye) model of Frame::antidistorsionarProyeccionEquidistante (Frame.cc:355-384): equidistant_tan.h's verdict
+// per point.  A decided point's two floats are final.  An undecided one gets the lowest candidate's floats and its index appended to
+// the launch's list (the host settles it with its own std::tan): the counter keeps counting past the list's capacity, which tells
+// the host to settle the whole launch.  A separate kernel: the double-double series would cost the pinhole kernel its registers.
+__global__ __launch_bounds__(64) void k_undistort_equidistant(EquidistantArgs A) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  float fu, fv;
+  if (!undistort_input(A, i, fu, fv)) return;
+  float ox, oy;
+  const bool decided = equidistant_verdict(A.cam, fu, fv, &ox, &oy);
+  A.out[2 * (long long)i] = ox;
+  A.out[2 * (long long)i + 1] = oy;
+  if (A.flags) A.flags[i] = decided ? 0 : 1;
+  if (!decided) {
+    const uint32_t k = atomicAdd(A.undecided, 1u);
+    if (k < (uint32_t)kUndecidedCap) A.undecided[1 + k] = (uint32_t)i;
+  }
+}
+
+void launch_undistort_equidistant(const EquidistantArgs& A, hipStream_t st) {
+  if (A.n <= 0) return;
+  hipLaunchKernelGGL(k_undistort_equidistant, dim3((A.n + 63) / 64), dim3(64), 0, st, A);
 }
 
 void launch_undistort(const UndistortArgs& A, hipStream_t st) {
