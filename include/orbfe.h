@@ -1063,6 +1063,57 @@ int orbfe_search_for_triangulation(orbfe_matcher* m, const OrbfeKeyPoint* kps1_u
                                    float ex, float ey, const float* scale_factors2, const float* level_sigma2_2,
                                    int nlevels2, int check_orientation, int32_t* pairs_out, int* nmatches);
 
+/* The SearchForTriangulation loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-232: mpCurrentKeyFrame against
+ * each of up to 20 covisible neighbours) on RESIDENT keyframes, all neighbours in one call.  Keypoints and descriptor rows of
+ * every keyframe are read where its orbfe_frame holds them; what crosses the link per keyframe is its FeatureVector's feature
+ * list (4 bytes per feature) and its MapPoint flags (1 byte per keypoint).
+ *
+ * Why one call equals the loop.  Triangulating neighbour i's pairs gives keypoints of the current keyframe a MapPoint, and
+ * neighbour i + 1 skips those (ORBmatcher.cc:694-699).  That dependency is a mask and nothing more: each idx1 lies under one
+ * vocabulary node, vbMatched2 is never set, so the best idx2 of one idx1 depends on no other idx1 (:686-770).  The RAW row of
+ * neighbour k -- matches12 before the orientation histogram, computed with the flags at loop entry -- therefore holds the
+ * reference's entry for every idx1 that still has no MapPoint when the loop reaches k; the others only have to be dropped,
+ * BEFORE the histogram (:745-791), the one place where matches interact.  orbfe_triangulation_finish does that on the host.
+ * The contract: while the loop runs, the current keyframe's flags only grow, and a neighbour's own flags change only in its own
+ * iteration, after its search.
+ *
+ * One OrbfeTriangulationNeighbour per neighbour: its resident frame, has_mp2 [orbfe_frame_size(frame2)], its FeatureVector, F12
+ * row-major, the epipole (ex, ey) (:657-666), pKF2->mvScaleFactors / mvLevelSigma2 (nlevels2 in 1..16). */
+typedef struct OrbfeTriangulationNeighbour {
+  orbfe_frame* frame2;
+  const uint8_t* has_mp2;
+  const uint32_t *fv2_nodes, *fv2_offsets, *fv2_features;
+  int n_fv2;
+  float F12[9], ex, ey;
+  const float *scale_factors2, *level_sigma2_2;
+  int nlevels2;
+} OrbfeTriangulationNeighbour;
+/* matches12_raw: n_nb rows of n1 = orbfe_frame_size(frame1) entries; row k, entry idx1 = the neighbour's keypoint the search
+ * takes for idx1, or -1 where nothing matched or has_mp1[idx1] is set.  One upload, one launch, one download, one wait.
+ * n_nb == 0 is valid; a neighbour that shares no vocabulary node with frame1 yields a row of -1.  Everything is checked before
+ * anything is sent or written; ORBFE_ERR_INVALID names the neighbour for: a keypoint octave of frame2 outside [0, nlevels2), a
+ * feature index that is no keypoint of its frame, a frame on another device than m, nlevels2 outside 1..16.  ORBFE_ERR_OVERFLOW:
+ * a vocabulary node with more than 65 535 features of a neighbour. */
+int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orbfe_frame* frame1, const uint8_t* has_mp1,
+                                                const uint32_t* fv1_nodes, const uint32_t* fv1_offsets, const uint32_t* fv1_features,
+                                                int n_fv1, int n_nb, const OrbfeTriangulationNeighbour* neighbours,
+                                                int32_t* matches12_raw);
+/* Host only: one neighbour's result from its raw row, at the moment the loop reaches it.  In this order: entries whose
+ * has_mp1_now is set are dropped; the orientation histogram prunes the rest when check_orientation (kps1_un / kps2_un: the
+ * two keyframes' mvKeysUn, read for their angles; may be NULL otherwise); the pairs are written in ascending idx1 (capacity n1
+ * pairs) and *nmatches is the reference's return value -- exactly what orbfe_search_for_triangulation gives for has_mp1_now.
+ * has_mp1_initial: the flags the raw row was computed with.  If has_mp1_now CLEARS one of them the raw row lacks that keypoint:
+ * ORBFE_ERR_STALE, nothing written -- search that neighbour singly. */
+#define ORBFE_ERR_STALE (-7)     /* a raw triangulation row does not cover the flags it is finished with */
+int orbfe_triangulation_finish(const int32_t* matches12_raw_row, int n1, const uint8_t* has_mp1_initial, const uint8_t* has_mp1_now,
+                               int check_orientation, const OrbfeKeyPoint* kps1_un, const OrbfeKeyPoint* kps2_un, int n2,
+                               int32_t* pairs_out, int* nmatches);
+/* One neighbour: a batch of one, finished with the same flags.  orbfe_search_for_triangulation on resident keyframes. */
+int orbfe_search_for_triangulation_frames(orbfe_matcher* m, orbfe_frame* frame1, const uint8_t* has_mp1, const uint32_t* fv1_nodes,
+                                          const uint32_t* fv1_offsets, const uint32_t* fv1_features, int n_fv1,
+                                          const OrbfeTriangulationNeighbour* neighbour, int check_orientation,
+                                          const OrbfeKeyPoint* kps1_un, const OrbfeKeyPoint* kps2_un, int32_t* pairs_out, int* nmatches);
+
 /* void Frame::antidistorsionarProyeccionEquidistante(cv::Mat& puntos)  (src/Frame.cc:355-384): os1's
  * equidistant-fisheye keypoint undistortion (camera `modo: 1`), used by Frame::UndistortKeyPoints (:286-320) and
  * Frame::ComputeImageBounds (:322-353).  Host double-precision math on n (x, y) float pairs, in place; K is the

@@ -307,6 +307,7 @@ class MatcherContext {
   orbfe_matcher* get() const { return m_; }
   int device() const { return device_; }
   void setFrameCacheCapacity(size_t c) { cap_ = c; trim(); }
+  size_t frameCacheCapacity() const { return cap_; }           // a call that holds k frames at once needs k of them (TriangulationSearch.h)
   size_t residentFrames() const { return cache_.size(); }
   size_t residentUploads() const { return uploads_; }          // frames whose features crossed PCIe (orbfe_frame_create)
   size_t residentFromExtract() const { return fromExtract_; }  // frames taken from an extractor's arena (no upload)

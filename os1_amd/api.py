@@ -114,6 +114,9 @@ def load_library():
                                          C.POINTER(ci)]
     L.orbfe_search_for_triangulation.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, cf, cf,
                                                  vp, vp, ci, ci, vp, C.POINTER(ci)]
+    L.orbfe_search_for_triangulation_frames_batch.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp]
+    L.orbfe_triangulation_finish.argtypes = [vp, ci, vp, vp, ci, vp, vp, ci, vp, C.POINTER(ci)]
+    L.orbfe_search_for_triangulation_frames.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_extractor_max_keypoints_for_size.argtypes = [vp, ci, ci]
     L.orbfe_extractor_set_vocabulary.argtypes = [vp, vp, ci]
     L.orbfe_extract_bow_raw.argtypes = [vp, ci, vp, vp, ci, C.POINTER(ci)]
@@ -511,6 +514,34 @@ class Extractor:
         s = np.zeros_like(a)
         _check(self.L.orbfe_debug_sincos(self.h, _p(a), a.size, _p(c), _p(s)))
         return c, s
+
+
+ERR_STALE = -7      # ORBFE_ERR_STALE: a raw triangulation row does not cover the flags it is finished with
+
+
+class TriangulationNeighbour(C.Structure):
+    """OrbfeTriangulationNeighbour: one neighbour of Matcher.search_for_triangulation_frames_batch."""
+    _fields_ = [('frame2', C.c_void_p), ('has_mp2', C.c_void_p), ('fv2_nodes', C.c_void_p), ('fv2_offsets', C.c_void_p),
+                ('fv2_features', C.c_void_p), ('n_fv2', C.c_int), ('F12', C.c_float * 9), ('ex', C.c_float), ('ey', C.c_float),
+                ('scale_factors2', C.c_void_p), ('level_sigma2_2', C.c_void_p), ('nlevels2', C.c_int)]
+
+
+def triangulation_finish(raw_row, has_mp1_initial, has_mp1_now, check_ori, kps1, kps2, n2=None):
+    """One neighbour's SearchForTriangulation result from its raw row (Matcher.search_for_triangulation_frames_batch), with the
+    current keyframe's flags as they stand NOW: mask, then the orientation histogram, then the pairs -> (nmatches, pairs[n,2]).
+    Host only.  Raises OrbfeError with code ERR_STALE when has_mp1_now clears a flag has_mp1_initial had set."""
+    L = load_library()
+    raw = np.ascontiguousarray(raw_row, np.int32)
+    h0, h1 = np.ascontiguousarray(has_mp1_initial, np.uint8), np.ascontiguousarray(has_mp1_now, np.uint8)
+    assert len(h0) == len(raw) == len(h1)
+    k1 = None if kps1 is None else np.ascontiguousarray(kps1, KP_DTYPE)
+    k2 = None if kps2 is None else np.ascontiguousarray(kps2, KP_DTYPE)
+    n2 = len(k2) if n2 is None else int(n2)
+    pairs = np.full((max(len(raw), 1), 2), -1, np.int32)
+    nm = C.c_int(0)
+    _check(L.orbfe_triangulation_finish(_p(raw), len(raw), _p(h0), _p(h1), int(check_ori), None if k1 is None else _p(k1),
+                                        None if k2 is None else _p(k2), n2, _p(pairs), C.byref(nm)))
+    return nm.value, pairs[:nm.value]
 
 
 class Camera(C.Structure):
@@ -1149,6 +1180,52 @@ class Matcher:
                                                      _p(f1[2]), len(f1[0]), _p(kps2), _p(desc2), _p(h2), len(kps2),
                                                      _p(f2[0]), _p(f2[1]), _p(f2[2]), len(f2[0]), _p(F), ex, ey, _p(sc),
                                                      _p(sg), len(sc), int(check_ori), _p(pairs), C.byref(nm)))
+        return nm.value, pairs[:nm.value]
+
+    @staticmethod
+    def _tri_neighbours(neighbours):
+        """(ctypes array of OrbfeTriangulationNeighbour, the arrays it points into) from [(frame2, has_mp2, fv2, F12, ex, ey,
+        scale2, sigma2)]."""
+        arr = (TriangulationNeighbour * max(len(neighbours), 1))()
+        keep = []
+        for t, (frame2, has2, fv2, F12, ex, ey, scale2, sigma2) in zip(arr, neighbours):
+            h2 = np.ascontiguousarray(has2, np.uint8)
+            f2 = [np.ascontiguousarray(a, np.uint32) for a in fv2]
+            sc, sg = np.ascontiguousarray(scale2, np.float32), np.ascontiguousarray(sigma2, np.float32)
+            keep += [frame2, h2, f2, sc, sg]
+            t.frame2, t.has_mp2 = frame2.h, h2.ctypes.data
+            t.fv2_nodes, t.fv2_offsets, t.fv2_features, t.n_fv2 = f2[0].ctypes.data, f2[1].ctypes.data, f2[2].ctypes.data, len(f2[0])
+            t.F12 = (C.c_float * 9)(*[float(v) for v in np.asarray(F12, np.float32).reshape(9)])
+            t.ex, t.ey = float(ex), float(ey)
+            t.scale_factors2, t.level_sigma2_2, t.nlevels2 = sc.ctypes.data, sg.ctypes.data, len(sc)
+        return arr, keep
+
+    def search_for_triangulation_frames_batch(self, frame1, has_mp1, fv1, neighbours):
+        """The SearchForTriangulation loop of LocalMapping::CreateNewMapPoints on resident keyframes in ONE GPU submission:
+        frame1 (a Frame) against neighbours = [(frame2, has_mp2, fv2, F12, ex, ey, scale2, sigma2)].  Returns the raw rows
+        [len(neighbours), len(frame1)] int32: the neighbour's keypoint for idx1, or -1 (nothing matched, or has_mp1 set); finish
+        each row with triangulation_finish when the loop reaches its neighbour."""
+        h1 = np.ascontiguousarray(has_mp1, np.uint8)
+        f1 = [np.ascontiguousarray(a, np.uint32) for a in fv1]
+        arr, _keep = self._tri_neighbours(neighbours)
+        raw = np.full((len(neighbours), max(len(frame1), 1)), -1, np.int32)
+        _check(self.L.orbfe_search_for_triangulation_frames_batch(self.h, frame1.h, _p(h1), _p(f1[0]), _p(f1[1]), _p(f1[2]), len(f1[0]),
+                                                                  len(neighbours), C.cast(arr, C.c_void_p), _p(raw)))
+        return raw[:, :len(frame1)]
+
+    def search_for_triangulation_frames(self, frame1, has_mp1, fv1, neighbour, kps1=None, kps2=None, check_ori=True):
+        """ORBmatcher::SearchForTriangulation on two resident keyframes (a batch of one, finished with the same flags)
+        -> (nmatches, pairs[n,2]).  kps1 / kps2 (mvKeysUn, for their angles) are needed with check_ori."""
+        h1 = np.ascontiguousarray(has_mp1, np.uint8)
+        f1 = [np.ascontiguousarray(a, np.uint32) for a in fv1]
+        arr, _keep = self._tri_neighbours([neighbour])
+        k1 = None if kps1 is None else np.ascontiguousarray(kps1, KP_DTYPE)
+        k2 = None if kps2 is None else np.ascontiguousarray(kps2, KP_DTYPE)
+        pairs = np.full((max(len(frame1), 1), 2), -1, np.int32)
+        nm = C.c_int(0)
+        _check(self.L.orbfe_search_for_triangulation_frames(self.h, frame1.h, _p(h1), _p(f1[0]), _p(f1[1]), _p(f1[2]), len(f1[0]),
+                                                            C.cast(arr, C.c_void_p), int(check_ori), None if k1 is None else _p(k1),
+                                                            None if k2 is None else _p(k2), _p(pairs), C.byref(nm)))
         return nm.value, pairs[:nm.value]
 
     def search_by_bow(self, desc1, angle1, valid1, fv1, desc2, angle2, valid2, fv2, nnratio=0.7, check_ori=True,

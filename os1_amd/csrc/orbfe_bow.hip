@@ -28,9 +28,15 @@
 #include "../../include/orbfe.h"
 #include "bow_batch_plan.h"
 #include "hip_buffers.h"
+#include "tri_batch_plan.h"
 
 namespace orbfe {
 int gpu_readable(const void* p, int device);   // orbfe_frame.hip: 0 ordinary host memory, 1 page-locked, 2 this device's, -1 another's
+// orbfe_frame.hip: a resident frame's device arrays in keypoint order (none of these waits) and the stream order behind its build
+void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
+void frame_xy(const orbfe_frame* f, const float** x, const float** y);
+const uint8_t* frame_descriptor_rows(const orbfe_frame* f);
+void frame_wait_ready(orbfe_frame* f, hipStream_t st);
 int matcher_device(const orbfe_matcher* m);
 hipStream_t matcher_stream(const orbfe_matcher* m);
 std::shared_ptr<void>& matcher_bow_slot(orbfe_matcher* m);
@@ -596,6 +602,104 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyP
     }
   }
   done();
+}
+
+// A load through a pointer that the kernel itself read from memory (the per-neighbour table below): the compiler cannot tell
+// that it points to global memory and would emit a flat load; these say so.
+template <class T>
+__device__ __forceinline__ T gload(const T* p) { return *(const __attribute__((address_space(1))) T*)p; }
+__device__ __forceinline__ uint4 gload_row(const uint4* p) {
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  const v4u v = *(const __attribute__((address_space(1))) v4u*)p;
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// SearchForTriangulation of ONE keyframe against SEVERAL neighbours (the loop of LocalMapping::CreateNewMapPoints,
+// LocalMapping.cc:207-232), every keyframe a resident frame: one workgroup per (neighbour, common vocabulary node) record of
+// tri_batch_plan.h.  Keypoints (x, y, octave) and descriptor rows of both sides come from the frames' own device arrays; what
+// the call uploaded is the record list, the feature lists, the MapPoint flags and one TriNeighbour per neighbour.  The
+// neighbour's index comes out of the record, the record's out of blockIdx: both are wave-uniform, so the record, the table
+// entry's pointers and F12 / ex / ey are scalar loads into SGPRs, paid once per wave; scale2 / sigma2 are indexed by a
+// candidate's octave and are vector loads of a 64-byte line that stays in the CU's cache.  The per-candidate rule is
+// k_bow_triangulate's (tri_candidate_key, epipolar_line), so are the two routes: nodes of up to kBowSide features per side from
+// LDS -- 23 KiB per workgroup, six workgroups per CU --, larger ones from global memory.  matches12[k * n1 + idx1] is written
+// where idx1 found a candidate; the host filled the rest with -1.  Side 1 is the same for every neighbour: the records are
+// sorted node-major, and what is read of the current keyframe -- 2 000 x (32 B descriptor row + x + y) = 80 KB -- fits every XCD's L2
+// many times over.
+struct TriNeighbour {
+  const float *x2, *y2;    // the neighbour's resident frame: mvKeysUn ...
+  const int* oct2;
+  const uint4* desc2;      // ... and mDescriptors, keypoint order
+  TriParams T;
+  uint32_t flag2;          // where its MapPoint flags start in the call's flag part
+};
+static_assert(sizeof(TriNeighbour) == 208 && sizeof(BowPair) == sizeof(orbfe::TriRecord), "table entry / record layout");
+__global__ void __launch_bounds__(kBowThreads) k_bow_triangulate_batch(const TriNeighbour* __restrict__ nbs, const BowPair* __restrict__ recs,
+                                                                       const float* __restrict__ x1g, const float* __restrict__ y1g,
+                                                                       const uint4* __restrict__ desc1, const uint8_t* __restrict__ hasMP1,
+                                                                       const uint32_t* __restrict__ feat1, const uint8_t* __restrict__ flags2,
+                                                                       const uint32_t* __restrict__ feat2, int32_t* __restrict__ matches12) {
+  __shared__ uint4 d1s[2 * kBowSide], d2s[2 * kBowSide];
+  __shared__ float x1s[kBowSide], y1s[kBowSide], x2s[kBowSide], y2s[kBowSide];
+  __shared__ uint32_t row1[kBowSide], row2[kBowSide];   // keypoint index | 0x80000000: has a MapPoint (skipped)
+  __shared__ int o2s[kBowSide];
+  const BowPair P = recs[blockIdx.x];   // (b2, e2: into feat2; base1: the neighbour's row of matches12; tk: the neighbour)
+  const TriNeighbour& N = nbs[P.tk];
+  const TriParams& T = N.T;
+  const float *x2g = N.x2, *y2g = N.y2;   // (read with gload: pointers that come out of memory are generic to the compiler)
+  const int* oct2 = N.oct2;
+  const uint4* desc2 = N.desc2;
+  const uint8_t* hasMP2 = flags2 + N.flag2;
+  int32_t* out = matches12 + (size_t)(unsigned)P.base1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n1g = P.e1 - P.b1, n2g = P.e2 - P.b2;
+  if (n1g <= kBowSide && n2g <= kBowSide) {
+    for (int i = tid; i < n1g; i += kBowThreads) {
+      const unsigned idx1 = feat1[P.b1 + i];
+      row1[i] = idx1 | (hasMP1[idx1] ? 0x80000000u : 0u);
+      d1s[2 * i] = desc1[2 * (size_t)idx1]; d1s[2 * i + 1] = desc1[2 * (size_t)idx1 + 1];
+      x1s[i] = x1g[idx1]; y1s[i] = y1g[idx1];
+    }
+    for (int i = tid; i < n2g; i += kBowThreads) {
+      const unsigned idx2 = feat2[P.b2 + i];
+      row2[i] = idx2 | (hasMP2[idx2] ? 0x80000000u : 0u);
+      d2s[2 * i] = gload_row(desc2 + 2 * (size_t)idx2); d2s[2 * i + 1] = gload_row(desc2 + 2 * (size_t)idx2 + 1);
+      x2s[i] = gload(x2g + idx2); y2s[i] = gload(y2g + idx2); o2s[i] = gload(oct2 + idx2);
+    }
+    __syncthreads();
+    for (int r = wave; r < n1g; r += kBowThreads / 64) {
+      const unsigned idx1 = row1[r];
+      if (idx1 & 0x80000000u) continue;   // wave-uniform
+      const uint4 a0 = d1s[2 * r], a1 = d1s[2 * r + 1];
+      float la, lb, lc, den;
+      epipolar_line(x1s[r], y1s[r], T, &la, &lb, &lc, &den);
+      unsigned key = 0xffffffffu;
+      for (int p = lane; p < n2g; p += 64) {
+        if (row2[p] & 0x80000000u) continue;
+        const int dist = hamming256(a0, a1, d2s[2 * p], d2s[2 * p + 1]);
+        key = min(key, tri_candidate_key(dist, x2s[p], y2s[p], o2s[p], p, la, lb, lc, den, T));
+      }
+      key = wave_min(key);
+      if (key != 0xffffffffu && lane == 0) out[idx1] = (int32_t)row2[(int)(0xffffu - (key & 0xffffu))];
+    }
+    return;
+  }
+  for (int i1 = P.b1 + wave; i1 < P.e1; i1 += kBowThreads / 64) {   // (a node too large for LDS: the same split, from global memory)
+    const unsigned idx1 = feat1[i1];
+    if (hasMP1[idx1]) continue;   // wave-uniform
+    const uint4 a0 = desc1[2 * (size_t)idx1], a1 = desc1[2 * (size_t)idx1 + 1];
+    float la, lb, lc, den;
+    epipolar_line(x1g[idx1], y1g[idx1], T, &la, &lb, &lc, &den);
+    unsigned key = 0xffffffffu;
+    for (int p = lane; p < n2g; p += 64) {
+      const unsigned idx2 = feat2[P.b2 + p];
+      if (hasMP2[idx2]) continue;
+      const int dist = hamming256(a0, a1, gload_row(desc2 + 2 * (size_t)idx2), gload_row(desc2 + 2 * (size_t)idx2 + 1));
+      key = min(key, tri_candidate_key(dist, gload(x2g + idx2), gload(y2g + idx2), gload(oct2 + idx2), p, la, lb, lc, den, T));
+    }
+    key = wave_min(key);
+    if (key != 0xffffffffu && lane == 0) out[idx1] = (int32_t)feat2[P.b2 + (int)(0xffffu - (key & 0xffffu))];
+  }
 }
 
 }  // namespace
@@ -1279,4 +1383,144 @@ extern "C" int orbfe_search_for_triangulation(orbfe_matcher* m, const OrbfeKeyPo
   }
   *nmatches = nm;
   return ORBFE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SearchForTriangulation on resident keyframes, all neighbours of CreateNewMapPoints in one call
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+orbfe::TriSide tri_side(orbfe_frame* f, const uint8_t* has_mp, const uint32_t* nodes, const uint32_t* offsets, const uint32_t* features, int n_fv) {
+  orbfe::TriSide s;
+  s.frame = f != nullptr;
+  if (f) {
+    const int* oct;
+    const float* angle;
+    s.device = orbfe_frame_device(f);
+    s.n = orbfe_frame_size(f);
+    orbfe::frame_source_arrays(f, &oct, &angle, &s.maxOctave);
+  }
+  s.has_mp = has_mp; s.nodes = nodes; s.offsets = offsets; s.features = features; s.n_fv = n_fv;
+  return s;
+}
+
+}  // namespace
+
+extern "C" int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orbfe_frame* frame1, const uint8_t* has_mp1,
+                                                           const uint32_t* fv1_nodes, const uint32_t* fv1_offsets,
+                                                           const uint32_t* fv1_features, int n_fv1, int n_nb,
+                                                           const OrbfeTriangulationNeighbour* neighbours, int32_t* matches12_raw) {
+  if (!m) { set_err("matcher is NULL"); return ORBFE_ERR_INVALID; }
+  const orbfe::TriSide s1 = tri_side(frame1, has_mp1, fv1_nodes, fv1_offsets, fv1_features, n_fv1);
+  std::vector<orbfe::TriSide> s2((size_t)std::max(n_nb, 0));
+  for (int k = 0; k < n_nb && neighbours; k++) {
+    const OrbfeTriangulationNeighbour& N = neighbours[k];
+    s2[k] = tri_side(N.frame2, N.has_mp2, N.fv2_nodes, N.fv2_offsets, N.fv2_features, N.n_fv2);
+    s2[k].nlevels = N.nlevels2;
+    s2[k].tables = N.scale_factors2 && N.level_sigma2_2;
+  }
+  orbfe::TriBatchPlan plan;
+  const int prc = orbfe::tri_batch_plan(orbfe::matcher_device(m), s1, n_nb, neighbours ? s2.data() : nullptr, sizeof(TriNeighbour), plan);
+  if (prc) { set_err("%s", plan.why); return prc; }
+  if (plan.entries == 0) return ORBFE_OK;
+  if (!matches12_raw) { set_err("matches12_raw is NULL"); return ORBFE_ERR_INVALID; }
+  const size_t rows = (size_t)plan.entries;
+  if (plan.records.empty()) {
+    for (size_t i = 0; i < rows; i++) matches12_raw[i] = -1;
+    return ORBFE_OK;
+  }
+  HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
+  std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
+  if (!slot) slot = std::make_shared<BowScratch>();
+  BowScratch* S = static_cast<BowScratch*>(slot.get());
+  hipStream_t st = orbfe::matcher_stream(m);
+  int rc;
+  if ((rc = S->h_arena.ensure(plan.bytes)) || (rc = S->d_arena.ensure(plan.bytes)) || (rc = S->d_m12.ensure(rows)) || (rc = S->h_m12.ensure(rows))) return rc;
+  // the upload image: [neighbour table | records | flags 1 | features 1 | flags 2 of every neighbour | features 2 of every neighbour]
+  uint8_t* H = S->h_arena.p;
+  TriNeighbour* tab = reinterpret_cast<TriNeighbour*>(H + plan.oTable);
+  for (int k = 0; k < n_nb; k++) {
+    const OrbfeTriangulationNeighbour& N = neighbours[k];
+    TriNeighbour& t = tab[k];
+    const float* angle;
+    int maxOctave;
+    orbfe::frame_xy(N.frame2, &t.x2, &t.y2);
+    orbfe::frame_source_arrays(N.frame2, &t.oct2, &angle, &maxOctave);
+    t.desc2 = reinterpret_cast<const uint4*>(orbfe::frame_descriptor_rows(N.frame2));
+    memcpy(t.T.F12, N.F12, sizeof t.T.F12);
+    t.T.ex = N.ex; t.T.ey = N.ey;
+    for (int i = 0; i < 16; i++) { t.T.scale2[i] = N.scale_factors2[std::min(i, N.nlevels2 - 1)]; t.T.sigma2[i] = N.level_sigma2_2[std::min(i, N.nlevels2 - 1)]; }
+    t.flag2 = plan.flag2[k];
+    if (s2[k].n) memcpy(H + plan.oFlag2 + plan.flag2[k], N.has_mp2, (size_t)s2[k].n);
+    const size_t nf2 = N.n_fv2 ? N.fv2_offsets[N.n_fv2] : 0;
+    if (nf2) memcpy(H + plan.oFeat2 + 4 * (size_t)plan.feat2[k], N.fv2_features, 4 * nf2);
+  }
+  memcpy(H + plan.oRecords, plan.records.data(), sizeof(orbfe::TriRecord) * plan.records.size());
+  memcpy(H + plan.oFlag1, has_mp1, (size_t)s1.n);
+  memcpy(H + plan.oFeat1, fv1_features, 4 * plan.nFeat1);
+  uint8_t* D = S->d_arena.p;
+  HIP_TRY(hipMemcpyAsync(D, H, plan.bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(S->d_m12.p, 0xff, sizeof(int32_t) * rows, st));
+  orbfe::frame_wait_ready(frame1, st);
+  for (int k = 0; k < n_nb; k++) orbfe::frame_wait_ready(neighbours[k].frame2, st);
+  const float *x1, *y1;
+  orbfe::frame_xy(frame1, &x1, &y1);
+  hipLaunchKernelGGL(k_bow_triangulate_batch, dim3((unsigned)plan.records.size()), dim3(kBowThreads), 0, st,
+                     reinterpret_cast<const TriNeighbour*>(D + plan.oTable), reinterpret_cast<const BowPair*>(D + plan.oRecords), x1, y1,
+                     reinterpret_cast<const uint4*>(orbfe::frame_descriptor_rows(frame1)), (const uint8_t*)(D + plan.oFlag1),
+                     reinterpret_cast<const uint32_t*>(D + plan.oFeat1), (const uint8_t*)(D + plan.oFlag2),
+                     reinterpret_cast<const uint32_t*>(D + plan.oFeat2), S->d_m12.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(S->h_m12.p, S->d_m12.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(matches12_raw, S->h_m12.p, sizeof(int32_t) * rows);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_triangulation_finish(const int32_t* matches12_raw_row, int n1, const uint8_t* has_mp1_initial,
+                                          const uint8_t* has_mp1_now, int check_orientation, const OrbfeKeyPoint* kps1_un,
+                                          const OrbfeKeyPoint* kps2_un, int n2, int32_t* pairs_out, int* nmatches) {
+  if (n1 < 0 || n2 < 0 || !nmatches || (n1 > 0 && (!matches12_raw_row || !has_mp1_initial || !has_mp1_now || !pairs_out)) ||
+      (check_orientation && ((n1 > 0 && !kps1_un) || (n2 > 0 && !kps2_un)))) {
+    set_err("bad argument");
+    return ORBFE_ERR_INVALID;
+  }
+  thread_local std::vector<int32_t> row;   // (scratch of the calling thread: CreateNewMapPoints finishes up to 20 rows per keyframe)
+  row.resize((size_t)n1);
+  int at = -1;
+  const int rc = orbfe::tri_finish_mask(matches12_raw_row, n1, has_mp1_initial, has_mp1_now, n2, row.data(), &at);
+  if (rc == orbfe::kTriFinishStale) {
+    set_err("keypoint %d had a MapPoint when the raw row was computed and has none now: the row does not cover it", at);
+    return ORBFE_ERR_STALE;
+  }
+  if (rc) { set_err("raw entry %d is no keypoint of the neighbour (n2 = %d)", at, n2); return ORBFE_ERR_INVALID; }
+  int nm = 0;
+  for (int i = 0; i < n1; i++) if (row[i] >= 0) nm++;
+  if (check_orientation && n1 > 0 && n2 > 0)
+    nm -= prune_by_orientation(&kps1_un[0].angle, sizeof(OrbfeKeyPoint), &kps2_un[0].angle, sizeof(OrbfeKeyPoint), n1, row.data());
+  int np = 0;
+  for (int i = 0; i < n1; i++) {   // vMatchedPairs in ascending idx1 (ORBmatcher.cc:792-800)
+    if (row[i] < 0) continue;
+    pairs_out[2 * np] = i;
+    pairs_out[2 * np + 1] = row[i];
+    np++;
+  }
+  *nmatches = nm;
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_search_for_triangulation_frames(orbfe_matcher* m, orbfe_frame* frame1, const uint8_t* has_mp1,
+                                                     const uint32_t* fv1_nodes, const uint32_t* fv1_offsets, const uint32_t* fv1_features,
+                                                     int n_fv1, const OrbfeTriangulationNeighbour* neighbour, int check_orientation,
+                                                     const OrbfeKeyPoint* kps1_un, const OrbfeKeyPoint* kps2_un, int32_t* pairs_out,
+                                                     int* nmatches) {
+  if (!neighbour || !nmatches) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
+  *nmatches = 0;
+  const int n1 = orbfe_frame_size(frame1), n2 = orbfe_frame_size(neighbour->frame2);
+  if (n1 > 0 && !pairs_out) { set_err("pairs_out is NULL"); return ORBFE_ERR_INVALID; }
+  if (check_orientation && ((n1 > 0 && !kps1_un) || (n2 > 0 && !kps2_un))) { set_err("check_orientation needs both keyframes' keypoints"); return ORBFE_ERR_INVALID; }
+  std::vector<int32_t> raw((size_t)std::max(n1, 1), -1);
+  int rc = orbfe_search_for_triangulation_frames_batch(m, frame1, has_mp1, fv1_nodes, fv1_offsets, fv1_features, n_fv1, 1, neighbour, raw.data());
+  if (rc || n1 == 0) return rc;
+  return orbfe_triangulation_finish(raw.data(), n1, has_mp1, has_mp1, check_orientation, kps1_un, kps2_un, n2, pairs_out, nmatches);
 }
