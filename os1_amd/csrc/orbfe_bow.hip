@@ -526,84 +526,6 @@ __device__ __forceinline__ unsigned tri_candidate_key(int dist, float x2, float 
   return ((unsigned)dist << 16) | (0xffffu - (unsigned)p);
 }
 
-// Round 3: a block of four waves per node.  Both feature lists with their flags, descriptors and keypoint coordinates are
-// fetched once into LDS (nodes of up to kBowSide features per side; from the page-locked arena directly on the route
-// without copy commands); the frame-1 features are independent (see above), so the four waves take every fourth one and
-// scan the node's frame-2 features from LDS.  Larger nodes: the same split, everything from global memory.
-__global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyPoint* __restrict__ kps1, const uint4* __restrict__ desc1,
-                                                                 const uint8_t* __restrict__ hasMP1, const uint32_t* __restrict__ feat1,
-                                                                 const OrbfeKeyPoint* __restrict__ kps2, const uint4* __restrict__ desc2,
-                                                                 const uint8_t* __restrict__ hasMP2, const uint32_t* __restrict__ feat2,
-                                                                 const BowPair* __restrict__ pairs, TriParams T,
-                                                                 int32_t* __restrict__ matches12, unsigned* doneCounter, int* doneHost,
-                                                                 int doneSeq) {
-  __shared__ uint4 d1s[2 * kBowSide], d2s[2 * kBowSide];
-  __shared__ float x1s[kBowSide], y1s[kBowSide], x2s[kBowSide], y2s[kBowSide];
-  __shared__ uint32_t row1[kBowSide], row2[kBowSide];   // descriptor row | 0x80000000: has a MapPoint (skipped)
-  __shared__ int o2s[kBowSide];
-  const BowPair P = pairs[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n1g = P.e1 - P.b1, n2g = P.e2 - P.b2;
-  auto done = [&]() {   // (every wave's stores are acknowledged before the block counts itself off)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (doneCounter && tid == 0) signal_last_block(doneCounter, doneHost, doneSeq);
-  };
-  if (n1g <= kBowSide && n2g <= kBowSide) {
-    for (int i = tid; i < n1g; i += kBowThreads) {
-      const unsigned idx1 = feat1[P.b1 + i];
-      row1[i] = idx1 | (hasMP1[idx1] ? 0x80000000u : 0u);
-      d1s[2 * i] = desc1[2 * (size_t)idx1]; d1s[2 * i + 1] = desc1[2 * (size_t)idx1 + 1];
-      x1s[i] = kps1[idx1].x; y1s[i] = kps1[idx1].y;
-    }
-    for (int i = tid; i < n2g; i += kBowThreads) {
-      const unsigned idx2 = feat2[P.b2 + i];
-      row2[i] = idx2 | (hasMP2[idx2] ? 0x80000000u : 0u);
-      d2s[2 * i] = desc2[2 * (size_t)idx2]; d2s[2 * i + 1] = desc2[2 * (size_t)idx2 + 1];
-      x2s[i] = kps2[idx2].x; y2s[i] = kps2[idx2].y; o2s[i] = kps2[idx2].octave;
-    }
-    __syncthreads();
-    for (int r = wave; r < n1g; r += kBowThreads / 64) {
-      const unsigned idx1 = row1[r];
-      if (idx1 & 0x80000000u) continue;   // wave-uniform
-      const uint4 a0 = d1s[2 * r], a1 = d1s[2 * r + 1];
-      const float x1 = x1s[r], y1 = y1s[r];
-      float la, lb, lc, den;
-      epipolar_line(x1, y1, T, &la, &lb, &lc, &den);
-      unsigned key = 0xffffffffu;
-      for (int p = lane; p < n2g; p += 64) {
-        if (row2[p] & 0x80000000u) continue;
-        const int dist = hamming256(a0, a1, d2s[2 * p], d2s[2 * p + 1]);
-        key = min(key, tri_candidate_key(dist, x2s[p], y2s[p], o2s[p], p, la, lb, lc, den, T));
-      }
-      key = wave_min(key);
-      if (key != 0xffffffffu && lane == 0) matches12[idx1] = (int32_t)row2[(int)(0xffffu - (key & 0xffffu))];
-    }
-    done();
-    return;
-  }
-  {   // (a node too large for LDS: the four waves still share its frame-1 features, everything comes from global memory)
-    for (int i1 = P.b1 + wave; i1 < P.e1; i1 += kBowThreads / 64) {
-      const unsigned idx1 = feat1[i1];
-      if (hasMP1[idx1]) continue;   // wave-uniform
-      const uint4 a0 = desc1[2 * (size_t)idx1], a1 = desc1[2 * (size_t)idx1 + 1];
-      const float x1 = kps1[idx1].x, y1 = kps1[idx1].y;
-      float la, lb, lc, den;
-      epipolar_line(x1, y1, T, &la, &lb, &lc, &den);
-      unsigned key = 0xffffffffu;
-      for (int p = lane; p < n2g; p += 64) {
-        const unsigned idx2 = feat2[P.b2 + p];
-        if (hasMP2[idx2]) continue;
-        const int dist = hamming256(a0, a1, desc2[2 * (size_t)idx2], desc2[2 * (size_t)idx2 + 1]);
-        key = min(key, tri_candidate_key(dist, kps2[idx2].x, kps2[idx2].y, kps2[idx2].octave, p, la, lb, lc, den, T));
-      }
-      key = wave_min(key);
-      if (key != 0xffffffffu && lane == 0) matches12[idx1] = (int32_t)feat2[P.b2 + (int)(0xffffu - (key & 0xffffu))];
-    }
-  }
-  done();
-}
-
 // A load through a pointer that the kernel itself read from memory (the per-neighbour table below): the compiler cannot tell
 // that it points to global memory and would emit a flat load; these say so.
 template <class T>
@@ -614,57 +536,63 @@ __device__ __forceinline__ uint4 gload_row(const uint4* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// SearchForTriangulation of ONE keyframe against SEVERAL neighbours (the loop of LocalMapping::CreateNewMapPoints,
-// LocalMapping.cc:207-232), every keyframe a resident frame: one workgroup per (neighbour, common vocabulary node) record of
-// tri_batch_plan.h.  Keypoints (x, y, octave) and descriptor rows of both sides come from the frames' own device arrays; what
-// the call uploaded is the record list, the feature lists, the MapPoint flags and one TriNeighbour per neighbour.  The
-// neighbour's index comes out of the record, the record's out of blockIdx: both are wave-uniform, so the record, the table
-// entry's pointers and F12 / ex / ey are scalar loads into SGPRs, paid once per wave; scale2 / sigma2 are indexed by a
-// candidate's octave and are vector loads of a 64-byte line that stays in the CU's cache.  The per-candidate rule is
-// k_bow_triangulate's (tri_candidate_key, epipolar_line), so are the two routes: nodes of up to kBowSide features per side from
-// LDS -- 23 KiB per workgroup, six workgroups per CU --, larger ones from global memory.  matches12[k * n1 + idx1] is written
-// where idx1 found a candidate; the host filled the rest with -1.  Side 1 is the same for every neighbour: the records are
-// sorted node-major, and what is read of the current keyframe -- 2 000 x (32 B descriptor row + x + y) = 80 KB -- fits every XCD's L2
-// many times over.
-struct TriNeighbour {
-  const float *x2, *y2;    // the neighbour's resident frame: mvKeysUn ...
-  const int* oct2;
-  const uint4* desc2;      // ... and mDescriptors, keypoint order
-  TriParams T;
-  uint32_t flag2;          // where its MapPoint flags start in the call's flag part
+// Where one side's keypoints come from: x, y, octave, the two halves of the descriptor row and the MapPoint flag of keypoint i.
+// TriAos: OrbfeKeyPoint records, rows and flags in the call's arena (orbfe_search_for_triangulation, host arrays).
+struct TriAos {
+  const OrbfeKeyPoint* __restrict__ kps;
+  const uint4* __restrict__ desc;
+  const uint8_t* __restrict__ hasMP;
+  __device__ __forceinline__ float x(unsigned i) const { return kps[i].x; }
+  __device__ __forceinline__ float y(unsigned i) const { return kps[i].y; }
+  __device__ __forceinline__ int octave(unsigned i) const { return kps[i].octave; }
+  __device__ __forceinline__ uint4 lo(unsigned i) const { return desc[2 * (size_t)i]; }
+  __device__ __forceinline__ uint4 hi(unsigned i) const { return desc[2 * (size_t)i + 1]; }
+  __device__ __forceinline__ bool flagged(unsigned i) const { return hasMP[i]; }
 };
-static_assert(sizeof(TriNeighbour) == 208 && sizeof(BowPair) == sizeof(orbfe::TriRecord), "table entry / record layout");
-__global__ void __launch_bounds__(kBowThreads) k_bow_triangulate_batch(const TriNeighbour* __restrict__ nbs, const BowPair* __restrict__ recs,
-                                                                       const float* __restrict__ x1g, const float* __restrict__ y1g,
-                                                                       const uint4* __restrict__ desc1, const uint8_t* __restrict__ hasMP1,
-                                                                       const uint32_t* __restrict__ feat1, const uint8_t* __restrict__ flags2,
-                                                                       const uint32_t* __restrict__ feat2, int32_t* __restrict__ matches12) {
+// TriResident: a resident frame's own x / y / octave arrays and descriptor rows; the flags are the call's.  Side 2's pointers
+// come out of the neighbour table, so every load goes through gload (for side 1's, kernel arguments, it changes nothing).
+struct TriResident {
+  const float *xs, *ys;
+  const int* oct;
+  const uint4* desc;
+  const uint8_t* __restrict__ hasMP;
+  __device__ __forceinline__ float x(unsigned i) const { return gload(xs + i); }
+  __device__ __forceinline__ float y(unsigned i) const { return gload(ys + i); }
+  __device__ __forceinline__ int octave(unsigned i) const { return gload(oct + i); }
+  __device__ __forceinline__ uint4 lo(unsigned i) const { return gload_row(desc + 2 * (size_t)i); }
+  __device__ __forceinline__ uint4 hi(unsigned i) const { return gload_row(desc + 2 * (size_t)i + 1); }
+  __device__ __forceinline__ bool flagged(unsigned i) const { return hasMP[i]; }
+};
+
+// The node search of both SearchForTriangulation kernels: a block of four waves per common vocabulary node P.  Both feature
+// lists with their flags, descriptors and keypoint coordinates are fetched once into LDS (nodes of up to kBowSide features per
+// side: 23 KiB per workgroup, six workgroups per CU); the frame-1 features are independent (see above), so the four waves take
+// every fourth one and scan the node's frame-2 features from LDS.  Larger nodes: the same split, everything from global
+// memory.  out[idx1] is written where idx1 found a candidate; the host filled the rest with -1.  (Tp is a pointer on purpose:
+// a reference PARAMETER is marked dereferenceable, which lets the compiler load F12 / ex / ey of a table entry ahead of both
+// routes instead of next to their use and hold them in 15 more SGPRs throughout.)
+template <class Side1, class Side2>
+__device__ __forceinline__ void tri_node_search(const Side1 s1, const Side2 s2, const BowPair P, const uint32_t* __restrict__ feat1,
+                                                const uint32_t* __restrict__ feat2, const TriParams* Tp, int32_t* __restrict__ out) {
+  const TriParams& T = *Tp;
   __shared__ uint4 d1s[2 * kBowSide], d2s[2 * kBowSide];
   __shared__ float x1s[kBowSide], y1s[kBowSide], x2s[kBowSide], y2s[kBowSide];
-  __shared__ uint32_t row1[kBowSide], row2[kBowSide];   // keypoint index | 0x80000000: has a MapPoint (skipped)
+  __shared__ uint32_t row1[kBowSide], row2[kBowSide];   // keypoint index (= descriptor row) | 0x80000000: has a MapPoint (skipped)
   __shared__ int o2s[kBowSide];
-  const BowPair P = recs[blockIdx.x];   // (b2, e2: into feat2; base1: the neighbour's row of matches12; tk: the neighbour)
-  const TriNeighbour& N = nbs[P.tk];
-  const TriParams& T = N.T;
-  const float *x2g = N.x2, *y2g = N.y2;   // (read with gload: pointers that come out of memory are generic to the compiler)
-  const int* oct2 = N.oct2;
-  const uint4* desc2 = N.desc2;
-  const uint8_t* hasMP2 = flags2 + N.flag2;
-  int32_t* out = matches12 + (size_t)(unsigned)P.base1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n1g = P.e1 - P.b1, n2g = P.e2 - P.b2;
   if (n1g <= kBowSide && n2g <= kBowSide) {
     for (int i = tid; i < n1g; i += kBowThreads) {
       const unsigned idx1 = feat1[P.b1 + i];
-      row1[i] = idx1 | (hasMP1[idx1] ? 0x80000000u : 0u);
-      d1s[2 * i] = desc1[2 * (size_t)idx1]; d1s[2 * i + 1] = desc1[2 * (size_t)idx1 + 1];
-      x1s[i] = x1g[idx1]; y1s[i] = y1g[idx1];
+      row1[i] = idx1 | (s1.flagged(idx1) ? 0x80000000u : 0u);
+      d1s[2 * i] = s1.lo(idx1); d1s[2 * i + 1] = s1.hi(idx1);
+      x1s[i] = s1.x(idx1); y1s[i] = s1.y(idx1);
     }
     for (int i = tid; i < n2g; i += kBowThreads) {
       const unsigned idx2 = feat2[P.b2 + i];
-      row2[i] = idx2 | (hasMP2[idx2] ? 0x80000000u : 0u);
-      d2s[2 * i] = gload_row(desc2 + 2 * (size_t)idx2); d2s[2 * i + 1] = gload_row(desc2 + 2 * (size_t)idx2 + 1);
-      x2s[i] = gload(x2g + idx2); y2s[i] = gload(y2g + idx2); o2s[i] = gload(oct2 + idx2);
+      row2[i] = idx2 | (s2.flagged(idx2) ? 0x80000000u : 0u);
+      d2s[2 * i] = s2.lo(idx2); d2s[2 * i + 1] = s2.hi(idx2);
+      x2s[i] = s2.x(idx2); y2s[i] = s2.y(idx2); o2s[i] = s2.octave(idx2);
     }
     __syncthreads();
     for (int r = wave; r < n1g; r += kBowThreads / 64) {
@@ -684,22 +612,65 @@ __global__ void __launch_bounds__(kBowThreads) k_bow_triangulate_batch(const Tri
     }
     return;
   }
-  for (int i1 = P.b1 + wave; i1 < P.e1; i1 += kBowThreads / 64) {   // (a node too large for LDS: the same split, from global memory)
+  for (int i1 = P.b1 + wave; i1 < P.e1; i1 += kBowThreads / 64) {   // (a node too large for LDS)
     const unsigned idx1 = feat1[i1];
-    if (hasMP1[idx1]) continue;   // wave-uniform
-    const uint4 a0 = desc1[2 * (size_t)idx1], a1 = desc1[2 * (size_t)idx1 + 1];
+    if (s1.flagged(idx1)) continue;   // wave-uniform
+    const uint4 a0 = s1.lo(idx1), a1 = s1.hi(idx1);
     float la, lb, lc, den;
-    epipolar_line(x1g[idx1], y1g[idx1], T, &la, &lb, &lc, &den);
+    epipolar_line(s1.x(idx1), s1.y(idx1), T, &la, &lb, &lc, &den);
     unsigned key = 0xffffffffu;
     for (int p = lane; p < n2g; p += 64) {
       const unsigned idx2 = feat2[P.b2 + p];
-      if (hasMP2[idx2]) continue;
-      const int dist = hamming256(a0, a1, gload_row(desc2 + 2 * (size_t)idx2), gload_row(desc2 + 2 * (size_t)idx2 + 1));
-      key = min(key, tri_candidate_key(dist, gload(x2g + idx2), gload(y2g + idx2), gload(oct2 + idx2), p, la, lb, lc, den, T));
+      if (s2.flagged(idx2)) continue;
+      const int dist = hamming256(a0, a1, s2.lo(idx2), s2.hi(idx2));
+      key = min(key, tri_candidate_key(dist, s2.x(idx2), s2.y(idx2), s2.octave(idx2), p, la, lb, lc, den, T));
     }
     key = wave_min(key);
     if (key != 0xffffffffu && lane == 0) out[idx1] = (int32_t)feat2[P.b2 + (int)(0xffffu - (key & 0xffffu))];
   }
+}
+
+// orbfe_search_for_triangulation: both sides from the call's arena -- from the page-locked one directly on the route without
+// copy commands, where every wave's stores are acknowledged before the block counts itself off.
+__global__ void __launch_bounds__(kBowThreads) k_bow_triangulate(const OrbfeKeyPoint* __restrict__ kps1, const uint4* __restrict__ desc1,
+                                                                 const uint8_t* __restrict__ hasMP1, const uint32_t* __restrict__ feat1,
+                                                                 const OrbfeKeyPoint* __restrict__ kps2, const uint4* __restrict__ desc2,
+                                                                 const uint8_t* __restrict__ hasMP2, const uint32_t* __restrict__ feat2,
+                                                                 const BowPair* __restrict__ pairs, TriParams T,
+                                                                 int32_t* __restrict__ matches12, unsigned* doneCounter, int* doneHost,
+                                                                 int doneSeq) {
+  tri_node_search(TriAos{kps1, desc1, hasMP1}, TriAos{kps2, desc2, hasMP2}, pairs[blockIdx.x], feat1, feat2, &T, matches12);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (doneCounter && threadIdx.x == 0) signal_last_block(doneCounter, doneHost, doneSeq);
+}
+
+// SearchForTriangulation of ONE keyframe against SEVERAL neighbours (the loop of LocalMapping::CreateNewMapPoints,
+// LocalMapping.cc:207-232), every keyframe a resident frame: one workgroup per (neighbour, common vocabulary node) record of
+// tri_batch_plan.h.  Keypoints (x, y, octave) and descriptor rows of both sides come from the frames' own device arrays; what
+// the call uploaded is the record list, the feature lists, the MapPoint flags and one TriNeighbour per neighbour.  The
+// neighbour's index comes out of the record, the record's out of blockIdx: both are wave-uniform, so the record, the table
+// entry's pointers and F12 / ex / ey are scalar loads into SGPRs, paid once per wave; scale2 / sigma2 are indexed by a
+// candidate's octave and are vector loads of a 64-byte line that stays in the CU's cache.  Row k * n1 of matches12 is
+// neighbour k's.  Side 1 is the same for every neighbour: the records are sorted node-major, and what is read of the current
+// keyframe -- 2 000 x (32 B descriptor row + x + y) = 80 KB -- fits every XCD's L2 many times over.
+struct TriNeighbour {
+  const float *x2, *y2;    // the neighbour's resident frame: mvKeysUn ...
+  const int* oct2;
+  const uint4* desc2;      // ... and mDescriptors, keypoint order
+  TriParams T;
+  uint32_t flag2;          // where its MapPoint flags start in the call's flag part
+};
+static_assert(sizeof(TriNeighbour) == 208 && sizeof(BowPair) == sizeof(orbfe::TriRecord), "table entry / record layout");
+__global__ void __launch_bounds__(kBowThreads) k_bow_triangulate_batch(const TriNeighbour* __restrict__ nbs, const BowPair* __restrict__ recs,
+                                                                       const float* __restrict__ x1g, const float* __restrict__ y1g,
+                                                                       const uint4* __restrict__ desc1, const uint8_t* __restrict__ hasMP1,
+                                                                       const uint32_t* __restrict__ feat1, const uint8_t* __restrict__ flags2,
+                                                                       const uint32_t* __restrict__ feat2, int32_t* __restrict__ matches12) {
+  const BowPair P = recs[blockIdx.x];   // (b2, e2: into feat2; base1: the neighbour's row of matches12; tk: the neighbour)
+  const TriNeighbour& N = nbs[P.tk];
+  tri_node_search(TriResident{x1g, y1g, nullptr, desc1, hasMP1}, TriResident{N.x2, N.y2, N.oct2, N.desc2, flags2 + N.flag2}, P, feat1,
+                  feat2, &N.T, matches12 + (size_t)(unsigned)P.base1);
 }
 
 }  // namespace
@@ -1058,8 +1029,9 @@ struct BowCall {
   size_t rows = 0;           // entries of matches12
   bool zerocopy = false;
 
-  // parts: bytes of each array of the arena, in order; the caller fills them at host(i) and then submits
-  int open(orbfe_matcher* m, std::initializer_list<size_t> parts, size_t nRows, const std::vector<BowPair>& pairs) {
+  // parts: bytes of each array of the arena, in order; the caller fills them at host(i) and then submits.  pairs: the nodes,
+  // whose sizes decide the route; nullptr: the upload route (a caller whose kernel has no completion word)
+  int open(orbfe_matcher* m, std::initializer_list<size_t> parts, size_t nRows, const std::vector<BowPair>* pairs) {
     HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
     std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
     if (!slot) slot = std::make_shared<BowScratch>();
@@ -1070,8 +1042,9 @@ struct BowCall {
     for (const size_t bytes : parts) off.push_back(off.back() + al(bytes));
     int rc;
     if ((rc = S->h_arena.ensure(off.back())) || (rc = S->d_arena.ensure(off.back())) || (rc = S->d_m12.ensure(rows)) || (rc = S->h_m12.ensure(rows))) return rc;
+    if (!pairs) return ORBFE_OK;
     bool small = true;
-    for (const BowPair& p : pairs) small = small && p.e1 - p.b1 <= kBowSide && p.e2 - p.b2 <= kBowSide;
+    for (const BowPair& p : *pairs) small = small && p.e1 - p.b1 <= kBowSide && p.e2 - p.b2 <= kBowSide;
     const char* zce = getenv("ORBFE_BOW_ZEROCOPY");   // (read per call: the parity tests run both routes in one process)
     zerocopy = small && !(zce && atoi(zce) == 0);
     return ORBFE_OK;
@@ -1163,6 +1136,34 @@ int prune_by_orientation(const float* angle1, size_t stride1, const float* angle
   return removed;
 }
 
+// what the kernels read of one SearchForTriangulation: F12, the epipole, and side 2's per-level tables padded to 16 entries
+TriParams tri_params(const float F12[9], float ex, float ey, const float* scale_factors2, const float* level_sigma2_2, int nlevels2) {
+  TriParams T;
+  memcpy(T.F12, F12, sizeof T.F12);
+  T.ex = ex; T.ey = ey;
+  for (int i = 0; i < 16; i++) { T.scale2[i] = scale_factors2[std::min(i, nlevels2 - 1)]; T.sigma2[i] = level_sigma2_2[std::min(i, nlevels2 - 1)]; }
+  return T;
+}
+
+// The tail of SearchForTriangulation over a finished matches12 row (ORBmatcher.cc:745-800): count, rotation histogram,
+// vMatchedPairs in ascending idx1.  (The histogram waits for n1 > 0 && n2 > 0: an empty side has no keypoint array to read an
+// angle from.  A row with a match has both, and the single call gets here only with a common node, so with both.)
+void tri_pairs_out(int32_t* row, int n1, int n2, int check_orientation, const OrbfeKeyPoint* kps1_un, const OrbfeKeyPoint* kps2_un,
+                   int32_t* pairs_out, int* nmatches) {
+  int nm = 0;
+  for (int i = 0; i < n1; i++) if (row[i] >= 0) nm++;
+  if (check_orientation && n1 > 0 && n2 > 0)
+    nm -= prune_by_orientation(&kps1_un[0].angle, sizeof(OrbfeKeyPoint), &kps2_un[0].angle, sizeof(OrbfeKeyPoint), n1, row);
+  int np = 0;
+  for (int i = 0; i < n1; i++) {
+    if (row[i] < 0) continue;
+    pairs_out[2 * np] = i;
+    pairs_out[2 * np + 1] = row[i];
+    np++;
+  }
+  *nmatches = nm;
+}
+
 }  // namespace
 
 // int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, ...) for SEVERAL keyframes against one frame -- the loop of
@@ -1224,7 +1225,7 @@ static int bow_batch_core(orbfe_matcher* m, int n_kf, const uint8_t* const* desc
   const size_t rows1 = rowBase[n_kf], feats1 = featBase[n_kf];
   enum { D1, D2, V1, V2, F1, F2, P };   // the arena's parts
   BowCall C;
-  if ((rc = C.open(m, {32 * rows1, 32 * (size_t)n2, rows1, (size_t)std::max(n2, 1), 4 * feats1, 4 * (size_t)nf2, sizeof(BowPair) * all.size()}, rows1, all)))
+  if ((rc = C.open(m, {32 * rows1, 32 * (size_t)n2, rows1, (size_t)std::max(n2, 1), 4 * feats1, 4 * (size_t)nf2, sizeof(BowPair) * all.size()}, rows1, &all)))
     return rc;
   BowScratch* S = C.S;
   for (int k = 0; k < n_kf; k++) {
@@ -1348,9 +1349,8 @@ extern "C" int orbfe_search_for_triangulation(orbfe_matcher* m, const OrbfeKeyPo
   enum { K1, K2, D1, D2, V1, V2, F1, F2, P };   // the arena's parts
   BowCall C;
   if ((rc = C.open(m, {sizeof(OrbfeKeyPoint) * (size_t)n1, sizeof(OrbfeKeyPoint) * (size_t)n2, 32 * (size_t)n1, 32 * (size_t)n2, (size_t)std::max(n1, 1),
-                       (size_t)std::max(n2, 1), 4 * (size_t)nf1, 4 * (size_t)nf2, sizeof(BowPair) * pairs.size()}, (size_t)n1, pairs)))
+                       (size_t)std::max(n2, 1), 4 * (size_t)nf1, 4 * (size_t)nf2, sizeof(BowPair) * pairs.size()}, (size_t)n1, &pairs)))
     return rc;
-  BowScratch* S = C.S;
   memcpy(C.host(K1), kps1_un, sizeof(OrbfeKeyPoint) * (size_t)n1);
   memcpy(C.host(K2), kps2_un, sizeof(OrbfeKeyPoint) * (size_t)n2);
   memcpy(C.host(D1), desc1, 32 * (size_t)n1);
@@ -1360,28 +1360,14 @@ extern "C" int orbfe_search_for_triangulation(orbfe_matcher* m, const OrbfeKeyPo
   memcpy(C.host(F1), fv1_features, 4 * (size_t)nf1);
   memcpy(C.host(F2), fv2_features, 4 * (size_t)nf2);
   memcpy(C.host(P), pairs.data(), sizeof(BowPair) * pairs.size());
-  TriParams T;
-  memcpy(T.F12, F12, sizeof T.F12);
-  T.ex = ex; T.ey = ey;
-  for (int i = 0; i < 16; i++) { T.scale2[i] = scale_factors2[std::min(i, nlevels2 - 1)]; T.sigma2[i] = level_sigma2_2[std::min(i, nlevels2 - 1)]; }
+  const TriParams T = tri_params(F12, ex, ey, scale_factors2, level_sigma2_2, nlevels2);
   rc = C.submit([&](uint8_t* B, int32_t* m12, unsigned* doneCounter, int* doneHost, int doneSeq) {
     hipLaunchKernelGGL(k_bow_triangulate, dim3((unsigned)pairs.size()), dim3(kBowThreads), 0, C.st, C.at<OrbfeKeyPoint>(B, K1),
                        C.at<uint4>(B, D1), C.at<uint8_t>(B, V1), C.at<uint32_t>(B, F1), C.at<OrbfeKeyPoint>(B, K2), C.at<uint4>(B, D2),
                        C.at<uint8_t>(B, V2), C.at<uint32_t>(B, F2), C.at<BowPair>(B, P), T, m12, doneCounter, doneHost, doneSeq);
   });
   if (rc) return rc;
-  int nm = 0;
-  for (int i = 0; i < n1; i++) if (S->h_m12.p[i] >= 0) nm++;
-  if (check_orientation)
-    nm -= prune_by_orientation(&kps1_un[0].angle, sizeof(OrbfeKeyPoint), &kps2_un[0].angle, sizeof(OrbfeKeyPoint), n1, S->h_m12.p);
-  int np = 0;
-  for (int i = 0; i < n1; i++) {   // vMatchedPairs in ascending idx1 (ORBmatcher.cc:792-800)
-    if (S->h_m12.p[i] < 0) continue;
-    pairs_out[2 * np] = i;
-    pairs_out[2 * np + 1] = S->h_m12.p[i];
-    np++;
-  }
-  *nmatches = nm;
+  tri_pairs_out(C.S->h_m12.p, n1, n2, check_orientation, kps1_un, kps2_un, pairs_out, nmatches);
   return ORBFE_OK;
 }
 
@@ -1429,15 +1415,12 @@ extern "C" int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orb
     for (size_t i = 0; i < rows; i++) matches12_raw[i] = -1;
     return ORBFE_OK;
   }
-  HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
-  std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
-  if (!slot) slot = std::make_shared<BowScratch>();
-  BowScratch* S = static_cast<BowScratch*>(slot.get());
-  hipStream_t st = orbfe::matcher_stream(m);
+  BowCall C;
   int rc;
-  if ((rc = S->h_arena.ensure(plan.bytes)) || (rc = S->d_arena.ensure(plan.bytes)) || (rc = S->d_m12.ensure(rows)) || (rc = S->h_m12.ensure(rows))) return rc;
-  // the upload image: [neighbour table | records | flags 1 | features 1 | flags 2 of every neighbour | features 2 of every neighbour]
-  uint8_t* H = S->h_arena.p;
+  if ((rc = C.open(m, {plan.bytes}, rows, nullptr))) return rc;
+  // the upload image, ONE part to BowCall (plan.bytes is a multiple of its 256-byte alignment): [neighbour table | records | flags 1 |
+  // features 1 | flags 2 of every neighbour | features 2 of every neighbour]
+  uint8_t* H = C.host(0);
   TriNeighbour* tab = reinterpret_cast<TriNeighbour*>(H + plan.oTable);
   for (int k = 0; k < n_nb; k++) {
     const OrbfeTriangulationNeighbour& N = neighbours[k];
@@ -1447,9 +1430,7 @@ extern "C" int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orb
     orbfe::frame_xy(N.frame2, &t.x2, &t.y2);
     orbfe::frame_source_arrays(N.frame2, &t.oct2, &angle, &maxOctave);
     t.desc2 = reinterpret_cast<const uint4*>(orbfe::frame_descriptor_rows(N.frame2));
-    memcpy(t.T.F12, N.F12, sizeof t.T.F12);
-    t.T.ex = N.ex; t.T.ey = N.ey;
-    for (int i = 0; i < 16; i++) { t.T.scale2[i] = N.scale_factors2[std::min(i, N.nlevels2 - 1)]; t.T.sigma2[i] = N.level_sigma2_2[std::min(i, N.nlevels2 - 1)]; }
+    t.T = tri_params(N.F12, N.ex, N.ey, N.scale_factors2, N.level_sigma2_2, N.nlevels2);
     t.flag2 = plan.flag2[k];
     if (s2[k].n) memcpy(H + plan.oFlag2 + plan.flag2[k], N.has_mp2, (size_t)s2[k].n);
     const size_t nf2 = N.n_fv2 ? N.fv2_offsets[N.n_fv2] : 0;
@@ -1458,22 +1439,21 @@ extern "C" int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orb
   memcpy(H + plan.oRecords, plan.records.data(), sizeof(orbfe::TriRecord) * plan.records.size());
   memcpy(H + plan.oFlag1, has_mp1, (size_t)s1.n);
   memcpy(H + plan.oFeat1, fv1_features, 4 * plan.nFeat1);
-  uint8_t* D = S->d_arena.p;
-  HIP_TRY(hipMemcpyAsync(D, H, plan.bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(S->d_m12.p, 0xff, sizeof(int32_t) * rows, st));
-  orbfe::frame_wait_ready(frame1, st);
-  for (int k = 0; k < n_nb; k++) orbfe::frame_wait_ready(neighbours[k].frame2, st);
   const float *x1, *y1;
   orbfe::frame_xy(frame1, &x1, &y1);
-  hipLaunchKernelGGL(k_bow_triangulate_batch, dim3((unsigned)plan.records.size()), dim3(kBowThreads), 0, st,
-                     reinterpret_cast<const TriNeighbour*>(D + plan.oTable), reinterpret_cast<const BowPair*>(D + plan.oRecords), x1, y1,
-                     reinterpret_cast<const uint4*>(orbfe::frame_descriptor_rows(frame1)), (const uint8_t*)(D + plan.oFlag1),
-                     reinterpret_cast<const uint32_t*>(D + plan.oFeat1), (const uint8_t*)(D + plan.oFlag2),
-                     reinterpret_cast<const uint32_t*>(D + plan.oFeat2), S->d_m12.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(S->h_m12.p, S->d_m12.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  memcpy(matches12_raw, S->h_m12.p, sizeof(int32_t) * rows);
+  rc = C.submit([&](uint8_t* D, int32_t* m12, unsigned*, int*, int) {
+    hipLaunchKernelGGL(k_bow_triangulate_batch, dim3((unsigned)plan.records.size()), dim3(kBowThreads), 0, C.st,
+                       reinterpret_cast<const TriNeighbour*>(D + plan.oTable), reinterpret_cast<const BowPair*>(D + plan.oRecords), x1, y1,
+                       reinterpret_cast<const uint4*>(orbfe::frame_descriptor_rows(frame1)), (const uint8_t*)(D + plan.oFlag1),
+                       reinterpret_cast<const uint32_t*>(D + plan.oFeat1), (const uint8_t*)(D + plan.oFlag2),
+                       reinterpret_cast<const uint32_t*>(D + plan.oFeat2), m12);
+  }, [&](uint8_t*) {   // the frames' own builds, after the upload and the fill as before
+    orbfe::frame_wait_ready(frame1, C.st);
+    for (int k = 0; k < n_nb; k++) orbfe::frame_wait_ready(neighbours[k].frame2, C.st);
+    return ORBFE_OK;
+  });
+  if (rc) return rc;
+  memcpy(matches12_raw, C.S->h_m12.p, sizeof(int32_t) * rows);
   return ORBFE_OK;
 }
 
@@ -1494,18 +1474,7 @@ extern "C" int orbfe_triangulation_finish(const int32_t* matches12_raw_row, int 
     return ORBFE_ERR_STALE;
   }
   if (rc) { set_err("raw entry %d is no keypoint of the neighbour (n2 = %d)", at, n2); return ORBFE_ERR_INVALID; }
-  int nm = 0;
-  for (int i = 0; i < n1; i++) if (row[i] >= 0) nm++;
-  if (check_orientation && n1 > 0 && n2 > 0)
-    nm -= prune_by_orientation(&kps1_un[0].angle, sizeof(OrbfeKeyPoint), &kps2_un[0].angle, sizeof(OrbfeKeyPoint), n1, row.data());
-  int np = 0;
-  for (int i = 0; i < n1; i++) {   // vMatchedPairs in ascending idx1 (ORBmatcher.cc:792-800)
-    if (row[i] < 0) continue;
-    pairs_out[2 * np] = i;
-    pairs_out[2 * np + 1] = row[i];
-    np++;
-  }
-  *nmatches = nm;
+  tri_pairs_out(row.data(), n1, n2, check_orientation, kps1_un, kps2_un, pairs_out, nmatches);
   return ORBFE_OK;
 }
 
