@@ -877,6 +877,40 @@ int orbfe_debug_covis_slots_per_pass(void);
 int orbfe_debug_covis_ms(const orbfe_matcher* m, double out[3]);
 
 /* ---------------------------------------------------------------------------------------------
+ * Keyframe culling.  The counting loop of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:574-598) for a batch of subjects in
+ * one call; the 90 % test, SetBadFlag and the recount after a keyframe has gone bad stay with the host
+ * (include/orbfe/KeyFrameCulling.h).
+ *
+ * Slots, MapPoint indices and the two CSRs (obs_offsets / obs_kf, subj_self / subj_offsets / subj_mp) are those of
+ * orbfe_covisibility_counts above: a caller that has written them down for that call can pass the same arrays.  Added here:
+ *   obs_level[o]   pKFi->mvKeysUn[mit->second].octave of observation o (next to obs_kf[o])
+ *   subj_level[e]  pKF->mvKeysUn[i].octave of the subject's entry e (next to subj_mp[e])
+ *   mp_nobs[p]     pMP->Observations(); NULL: the length of p's run in the CSR
+ *   th_obs         the reference's thObs, 3 there; any value >= 1 here
+ * For subject s and every entry e with p = subj_mp[e] >= 0 (-1 stands for whatever the reference skips: null, isBad()):
+ * n_mps[s]++; and if nobs(p) > th_obs, with c = the number of observations o of p with obs_kf[o] != subj_self[s] and
+ * (int)obs_level[o] <= (int)subj_level[e] + 1: n_redundant[s]++ iff c >= th_obs (the reference's break at thObs is only an early
+ * exit).  A MapPoint named twice by one subject counts twice; observers that are bad keyframes count, as in the reference;
+ * subj_self[s] == -1 excludes nobody.
+ * ORBFE_ERR_INVALID before anything is sent: a null pointer (obs_kf / obs_level and subj_mp / subj_level may be NULL where their
+ * CSR is empty, mp_nobs always); a negative size; th_obs < 1; offsets that decrease; an obs_kf outside [0, n_kf); a subj_mp
+ * outside [-1, n_mp); a subj_self outside [-1, n_kf); a negative mp_nobs.  n_subj == 0: ORBFE_OK.
+ * The call runs on the matcher's stream and returns when the two output arrays are written.  It takes no resident frames: only
+ * indices and level bytes cross PCIe.  Integer counting: the result is exact, whatever the order of the additions. */
+int orbfe_redundant_observations(orbfe_matcher* m,
+      int n_kf,                                   /* keyframe slots 0..n_kf-1 */
+      int n_mp, const int32_t* obs_offsets /* n_mp+1 */, const int32_t* obs_kf /* observer slot per observation */,
+      const uint8_t* obs_level /* octave per observation */,
+      const int32_t* mp_nobs /* n_mp, or NULL = the CSR's length per MapPoint */,
+      int n_subj, const int32_t* subj_self /* slot of the subject, or -1 */, const int32_t* subj_offsets /* n_subj+1 */,
+      const int32_t* subj_mp /* MapPoint index per keypoint entry, -1 = skipped */, const uint8_t* subj_level /* octave per entry */,
+      int th_obs,
+      int32_t* out_n_mps /* n_subj */, int32_t* out_n_redundant /* n_subj */);
+/* The last orbfe_redundant_observations of this matcher, ms: [0] argument check and staging on the host, [1] the kernel (events
+ * on the stream), [2] the whole call. */
+int orbfe_debug_culling_ms(const orbfe_matcher* m, double out[3]);
+
+/* ---------------------------------------------------------------------------------------------
  * Bag of words. Replaces the DBoW2 calls on the path: Frame::ComputeBoW (src/Frame.cc:277-284) ->
  * TemplatedVocabulary<FORB>::transform(features, BowVector&, FeatureVector&, levelsup)
  * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1136-1204, descent :1306-1347), and the two

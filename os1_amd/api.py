@@ -225,6 +225,8 @@ def load_library():
     L.orbfe_covisibility_counts.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(ci)]
     L.orbfe_debug_covis_slots_per_pass.argtypes = []
     L.orbfe_debug_covis_ms.argtypes = [vp, vp]
+    L.orbfe_redundant_observations.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+    L.orbfe_debug_culling_ms.argtypes = [vp, vp]
     L.orbfe_project_local_map.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci)]
     L.orbfe_search_local_points_frame.argtypes = [vp, vp, vp, vp, cf, vp, vp, ci, vp, ci, vp, cf, cf, vp, vp, vp, vp, vp,
                                                   C.POINTER(ci), C.POINTER(ci)]
@@ -1284,6 +1286,16 @@ class Matcher:
         _check(self.L.orbfe_debug_covis_ms(self.h, _p(out)))
         return out
 
+    def redundant_observations(self, n_kf, obs_offsets, obs_kf, obs_level, subj_self, subj_offsets, subj_mp, subj_level, th_obs=3, mp_nobs=None):
+        """The counts of LocalMapping::KeyFrameCulling for a batch of subjects: (n_mps, n_redundant); see redundant_observations."""
+        return redundant_observations(self, n_kf, obs_offsets, obs_kf, obs_level, subj_self, subj_offsets, subj_mp, subj_level, th_obs, mp_nobs)
+
+    def culling_ms(self):
+        """The last redundant_observations call, ms: host check + staging, kernel, whole call."""
+        out = np.zeros(3, np.float64)
+        _check(self.L.orbfe_debug_culling_ms(self.h, _p(out)))
+        return out
+
     def get_features_in_area(self, kps, bounds, x, y, r, min_level, max_level):
         kps = np.ascontiguousarray(kps, KP_DTYPE)
         b = np.asarray(bounds, np.float32)
@@ -1399,6 +1411,35 @@ def covisibility_counts(matcher, n_kf, obs_offsets, obs_kf, subj_self, subj_offs
         e.n_needed = needed.value if rc == -5 else None
         raise e
     return out_offsets, out_kf[:needed.value].copy(), out_count[:needed.value].copy()
+
+
+def redundant_observations(matcher, n_kf, obs_offsets, obs_kf, obs_level, subj_self, subj_offsets, subj_mp, subj_level, th_obs=3, mp_nobs=None):
+    """The counting loop of LocalMapping::KeyFrameCulling for a batch of subjects (orbfe_redundant_observations).  The CSRs are
+    those of covisibility_counts; obs_level / subj_level hold the octave (uint8) of every observation / entry, mp_nobs
+    MapPoint::Observations() (None: the CSR's length per MapPoint).  Returns (n_mps, n_redundant), int32 per subject: the entries
+    that name a MapPoint, and those of them whose MapPoint has more than th_obs observations of which at least th_obs are by other
+    keyframes at a level <= the entry's + 1.  matcher None reaches the library's argument check only (every call is then
+    refused, with the reason)."""
+    oo = np.ascontiguousarray(obs_offsets, np.int32)
+    ok = np.ascontiguousarray(obs_kf, np.int32)
+    ol = np.ascontiguousarray(obs_level, np.uint8)
+    ss = np.ascontiguousarray(subj_self, np.int32)
+    so = np.ascontiguousarray(subj_offsets, np.int32)
+    sm = np.ascontiguousarray(subj_mp, np.int32)
+    sv = np.ascontiguousarray(subj_level, np.uint8)
+    nb = None if mp_nobs is None else np.ascontiguousarray(mp_nobs, np.int32)
+    n_mp, n_subj = len(oo) - 1, len(ss)
+    if len(so) != n_subj + 1 or n_mp < 0 or len(ol) != len(ok) or len(sv) != len(sm) or (nb is not None and len(nb) != n_mp):
+        raise ValueError('redundant_observations: obs_offsets needs n_mp + 1 entries, subj_offsets n_subj + 1, mp_nobs n_mp, a level per observation and entry')
+    n_mps = np.zeros(max(n_subj, 1), np.int32)
+    n_red = np.zeros(max(n_subj, 1), np.int32)
+    L = load_library()
+    rc = L.orbfe_redundant_observations(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _p(ok) if len(ok) else None,
+                                        _p(ol) if len(ol) else None, None if nb is None else _p(nb), n_subj, _p(ss) if n_subj else None, _p(so),
+                                        _p(sm) if len(sm) else None, _p(sv) if len(sv) else None, int(th_obs), _p(n_mps), _p(n_red))
+    if rc != 0:
+        raise OrbfeError(rc, L.orbfe_last_error().decode('utf-8', 'replace'))
+    return n_mps[:n_subj].copy(), n_red[:n_subj].copy()
 
 
 class Vocabulary:
