@@ -556,7 +556,8 @@ unsigned long long orbfe_resident_invalidate(void);
 /* The frame's descriptor rows [n][32] in DEVICE memory, keypoint order; valid while the frame lives.  Returns when the
  * rows are complete.  Usable as the query descriptor rows of a search on another frame of the same device (a caller that
  * keeps descriptors on the GPU -- its own table of MapPoint descriptors, or a frame's rows -- passes device pointers and no
- * descriptor crosses PCIe). */
+ * descriptor crosses PCIe).  The call only reads the frame, and so does whoever reads the rows: several threads may use them
+ * at once, through any matcher or vocabulary of the device (the wait above is a host wait: no stream has to order itself). */
 const uint8_t* orbfe_frame_descriptors_device(orbfe_frame* f);
 /* Test / debug: the resident content back on the host -- keypoints (x, y, angle, octave; other fields zeroed) and
  * descriptor rows in keypoint order, the keypoint indices in grid order (capacity n) and the 64*48+1 cell offsets into
@@ -660,7 +661,8 @@ int orbfe_project_local_map(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* m
  * by orbfe_search_by_projection_frame_rows on the same inputs.
  * LEVEL CONTRACT: a MapPoint in view whose predicted level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID
  * (as an out-of-range level does in the rows form).  The projection kernel finds it and takes it out of the search before
- * anything is indexed with that level; the outputs are then unspecified, and the matcher, frame and table stay usable. */
+ * anything is indexed with that level; the outputs are then unspecified, and the matcher, frame and table stay usable.
+ * f is SEARCHED (one search of a frame at a time); orbfe_project_local_map alone reads nothing of f but its bounds. */
 int orbfe_search_local_points_frame(orbfe_matcher* m, orbfe_frame* f, orbfe_local_map* map, const OrbfeCamera* cam,
                                     float view_cos_limit, const int32_t* rows, const uint8_t* flags, int n_mp,
                                     const float* scale_factors, int nlevels, const uint8_t* kp_occupied, float th, float nnratio,
@@ -704,7 +706,9 @@ int orbfe_project_sources(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame*
  * LEVEL CONTRACT: a valid source whose level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID, as in
  * orbfe_search_local_points_frame: the projection kernel takes it out of the search before anything is indexed with that
  * level (LAST_FRAME: refused up front from the source frame's largest octave); the outputs are then unspecified, and the
- * matcher, frames and table stay usable. */
+ * matcher, frames and table stay usable.
+ * cur_frame is SEARCHED (one search of a frame at a time).  src_frame is only read (octaves, angles), here and in
+ * orbfe_project_sources, behind its build on m's stream: it may serve as the source of several threads' calls at once. */
 int orbfe_search_by_projection_sources_frame(orbfe_matcher* m, orbfe_frame* cur_frame, orbfe_frame* src_frame,
                                              orbfe_local_map* map, const OrbfeCamera* cam, int mode, const int32_t* rows,
                                              const uint8_t* flags, int n_src, const float* scale_factors, int nlevels,
@@ -769,7 +773,8 @@ int orbfe_project_keyframe(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_
  * orbfe_search_projected_frame on the same inputs.  n == 0 or an empty keyframe: ORBFE_OK, every best_idx -1.
  * LEVEL CONTRACT: a valid point whose predicted level lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID, as in
  * orbfe_search_local_points_frame: the projection kernel takes it out of the search before anything is indexed with that
- * level; the outputs are then unspecified, and the matcher, frame and table stay usable. */
+ * level; the outputs are then unspecified, and the matcher, frame and table stay usable.
+ * kf_frame is SEARCHED (one search of a frame at a time); orbfe_project_keyframe alone reads nothing of it but its bounds. */
 int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_frame, orbfe_local_map* map,
                                           const OrbfeKeyFrameProjection* proj, const int32_t* rows, const uint8_t* flags, int n,
                                           const float* scale_factors, int nlevels, float th, const uint8_t* kp_skip, int claim,
@@ -808,7 +813,10 @@ int orbfe_search_projected_keyframe_frame(orbfe_matcher* m, orbfe_frame* kf_fram
  * orbfe_distinctive_descriptors).
  * LEVEL CONTRACT: a MapPoint whose reference keypoint's octave lies outside [0, nlevels) fails the call with ORBFE_ERR_INVALID;
  * the kernel finds it before anything is indexed with that level and leaves that MapPoint's row unwritten (the other rows
- * of the batch are written, the host outputs are not); the matcher, frames and table stay usable. */
+ * of the batch are written, the host outputs are not); the matcher, frames and table stay usable.
+ * The keyframes are only read (descriptor rows, octaves): calls of other threads that only read them may overlap.  After the
+ * enqueue-only return the kernel may still be reading them; orbfe_frame_destroy is safe all the same -- it frees the frame's
+ * device memory with hipFree, which waits for the work of every stream of the device before it releases anything. */
 #define ORBFE_OBS_KF_BAD 1u              /* pKF->isBad(): not in the descriptor list; still in the normal */
 #define ORBFE_REFRESH_DESCRIPTOR   1     /* ComputeDistinctiveDescriptors */
 #define ORBFE_REFRESH_NORMAL_DEPTH 2     /* UpdateNormalAndDepth */
@@ -1077,7 +1085,8 @@ int orbfe_score_init_hypotheses_kps(orbfe_matcher* m, const OrbfeKeyPoint* kps1_
                                     float* best_score_h, float* best_score_f, uint8_t* inliers_h, uint8_t* inliers_f,
                                     int* n_matches);
 /* The same, with both frames resident (orbfe_frame; matches12 has orbfe_frame_size(f1) entries): only matches12 and the
- * hypotheses cross the link, the gather from the frames' undistorted keypoints happens on the device. */
+ * hypotheses cross the link, the gather from the frames' undistorted keypoints happens on the device.  Both frames are only
+ * read (their keypoint coordinates), behind their builds on m's stream: calls of other threads that only read them may overlap. */
 int orbfe_score_init_hypotheses_frames(orbfe_matcher* m, orbfe_frame* f1, orbfe_frame* f2, const int32_t* matches12, float sigma,
                                        int n_hyp, const float* H21, const float* H12, const float* F21, float* scores_h,
                                        float* scores_f, int32_t* best_h, int32_t* best_f, float* best_score_h,
@@ -1127,7 +1136,9 @@ typedef struct OrbfeTriangulationNeighbour {
  * n_nb == 0 is valid; a neighbour that shares no vocabulary node with frame1 yields a row of -1.  Everything is checked before
  * anything is sent or written; ORBFE_ERR_INVALID names the neighbour for: a keypoint octave of frame2 outside [0, nlevels2), a
  * feature index that is no keypoint of its frame, a frame on another device than m, nlevels2 outside 1..16.  ORBFE_ERR_OVERFLOW:
- * a vocabulary node with more than 65 535 features of a neighbour. */
+ * a vocabulary node with more than 65 535 features of a neighbour.  frame1 and every frame2 are only read (coordinates, octaves,
+ * descriptor rows), behind their builds on m's stream, and the call returns after its kernel has finished: calls of other threads
+ * that only read these frames may overlap, and a frame may be destroyed as soon as the call has returned. */
 int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orbfe_frame* frame1, const uint8_t* has_mp1,
                                                 const uint32_t* fv1_nodes, const uint32_t* fv1_offsets, const uint32_t* fv1_features,
                                                 int n_fv1, int n_nb, const OrbfeTriangulationNeighbour* neighbours,

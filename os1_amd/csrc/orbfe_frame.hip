@@ -578,6 +578,8 @@ struct orbfe_frame {
     // `ready` may have been recorded on the stream of an extractor that no longer exists (its destructor waited for the
     // stream's work, so the build is complete): errors of these two calls are not errors of the frame
     if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
+    // Readers of other streams may still be pending (orbfe_local_map_refresh_rows returns once enqueued): hipFree waits for
+    // the whole device before it releases anything.  A pooled or stream-ordered release here would have to wait itself.
     buf.release(); stage.release();
     (void)hipGetLastError();
   }
