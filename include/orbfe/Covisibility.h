@@ -72,8 +72,9 @@ struct CovisibilityCsr {
     kfs.push_back(pKF);
     return s;
   }
-  // the MapPoint's index; its observations are read the first time it is seen
-  int32_t mapPoint(MP* pMP) {
+  // the MapPoint's index; its observations are read the first time it is seen, and `seen(pMP, observations)` is told of them
+  template <class Seen>
+  int32_t mapPoint(MP* pMP, Seen&& seen) {
     typename std::map<MP*, int32_t>::iterator it = indexOf.find(pMP);
     if (it != indexOf.end()) return it->second;
     const int32_t p = (int32_t)obsOffsets.size() - 1;
@@ -81,15 +82,24 @@ struct CovisibilityCsr {
     const std::map<KF*, size_t> observations = pMP->GetObservations();
     for (typename std::map<KF*, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) obsKf.push_back(slot(mit->first));
     obsOffsets.push_back((int32_t)obsKf.size());
+    seen(pMP, observations);
     return p;
   }
-  // one subject: `skip(pMP)` says which entries the reference loop passes over
-  template <class Skip>
-  void subject(int32_t self, int32_t limit, const std::vector<MP*>& vpMP, Skip skip) {
-    for (size_t i = 0; i < vpMP.size(); i++) subjMp.push_back(skip(vpMP[i]) ? -1 : mapPoint(vpMP[i]));
+  // one subject: `skip(pMP)` says which entries the reference loop passes over; `entry(i, p)` is told of every entry, skipped (p
+  // is -1) or not, after `seen` has been told of its MapPoint
+  template <class Skip, class Seen, class Entry>
+  void subject(int32_t self, int32_t limit, const std::vector<MP*>& vpMP, Skip skip, Seen&& seen, Entry&& entry) {
+    for (size_t i = 0; i < vpMP.size(); i++) {
+      subjMp.push_back(skip(vpMP[i]) ? -1 : mapPoint(vpMP[i], seen));
+      entry(i, subjMp.back());
+    }
     subjSelf.push_back(self);
     subjLimit.push_back(limit);
     subjOffsets.push_back((int32_t)subjMp.size());
+  }
+  template <class Skip>
+  void subject(int32_t self, int32_t limit, const std::vector<MP*>& vpMP, Skip skip) {
+    subject(self, limit, vpMP, skip, [](MP*, const std::map<KF*, size_t>&) {}, [](size_t, int32_t) {});
   }
   int nSubjects() const { return (int)subjSelf.size(); }
   // no call needs more entries: per subject min(limit, observations reachable); limit < 0 stands for "every slot"
@@ -114,15 +124,9 @@ struct CovisibilityCsr {
     outOffsets.assign((size_t)nSubjects() + 1, 0);
     outKf.assign((size_t)cap + 1, 0);
     outCount.assign((size_t)cap + 1, 0);
-    obsKf.push_back(0);          // (never read: keeps data() non-null for empty CSRs)
-    subjMp.push_back(0);
-    int needed = 0;
-    const int rc = orbfe_covisibility_counts(m, nkf, (int)obsOffsets.size() - 1, obsOffsets.data(), obsKf.data(), nSubjects(), subjSelf.data(),
-                                             subjLimit.data(), subjOffsets.data(), subjMp.data(), outOffsets.data(), outKf.data(), outCount.data(),
-                                             (int)cap, &needed);
-    obsKf.pop_back();
-    subjMp.pop_back();
-    return rc;
+    int needed = 0;      // (an empty CSR's data() may be null: the call takes that)
+    return orbfe_covisibility_counts(m, nkf, (int)obsOffsets.size() - 1, obsOffsets.data(), obsKf.data(), nSubjects(), subjSelf.data(), subjLimit.data(),
+                                     subjOffsets.data(), subjMp.data(), outOffsets.data(), outKf.data(), outCount.data(), (int)cap, &needed);
   }
 };
 

@@ -49,34 +49,17 @@ struct KeyFrameCullingCsr : CovisibilityCsr<KF, MP> {
     if (octave < 0 || octave > 255) { ok = false; return 0; }
     return (uint8_t)octave;
   }
-  // the MapPoint's index; its observations are read the first time it is seen: slot, octave, Observations()
-  int32_t mapPoint(MP* pMP) {
-    typename std::map<MP*, int32_t>::iterator it = this->indexOf.find(pMP);
-    if (it != this->indexOf.end()) return it->second;
-    const int32_t p = (int32_t)this->obsOffsets.size() - 1;
-    this->indexOf[pMP] = p;
-    const std::map<KF*, size_t> observations = pMP->GetObservations();
-    for (typename std::map<KF*, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) {
-      this->obsKf.push_back(this->slot(mit->first));
-      obsLevel.push_back(level(mit->first->mvKeysUn[mit->second].octave));
-    }
-    this->obsOffsets.push_back((int32_t)this->obsKf.size());
-    mpNobs.push_back((int32_t)pMP->Observations());
-    return p;
-  }
-  // one subject, in slot `self`; keyframe 0 is never judged (LocalMapping.cc:567) and brings no entries
+  // one subject, in slot `self`; keyframe 0 is never judged (LocalMapping.cc:567) and brings no entries.  To CovisibilityCsr's
+  // walk this adds the octave of every observation and Observations() when a MapPoint is first seen, and the octave of every entry.
   void subject(int32_t self, KF* pKF) {
-    if (pKF->mnId != 0) {
-      const std::vector<MP*> vpMapPoints = pKF->GetMapPointMatches();
-      for (size_t i = 0; i < vpMapPoints.size(); i++) {
-        MP* pMP = vpMapPoints[i];
-        const bool skip = !pMP || pMP->isBad();                                   // LocalMapping.cc:576
-        this->subjMp.push_back(skip ? -1 : mapPoint(pMP));
-        subjLevel.push_back(skip ? 0 : level(pKF->mvKeysUn[i].octave));
-      }
-    }
-    this->subjSelf.push_back(self);
-    this->subjOffsets.push_back((int32_t)this->subjMp.size());
+    CovisibilityCsr<KF, MP>::subject(
+        self, -1, pKF->mnId != 0 ? pKF->GetMapPointMatches() : std::vector<MP*>(), [](MP* pMP) { return !pMP || pMP->isBad(); },   // LocalMapping.cc:576
+        [this](MP* pMP, const std::map<KF*, size_t>& observations) {
+          for (typename std::map<KF*, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit)
+            obsLevel.push_back(level(mit->first->mvKeysUn[mit->second].octave));
+          mpNobs.push_back((int32_t)pMP->Observations());
+        },
+        [this, pKF](size_t i, int32_t p) { subjLevel.push_back(p < 0 ? 0 : level(pKF->mvKeysUn[i].octave)); });
   }
 };
 
@@ -95,11 +78,6 @@ inline int KeyFrameCullingCount(Counter&& count, const std::vector<KeyFrameT*>& 
   const int n = csr.nSubjects();
   nMPs.assign((size_t)n, 0);
   nRedundant.assign((size_t)n, 0);
-  csr.obsKf.push_back(0);          // (never read: keeps data() non-null for empty CSRs)
-  csr.obsLevel.push_back(0);
-  csr.mpNobs.push_back(0);
-  csr.subjMp.push_back(0);
-  csr.subjLevel.push_back(0);
   return count((int)csr.kfs.size(), (int)csr.obsOffsets.size() - 1, csr.obsOffsets.data(), csr.obsKf.data(), csr.obsLevel.data(), csr.mpNobs.data(), n,
                csr.subjSelf.data(), csr.subjOffsets.data(), csr.subjMp.data(), csr.subjLevel.data(), thObs, nMPs.data(), nRedundant.data());
 }

@@ -1282,9 +1282,7 @@ class Matcher:
 
     def covis_ms(self):
         """The last covisibility_counts call, ms: host check + staging, kernel, whole call."""
-        out = np.zeros(3, np.float64)
-        _check(self.L.orbfe_debug_covis_ms(self.h, _p(out)))
-        return out
+        return self._three_ms(self.L.orbfe_debug_covis_ms)
 
     def redundant_observations(self, n_kf, obs_offsets, obs_kf, obs_level, subj_self, subj_offsets, subj_mp, subj_level, th_obs=3, mp_nobs=None):
         """The counts of LocalMapping::KeyFrameCulling for a batch of subjects: (n_mps, n_redundant); see redundant_observations."""
@@ -1292,8 +1290,11 @@ class Matcher:
 
     def culling_ms(self):
         """The last redundant_observations call, ms: host check + staging, kernel, whole call."""
+        return self._three_ms(self.L.orbfe_debug_culling_ms)
+
+    def _three_ms(self, call):
         out = np.zeros(3, np.float64)
-        _check(self.L.orbfe_debug_culling_ms(self.h, _p(out)))
+        _check(call(self.h, _p(out)))
         return out
 
     def get_features_in_area(self, kps, bounds, x, y, r, min_level, max_level):
@@ -1380,6 +1381,19 @@ def covisibility_bound(n_kf, obs_offsets, subj_offsets, subj_mp, subj_limit=None
     return int(np.minimum(reach, limit).sum())
 
 
+def _obs_graph(obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp):
+    """The observation graph covisibility_counts and redundant_observations both take: the five arrays as contiguous int32, n_mp,
+    n_subj, and whether the two offset arrays have the lengths that go with them."""
+    oo, ok, ss, so, sm = (np.ascontiguousarray(a, np.int32) for a in (obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp))
+    n_mp, n_subj = len(oo) - 1, len(ss)
+    return (oo, ok, ss, so, sm), n_mp, n_subj, len(so) == n_subj + 1 and n_mp >= 0
+
+
+def _pn(a):
+    """the array's pointer, None for an empty or absent one (the C calls take a null payload with an empty CSR)"""
+    return None if a is None or len(a) == 0 else _p(a)
+
+
 def covisibility_counts(matcher, n_kf, obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp, subj_limit=None, cap=None):
     """The counters of KeyFrame::UpdateConnections / Tracking::UpdateLocalKeyFrames for a batch of subjects
     (orbfe_covisibility_counts): MapPoint p is observed by the keyframe slots obs_kf[obs_offsets[p]:obs_offsets[p+1]]; subject s
@@ -1388,14 +1402,9 @@ def covisibility_counts(matcher, n_kf, obs_offsets, obs_kf, subj_self, subj_offs
     [out_offsets[s], out_offsets[s+1]) of the non-zero counters in ascending slot order.  cap (None: covisibility_bound, which
     always suffices) is the room for entries; a call that needs more raises OrbfeError with code -5 and .n_needed set.
     matcher None reaches the library's argument check only (every call is then refused, with the reason)."""
-    oo = np.ascontiguousarray(obs_offsets, np.int32)
-    ok = np.ascontiguousarray(obs_kf, np.int32)
-    ss = np.ascontiguousarray(subj_self, np.int32)
-    so = np.ascontiguousarray(subj_offsets, np.int32)
-    sm = np.ascontiguousarray(subj_mp, np.int32)
+    (oo, ok, ss, so, sm), n_mp, n_subj, fits = _obs_graph(obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp)
     sl = None if subj_limit is None else np.ascontiguousarray(subj_limit, np.int32)
-    n_mp, n_subj = len(oo) - 1, len(ss)
-    if len(so) != n_subj + 1 or (sl is not None and len(sl) != n_subj) or n_mp < 0:
+    if not fits or (sl is not None and len(sl) != n_subj):
         raise ValueError('covisibility_counts: obs_offsets needs n_mp + 1 entries, subj_offsets n_subj + 1, subj_limit n_subj')
     if cap is None:
         cap = covisibility_bound(n_kf, oo, so, sm, sl)
@@ -1403,9 +1412,9 @@ def covisibility_counts(matcher, n_kf, obs_offsets, obs_kf, subj_self, subj_offs
     out_kf = np.zeros(max(cap, 1), np.int32)
     out_count = np.zeros(max(cap, 1), np.int32)
     needed = C.c_int(0)
-    rc = load_library().orbfe_covisibility_counts(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _p(ok) if len(ok) else None, n_subj,
-                                                  _p(ss) if n_subj else None, None if sl is None else _p(sl), _p(so), _p(sm) if len(sm) else None,
-                                                  _p(out_offsets), _p(out_kf), _p(out_count), cap, C.byref(needed))
+    rc = load_library().orbfe_covisibility_counts(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _pn(ok), n_subj, _pn(ss),
+                                                  None if sl is None else _p(sl), _p(so), _pn(sm), _p(out_offsets), _p(out_kf), _p(out_count), cap,
+                                                  C.byref(needed))
     if rc != 0:
         e = OrbfeError(rc, load_library().orbfe_last_error().decode('utf-8', 'replace'))
         e.n_needed = needed.value if rc == -5 else None
@@ -1420,23 +1429,17 @@ def redundant_observations(matcher, n_kf, obs_offsets, obs_kf, obs_level, subj_s
     that name a MapPoint, and those of them whose MapPoint has more than th_obs observations of which at least th_obs are by other
     keyframes at a level <= the entry's + 1.  matcher None reaches the library's argument check only (every call is then
     refused, with the reason)."""
-    oo = np.ascontiguousarray(obs_offsets, np.int32)
-    ok = np.ascontiguousarray(obs_kf, np.int32)
+    (oo, ok, ss, so, sm), n_mp, n_subj, fits = _obs_graph(obs_offsets, obs_kf, subj_self, subj_offsets, subj_mp)
     ol = np.ascontiguousarray(obs_level, np.uint8)
-    ss = np.ascontiguousarray(subj_self, np.int32)
-    so = np.ascontiguousarray(subj_offsets, np.int32)
-    sm = np.ascontiguousarray(subj_mp, np.int32)
     sv = np.ascontiguousarray(subj_level, np.uint8)
     nb = None if mp_nobs is None else np.ascontiguousarray(mp_nobs, np.int32)
-    n_mp, n_subj = len(oo) - 1, len(ss)
-    if len(so) != n_subj + 1 or n_mp < 0 or len(ol) != len(ok) or len(sv) != len(sm) or (nb is not None and len(nb) != n_mp):
+    if not fits or len(ol) != len(ok) or len(sv) != len(sm) or (nb is not None and len(nb) != n_mp):
         raise ValueError('redundant_observations: obs_offsets needs n_mp + 1 entries, subj_offsets n_subj + 1, mp_nobs n_mp, a level per observation and entry')
     n_mps = np.zeros(max(n_subj, 1), np.int32)
     n_red = np.zeros(max(n_subj, 1), np.int32)
     L = load_library()
-    rc = L.orbfe_redundant_observations(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _p(ok) if len(ok) else None,
-                                        _p(ol) if len(ol) else None, None if nb is None else _p(nb), n_subj, _p(ss) if n_subj else None, _p(so),
-                                        _p(sm) if len(sm) else None, _p(sv) if len(sv) else None, int(th_obs), _p(n_mps), _p(n_red))
+    rc = L.orbfe_redundant_observations(None if matcher is None else matcher.h, n_kf, n_mp, _p(oo), _pn(ok), _pn(ol),
+                                        None if nb is None else _p(nb), n_subj, _pn(ss), _p(so), _pn(sm), _pn(sv), int(th_obs), _p(n_mps), _p(n_red))
     if rc != 0:
         raise OrbfeError(rc, L.orbfe_last_error().decode('utf-8', 'replace'))
     return n_mps[:n_subj].copy(), n_red[:n_subj].copy()

@@ -1,6 +1,7 @@
 // orbfe_covis.hip -- the counting loop of KeyFrame::UpdateConnections (reference src/KeyFrame.cc:305-331) and of
 // Tracking::UpdateLocalKeyFrames (src/Tracking.cc:862-879) for a batch of subjects.  C ABI: include/orbfe.h (covisibility
-// section); the argument check, the output bound and the host-side assembly are in covis_plan.h.
+// section); the argument check, the output bound and the host-side assembly are in covis_plan.h, the staging of the two CSRs,
+// which orbfe_redundant_observations takes too, in obs_graph_staging.h.
 //
 // Two CSRs of indices come up: MapPoint -> slots of the keyframes that observe it, subject -> MapPoints of its keypoints.  One
 // workgroup owns one subject and keeps an int32 histogram over observer slots in LDS.  Its lanes stride over the subject's
@@ -21,6 +22,7 @@
 #include "orbfe_matcher_internal.h"
 
 #include "covis_plan.h"
+#include "obs_graph_staging.h"
 
 namespace {
 
@@ -116,25 +118,6 @@ __global__ __launch_bounds__(kThreads) void k_covisibility(CovisParams P) {
   }
 }
 
-struct CovisScratch {
-  DevBuf<uint8_t> d_in, d_out;
-  PinBuf<uint8_t> h_in, h_out;
-  hipEvent_t t0 = nullptr, t1 = nullptr;   // around the launch
-  bool ldsAttr = false;
-  double ms[3] = {0, 0, 0};                // check + staging on the host, kernel, the whole call
-  ~CovisScratch() {
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-    d_in.release(); d_out.release(); h_in.release(); h_out.release();
-    (void)hipGetLastError();
-  }
-};
-
-CovisScratch* scratch_of(orbfe_matcher* m) {
-  if (!m->covis) m->covis = std::make_shared<CovisScratch>();
-  return static_cast<CovisScratch*>(m->covis.get());
-}
-
 }  // namespace
 
 extern "C" {
@@ -142,10 +125,7 @@ extern "C" {
 int orbfe_debug_covis_slots_per_pass(void) { return kSlots; }
 
 int orbfe_debug_covis_ms(const orbfe_matcher* m, double out[3]) {
-  if (!m || !out) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
-  const CovisScratch* S = static_cast<const CovisScratch*>(m->covis.get());
-  for (int k = 0; k < 3; k++) out[k] = S ? S->ms[k] : 0.0;
-  return ORBFE_OK;
+  return orbfe::ObsGraphScratch::lastMs(m ? &m->covis : nullptr, out);
 }
 
 int orbfe_covisibility_counts(orbfe_matcher* m, int n_kf, int n_mp, const int32_t* obs_offsets, const int32_t* obs_kf, int n_subj,
@@ -174,43 +154,30 @@ int orbfe_covisibility_counts(orbfe_matcher* m, int n_kf, int n_mp, const int32_
   if (!m) { set_err("covisibility: null pointer (matcher)"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(m->device));
   (void)hipGetLastError();
-  CovisScratch* S = scratch_of(m);
+  orbfe::ObsGraphScratch* S = orbfe::ObsGraphScratch::of(m->covis);
 
-  // one page-locked arena, one copy up: the two CSRs rebased to 0, self and limit per subject
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  // one page-locked arena, one copy up: the graph (obs_graph_stage), then the limit per subject
   const size_t ns = (size_t)n_subj, pieces = ns * (size_t)plan.nPass;
-  const size_t oObsOffs = take(4 * ((size_t)n_mp + 1)), oObsKf = take(4 * plan.nObs + 4), oSelf = take(4 * ns), oLimit = take(4 * ns),
-               oSubjOffs = take(4 * (ns + 1)), oSubjMp = take(4 * plan.nEntries + 4), inBytes = o;
   const unsigned devCap = (unsigned)std::min<uint64_t>((uint64_t)cap, plan.bound);
-  o = 0;
-  const size_t oCursor = take(4), oStart = take(4 * pieces), oCount = take(4 * pieces), headBytes = o, oKf = take(4 * (size_t)devCap + 4),
-               oCnt = take(4 * (size_t)devCap + 4), outBytes = o;
+  orbfe::Arena out;
+  const size_t oCursor = out.take(4), oStart = out.take(4 * pieces), oCount = out.take(4 * pieces), headBytes = out.size,
+               oKf = out.take(4 * (size_t)devCap + 4), oCnt = out.take(4 * (size_t)devCap + 4), outBytes = out.size;
+  orbfe::ObsGraphStaged at;
   int rc;
-  if ((rc = S->h_in.ensure(inBytes)) || (rc = S->d_in.ensure(inBytes)) || (rc = S->h_out.ensure(outBytes)) || (rc = S->d_out.ensure(outBytes))) return rc;
-  if (!S->t0) {
-    HIP_TRY(hipEventCreate(&S->t0));
-    HIP_TRY(hipEventCreate(&S->t1));
-  }
+  if ((rc = orbfe::obs_graph_stage(*S, plan, n_mp, obs_offsets, obs_kf, nullptr, n_subj, subj_self, subj_offsets, subj_mp, nullptr, false, 4 * ns, outBytes, at)))
+    return rc;
   uint8_t* H = S->h_in.p;
-  int32_t* ho = (int32_t*)(H + oObsOffs);
-  for (int p = 0; p <= n_mp; p++) ho[p] = obs_offsets[p] - plan.obsBase;
-  if (plan.nObs) memcpy(H + oObsKf, obs_kf + plan.obsBase, 4 * plan.nObs);
-  memcpy(H + oSelf, subj_self, 4 * ns);
-  int32_t* hl = (int32_t*)(H + oLimit);
+  int32_t* hl = (int32_t*)(H + at.extra);
   for (int s = 0; s < n_subj; s++) hl[s] = subj_limit ? subj_limit[s] : n_kf;
-  int32_t* hs = (int32_t*)(H + oSubjOffs);
-  for (int s = 0; s <= n_subj; s++) hs[s] = subj_offsets[s] - plan.subjBase;
-  if (plan.nEntries) memcpy(H + oSubjMp, subj_mp + plan.subjBase, 4 * plan.nEntries);
   const double tStaged = orbfe_matcher::nowMs();
-  HIP_TRY(hipMemcpyAsync(S->d_in.p, H, inBytes, hipMemcpyHostToDevice, m->stream));
+  HIP_TRY(hipMemcpyAsync(S->d_in.p, H, at.bytes, hipMemcpyHostToDevice, m->stream));
   HIP_TRY(hipMemsetAsync(S->d_out.p + oCursor, 0, 4, m->stream));
 
   CovisParams P{};
   uint8_t* D = S->d_in.p;
-  P.obsOffs = (const int32_t*)(D + oObsOffs); P.obsKf = (const int32_t*)(D + oObsKf);
-  P.subjSelf = (const int32_t*)(D + oSelf); P.subjLimit = (const int32_t*)(D + oLimit);
-  P.subjOffs = (const int32_t*)(D + oSubjOffs); P.subjMp = (const int32_t*)(D + oSubjMp);
+  P.obsOffs = (const int32_t*)(D + at.obsOffs); P.obsKf = (const int32_t*)(D + at.obsKf);
+  P.subjSelf = (const int32_t*)(D + at.self); P.subjLimit = (const int32_t*)(D + at.extra);
+  P.subjOffs = (const int32_t*)(D + at.subjOffs); P.subjMp = (const int32_t*)(D + at.subjMp);
   P.nPass = plan.nPass;
   P.bins = std::max(1, std::min(n_kf, kSlots));
   P.cap = devCap;

@@ -1,5 +1,6 @@
 // orbfe_culling.hip -- the counting loop of LocalMapping::KeyFrameCulling (reference src/LocalMapping.cc:574-598) for a batch of
-// subjects.  C ABI: include/orbfe.h (keyframe culling section); the argument check is in culling_plan.h; what follows the counting
+// subjects.  C ABI: include/orbfe.h (keyframe culling section); the argument check is in culling_plan.h, the staging of the two CSRs,
+// which orbfe_covisibility_counts takes too, in obs_graph_staging.h; what follows the counting
 // (the 90 % test, SetBadFlag, the recount after a cull) is include/orbfe/KeyFrameCulling.h.
 //
 // The CSRs of orbfe_covisibility_counts come up, with a level byte next to every observation and every entry.  The work is all
@@ -14,6 +15,7 @@
 #include "orbfe_matcher_internal.h"
 
 #include "culling_plan.h"
+#include "obs_graph_staging.h"
 
 namespace {
 
@@ -85,33 +87,12 @@ __global__ __launch_bounds__(kThreads) void k_redundant_observations(CullParams 
   }
 }
 
-struct CullingScratch {
-  DevBuf<uint8_t> d_in, d_out;
-  PinBuf<uint8_t> h_in, h_out;
-  hipEvent_t t0 = nullptr, t1 = nullptr;   // around the launch
-  double ms[3] = {0, 0, 0};                // check + staging on the host, kernel, the whole call
-  ~CullingScratch() {
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-    d_in.release(); d_out.release(); h_in.release(); h_out.release();
-    (void)hipGetLastError();
-  }
-};
-
-CullingScratch* scratch_of(orbfe_matcher* m) {
-  if (!m->culling) m->culling = std::make_shared<CullingScratch>();
-  return static_cast<CullingScratch*>(m->culling.get());
-}
-
 }  // namespace
 
 extern "C" {
 
 int orbfe_debug_culling_ms(const orbfe_matcher* m, double out[3]) {
-  if (!m || !out) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
-  const CullingScratch* S = static_cast<const CullingScratch*>(m->culling.get());
-  for (int k = 0; k < 3; k++) out[k] = S ? S->ms[k] : 0.0;
-  return ORBFE_OK;
+  return orbfe::ObsGraphScratch::lastMs(m ? &m->culling : nullptr, out);
 }
 
 int orbfe_redundant_observations(orbfe_matcher* m, int n_kf, int n_mp, const int32_t* obs_offsets, const int32_t* obs_kf, const uint8_t* obs_level,
@@ -139,49 +120,31 @@ int orbfe_redundant_observations(orbfe_matcher* m, int n_kf, int n_mp, const int
   if (!m) { set_err("redundant observations: null pointer (matcher)"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(m->device));
   (void)hipGetLastError();
-  CullingScratch* S = scratch_of(m);
+  orbfe::ObsGraphScratch* S = orbfe::ObsGraphScratch::of(m->culling);
 
-  // one page-locked arena, one copy up: the two CSRs rebased to 0, their level bytes, Observations() per MapPoint, self per subject
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+  // one page-locked arena, one copy up: the graph with its level bytes (obs_graph_stage), then Observations() per MapPoint
   const size_t ns = (size_t)n_subj;
-  const size_t oObsOffs = take(4 * ((size_t)n_mp + 1)), oObsKf = take(4 * plan.nObs + 4), oObsLevel = take(plan.nObs + 4), oNobs = take(4 * (size_t)n_mp + 4),
-               oSelf = take(4 * ns), oSubjOffs = take(4 * (ns + 1)), oSubjMp = take(4 * plan.nEntries + 4), oSubjLevel = take(plan.nEntries + 4),
-               inBytes = o;
-  o = 0;
-  const size_t oMps = take(4 * ns), oRed = take(4 * ns), outBytes = o;
+  orbfe::Arena out;
+  const size_t oMps = out.take(4 * ns), oRed = out.take(4 * ns), outBytes = out.size;
+  orbfe::ObsGraphStaged at;
   int rc;
-  if ((rc = S->h_in.ensure(inBytes)) || (rc = S->d_in.ensure(inBytes)) || (rc = S->h_out.ensure(outBytes)) || (rc = S->d_out.ensure(outBytes))) return rc;
-  if (!S->t0) {
-    HIP_TRY(hipEventCreate(&S->t0));
-    HIP_TRY(hipEventCreate(&S->t1));
-  }
+  if ((rc = orbfe::obs_graph_stage(*S, plan, n_mp, obs_offsets, obs_kf, obs_level, n_subj, subj_self, subj_offsets, subj_mp, subj_level, true,
+                                   4 * (size_t)n_mp + 4, outBytes, at)))
+    return rc;
   uint8_t* H = S->h_in.p;
-  int32_t* ho = (int32_t*)(H + oObsOffs);
-  for (int p = 0; p <= n_mp; p++) ho[p] = obs_offsets[p] - plan.obsBase;
-  if (plan.nObs) {
-    memcpy(H + oObsKf, obs_kf + plan.obsBase, 4 * plan.nObs);
-    memcpy(H + oObsLevel, obs_level + plan.obsBase, plan.nObs);
-  }
-  int32_t* hn = (int32_t*)(H + oNobs);
+  const int32_t* ho = (const int32_t*)(H + at.obsOffs);
+  int32_t* hn = (int32_t*)(H + at.extra);
   for (int p = 0; p < n_mp; p++) hn[p] = mp_nobs ? mp_nobs[p] : ho[p + 1] - ho[p];
-  memcpy(H + oSelf, subj_self, 4 * ns);
-  int32_t* hs = (int32_t*)(H + oSubjOffs);
-  for (int s = 0; s <= n_subj; s++) hs[s] = subj_offsets[s] - plan.subjBase;
-  if (plan.nEntries) {
-    memcpy(H + oSubjMp, subj_mp + plan.subjBase, 4 * plan.nEntries);
-    memcpy(H + oSubjLevel, subj_level + plan.subjBase, plan.nEntries);
-  }
   const double tStaged = orbfe_matcher::nowMs();
-  HIP_TRY(hipMemcpyAsync(S->d_in.p, H, inBytes, hipMemcpyHostToDevice, m->stream));
+  HIP_TRY(hipMemcpyAsync(S->d_in.p, H, at.bytes, hipMemcpyHostToDevice, m->stream));
   HIP_TRY(hipMemsetAsync(S->d_out.p, 0, outBytes, m->stream));
 
   CullParams P{};
   uint8_t* D = S->d_in.p;
-  P.obsOffs = (const int32_t*)(D + oObsOffs); P.obsKf = (const int32_t*)(D + oObsKf); P.obsLevel = D + oObsLevel;
-  P.mpNobs = (const int32_t*)(D + oNobs);
-  P.subjSelf = (const int32_t*)(D + oSelf); P.subjOffs = (const int32_t*)(D + oSubjOffs);
-  P.subjMp = (const int32_t*)(D + oSubjMp); P.subjLevel = D + oSubjLevel;
+  P.obsOffs = (const int32_t*)(D + at.obsOffs); P.obsKf = (const int32_t*)(D + at.obsKf); P.obsLevel = D + at.obsLevel;
+  P.mpNobs = (const int32_t*)(D + at.extra);
+  P.subjSelf = (const int32_t*)(D + at.self); P.subjOffs = (const int32_t*)(D + at.subjOffs);
+  P.subjMp = (const int32_t*)(D + at.subjMp); P.subjLevel = D + at.subjLevel;
   P.nSubj = n_subj; P.nEntries = (int)plan.nEntries; P.thObs = th_obs;
   P.outMps = (int32_t*)(S->d_out.p + oMps); P.outRed = (int32_t*)(S->d_out.p + oRed);
   HIP_TRY(hipEventRecord(S->t0, m->stream));

@@ -166,10 +166,10 @@ def small_map(seed=11, n_kf=40, entries=200):
 SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all']
 
 
-def compile_plan_test(out, sanitize=True):
-    """os1_amd/csrc/covis_plan.h as a program of its own, the sanitizers linked into that program"""
-    cmd = ['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-I' + os.path.join(ROOT, 'os1_amd', 'csrc'),
-           os.path.join(CPP, 'covis_plan_test.cpp'), '-o', out]
+def compile_plan_test(out, sanitize=True, src='covis_plan_test.cpp'):
+    """os1_amd/csrc/covis_plan.h (or, with src given, another plan header's test) as a program of its own; the sanitizers, where
+    asked for, linked into that program"""
+    cmd = ['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-I' + os.path.join(ROOT, 'os1_amd', 'csrc'), os.path.join(CPP, src), '-o', out]
     if sanitize:
         cmd[1:1] = SANITIZE
     subprocess.check_call(cmd)

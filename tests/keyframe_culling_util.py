@@ -7,6 +7,8 @@ import subprocess
 
 import numpy as np
 
+import covisibility_util
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, 'tests', 'cpp')
 REF_SRC = os.path.join(CPP, 'keyframe_culling_ref.cpp')
@@ -260,17 +262,12 @@ def culling_job(seed=3, n_subj=100, entries=1000, obs=(2, 40)):
 # ---------------------------------------------------------------------------------------------------------------------
 # the stand-alone programs
 # ---------------------------------------------------------------------------------------------------------------------
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+SANITIZE = covisibility_util.SANITIZE
 
 
 def compile_plan_test(out, sanitize):
     """os1_amd/csrc/culling_plan.h as a program of its own; the sanitizers, where asked for, linked into that program"""
-    cmd = ['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-I' + os.path.join(ROOT, 'os1_amd', 'csrc'),
-           os.path.join(CPP, 'culling_plan_test.cpp'), '-o', out]
-    if sanitize:
-        cmd[1:1] = SANITIZE
-    subprocess.check_call(cmd)
-    return out
+    return covisibility_util.compile_plan_test(out, sanitize, 'culling_plan_test.cpp')
 
 
 def _includes():

@@ -16,7 +16,8 @@ Shapes, each because the kernel can go wrong there (keyframe_culling_util.crafte
   a MapPoint named twice                         counts twice
   mp_nobs given, NULL, disagreeing with the CSR  Observations() decides, the CSR is counted
   rebased CSRs                                   offsets[0] > 0, junk in front that must not be read
-  a random map                                   40 keyframes of 300 entries, 2 to 30 observations, levels 0..7"""
+  a random map                                   40 keyframes of 300 entries, 2 to 30 observations, levels 0..7
+  covisibility and culling calls interleaved     the staging the two calls share, over buffers that are too large and that regrow"""
 import numpy as np
 import pytest
 
@@ -108,6 +109,51 @@ def test_two_calls_of_different_size_on_one_matcher_agree_with_fresh_matchers(wo
         finally:
             f.close()
         assert pairs(fresh) == pairs(got)
+
+
+def test_covisibility_and_culling_calls_interleaved_on_one_matcher(world):
+    """The two calls stage the same graph through one piece of code into grow-only buffers of their own.  On one matcher: a larger
+    covisibility call, a small culling call, a small covisibility call (its buffers are larger than it needs and hold the first
+    call's data), a larger culling call (its buffers regrow).  Larger: 300 MapPoints, 65 keyframes, 5 subjects of 150 entries -- every
+    part of the upload arena and covisibility's output arrays are past one 256-byte granule (culling's two output arrays are 4 bytes
+    per subject: one granule each up to 64 subjects) -- and MapPoint 0 is seen from all 65 keyframes, so that the wave route of
+    k_redundant_observations runs on the restaged data.  All outputs are integers and must equal the numpy counts."""
+    import covisibility_util as CU
+    w = world
+    rng = np.random.default_rng(23)
+    n_kf, n_mp = 65, 300
+    observers = [[(j, 0) for j in range(n_kf)]]
+    for _ in range(n_mp - 1):
+        slots = np.sort(rng.choice(n_kf, int(rng.integers(0, 13)), replace=False))
+        observers.append(list(zip(slots.tolist(), rng.integers(0, 8, len(slots)).tolist())))
+    subjects = []
+    for self_ in (0, 17, 64, -1, 3):
+        mp = rng.integers(0, n_mp, 150)
+        mp[rng.random(150) < 0.1] = -1
+        mp[7] = 0
+        subjects.append((self_, list(zip(mp.tolist(), rng.integers(0, 8, 150).tolist()))))
+    tiny_obs = [[(0, 0), (1, 1), (2, 0), (3, 2)], [(1, 0)], []]
+    tiny_subj = [(0, [(0, 1), (1, 0), (-1, 0)]), (-1, [(2, 1), (0, 3)])]
+
+    def covis(n, obs, subj):
+        return CU.Case(n, [[j for j, _ in o] for o in obs], [(s, None, [p for p, _ in e]) for s, e in subj])
+
+    big_covis, big_cull = covis(n_kf, observers, subjects), U.Case(n_kf, observers, subjects)
+    small_covis, small_cull = covis(4, tiny_obs, tiny_subj), U.Case(4, tiny_obs, tiny_subj)
+    assert big_cull.n_mp == 300 and big_cull.n_subj == 5 and small_cull.n_mp == 3 and small_cull.n_subj == 2
+    assert np.diff(big_cull.obs_offsets).max() == 65 > U.LONG and len(big_cull.obs_level) > 256 and CU.np_counts(big_covis)[0][-1] > 64
+    m = w.api.Matcher(0)
+    try:
+        got = [w.api.covisibility_counts(m, *big_covis.args()), m.redundant_observations(*small_cull.args()),
+               w.api.covisibility_counts(m, *small_covis.args()), m.redundant_observations(*big_cull.args())]
+    finally:
+        m.close()
+    expect = [CU.np_counts(big_covis), U.np_counts(small_cull), CU.np_counts(small_covis), U.np_counts(big_cull)]
+    for k, (g, e) in enumerate(zip(got, expect)):
+        assert len(g) == len(e)
+        for a, b in zip(g, e):
+            assert a.dtype == np.int32 and np.array_equal(a, b), (k, a.tolist(), b.tolist())
+    assert pairs(got[1]) == [(2, 1), (2, 1)] and got[3][1].sum() > 0      # the small culling call by hand; the larger one finds redundancy
 
 
 def test_refusals_with_a_live_matcher(world):
