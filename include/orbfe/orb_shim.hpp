@@ -895,6 +895,18 @@ inline bool projectIntoKeyFrame(KeyFrameT* pKF, MapPointT* pMP, const float Rcw[
   S.valid[i] = 1;
   return true;
 }
+// the row of MapPoint p in the context's local-map table (MatcherContext::localMapRow): what `geometry` hands over, then
+// GetDescriptor()
+template <class MapPointT, class GeometryFn>
+inline int32_t sourceRow(MatcherContext& ctx, MapPointT* p, GeometryFn& geometry) {
+  float row[16];
+  float& minRaw = row[6];
+  float& maxRaw = row[7];
+  geometry(p, row, row + 3, minRaw, maxRaw);
+  const auto d = p->GetDescriptor();
+  std::memcpy(row + 8, d.data, 32);
+  return ctx.localMapRow(p, reinterpret_cast<const uint8_t*>(row));
+}
 }  // namespace detail
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -936,13 +948,7 @@ inline int SearchLocalPoints(MatcherContext& ctx, FrameT& F, const std::vector<M
     if (p->mnLastFrameSeen == F.mnId) { flags[i] = ORBFE_MP_SKIP; continue; }   // Tracking.cc:804-805
     if (p->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                       // :806-807
     flags[i] = (uint8_t)((p->plCandidato ? ORBFE_MP_CANDIDATO : 0) | (p->Observations() > 0 ? ORBFE_MP_OBSERVED : 0));
-    float row[16];
-    float& minRaw = row[6];
-    float& maxRaw = row[7];
-    geometry(p, row, row + 3, minRaw, maxRaw);
-    const auto d = p->GetDescriptor();
-    std::memcpy(row + 8, d.data, 32);
-    rows[i] = ctx.localMapRow(p, reinterpret_cast<const uint8_t*>(row));
+    rows[i] = detail::sourceRow(ctx, p, geometry);
   }
   ctx.localMapCommit();
   orbfe_frame* rf = ctx.resident(F, 0);
@@ -977,67 +983,193 @@ inline int SearchLocalPoints(MatcherContext& ctx, FrameT& F, const std::vector<M
   return nmatches;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The six pose-driven searches: ONE function per search, TWO middles.
+// Each search is written once, as a detail::...Impl that owns everything around the search itself -- the pose set-up, which
+// sources are projected (`classify(i)`: 0 = project, else the flag byte ORBFE_MP_SKIP / ORBFE_MP_BAD), the occupancy bytes
+// and the bookkeeping that follows -- and takes the middle step as a callable.  The two public forms of a search pass
+//   the host middle  (SearchByProjection / Fuse / SearchBySim3, the reference's names): project on the host where classify
+//                    allows it, then one windowed search (detail::searchProjectedUv into a Frame, searchProjected into a KeyFrame);
+//   the GPU middle   (SearchByProjectionLastFrame / ...KeyFrame / ...Scw, FuseKeyFrame, FuseScw, SearchBySim3Device; last argument
+//                    SearchLocalPoints' `geometry` functor): classify's byte and one row number per source (detail::sourceRows)
+//                    are all that crosses PCIe, then projection, windows and best match in one call.  The source frame's resident
+//                    copy supplies mvKeys[i].octave and mvKeysUn[i].angle (both copies of one record: Frame::UndistortKeyPoints
+//                    replaces pt only); positions, normals, depth ranges and descriptors are rows of the context's local-map
+//                    table -- SearchLocalPoints' rows, so a MapPoint keeps ONE row and only changed rows are sent.  The fused
+//                    keyframe call refuses a valid point whose predicted level lies outside the keyframe's pyramid (the
+//                    reference would index mvScaleFactors out of range with it).
+// A GPU form first makes its frames resident; when it cannot (frame cache off, sizes that do not line up, a pyramid the fused
+// call does not take) it IS the host form, with the caller's Ops.  All twelve take `class Ops = detail::RestatedOps` first;
+// SearchByProjectionLastFrame / ...KeyFrame gained it last, and as no call names Ops for these two (their other template
+// parameters are deduced) every existing call compiles to what it did.
+// ---------------------------------------------------------------------------------------------------------------
+namespace detail {
+template <class Ops, class FrameT>
+inline void currentCamera(const FrameT& F, OrbfeCamera& cam) {
+  poseRt(F.mTcw, cam.Rcw, cam.tcw);
+  Ops::gemmT3(cam.Rcw, cam.tcw, -1.0, cam.Ow);   // -Rcw.t()*tcw (ORBmatcher.cc:1431; the LastFrame form does not read it)
+  cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy;
+  cam.logScaleFactor = F.mfLogScaleFactor;
+}
+// one windowed search of sources projected on the host into a Frame (the two frame-side host middles), as searchProjected
+// is for a KeyFrame
+template <class FrameT>
+inline int searchProjectedUv(MatcherContext& ctx, FrameT& F, const uint8_t* occ, const float* uv, const int32_t* lvl, const float* ang,
+                             const uint8_t* flags, const uint8_t* valid, const uint8_t* sdesc, int ns, float th, int max_dist,
+                             int skip_any_occupied, bool checkOrientation, int32_t* assigned) {
+  const int n = (int)F.mvKeysUn.size();
+  std::vector<uint8_t> tmp;
+  float b[4];
+  frameBounds(F, b);
+  int nmatches = 0;
+  if (orbfe_frame* rf = ctx.resident(F, 0))
+    check(orbfe_search_by_projection_uv_frame(ctx.get(), rf, F.mvScaleFactors.data(), (int)F.mvScaleFactors.size(), occ, uv, lvl, ang,
+                                              flags, valid, sdesc, ns, th, max_dist, skip_any_occupied, checkOrientation ? 1 : 0,
+                                              assigned, &nmatches));
+  else
+    check(orbfe_search_by_projection_uv(ctx.get(), reinterpret_cast<const OrbfeKeyPoint*>(F.mvKeysUn.data()),
+                                        packedDescriptors(F.mDescriptors, n, tmp), n, b, F.mvScaleFactors.data(),
+                                        (int)F.mvScaleFactors.size(), occ, uv, lvl, ang, flags, valid, sdesc, ns, th, max_dist,
+                                        skip_any_occupied, checkOrientation ? 1 : 0, assigned, &nmatches));
+  return nmatches;
+}
+// the source loop of every GPU middle: flags[i] = classify(i), and the local-map row of each source that is projected
+template <class PointsT, class Classify, class GeometryFn>
+inline void sourceRows(MatcherContext& ctx, const PointsT& pts, int ns, Classify classify, GeometryFn& geometry, uint8_t*& flags,
+                       int32_t*& rows) {
+  flags = ctx.scratch<uint8_t>(1, ns, true);
+  rows = ctx.scratch<int32_t>(2, ns, true);
+  ctx.localMapBegin((size_t)ns);
+  for (int i = 0; i < ns; i++) {
+    flags[i] = classify(i);
+    if (!(flags[i] & (ORBFE_MP_SKIP | ORBFE_MP_BAD))) rows[i] = sourceRow(ctx, pts[i], geometry);
+  }
+  ctx.localMapCommit();
+}
+// the GPU middle of the two frame-side searches
+template <class Ops, class FrameT, class PointsT, class Classify, class GeometryFn>
+inline int searchSourcesFrame(MatcherContext& ctx, orbfe_frame* cur, orbfe_frame* src, const FrameT& CurrentFrame, int source_mode,
+                              const PointsT& pts, int ns, Classify classify, GeometryFn& geometry, const uint8_t* occ, float th,
+                              int max_dist, bool checkOrientation, int32_t* assigned) {
+  uint8_t* flags;
+  int32_t* rows;
+  sourceRows(ctx, pts, ns, classify, geometry, flags, rows);
+  OrbfeCamera cam;
+  currentCamera<Ops>(CurrentFrame, cam);
+  int nmatches = 0, nValid = 0;
+  check(orbfe_search_by_projection_sources_frame(ctx.get(), cur, src, ctx.localMap(), &cam, source_mode, rows, flags, ns,
+                                                 CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ, th,
+                                                 max_dist, checkOrientation ? 1 : 0, nullptr, nullptr, nullptr, assigned, &nmatches,
+                                                 &nValid));
+  return nmatches;
+}
+// the write-back of the two frame-side searches: assigned[i] >= 0 is a source index, -2 a match the rotation check took
+// away (:1409-1419, :1538-1548)
+template <class FrameT, class PointsT>
+inline void assignFromSources(FrameT& CurrentFrame, const int32_t* assigned, const PointsT& sources) {
+  const int n = (int)CurrentFrame.mvKeysUn.size();
+  for (int i = 0; i < n; i++) {
+    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = sources[assigned[i]];
+    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;
+  }
+}
+
+// SearchByProjection(Cur, Last, th).  middle(classify, occ, assigned) -> nmatches.  ORBFE_MP_OBSERVED is not classify's: each
+// middle reads Observations() where it does today (the host one after the projection, for the sources that survive it).
+template <class FrameT, class Middle>
+inline int searchByProjectionLastFrameImpl(MatcherContext& ctx, FrameT& CurrentFrame, const FrameT& LastFrame, Middle middle) {
+  const int n = (int)CurrentFrame.mvKeysUn.size();
+  // the context's page-locked arrays (see SearchByProjection(F, MapPoints) above)
+  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
+  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
+  for (int i = 0; i < n; i++)
+    if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) occ[i] = 1;   // :1364-1366
+  auto classify = [&](int i) -> uint8_t {                                                                // :1318-1321
+    return !LastFrame.mvpMapPoints[i] || LastFrame.mvbOutlier[i] ? (uint8_t)ORBFE_MP_SKIP : (uint8_t)0;
+  };
+  const int nmatches = middle(classify, occ, assigned);
+  assignFromSources(CurrentFrame, assigned, LastFrame.mvpMapPoints);
+  return nmatches;
+}
+// SearchByProjection(Cur, pKF, sAlreadyFound, th, ORBdist).  occ[n] zeroed and assigned[n] are the caller's (std::vector in
+// the host form, page-locked in the GPU form); middle(classify) -> nmatches.
+template <class FrameT, class PointsT, class SetT, class Middle>
+inline int searchByProjectionKeyFrameImpl(FrameT& CurrentFrame, const PointsT& vpMPs, const SetT& sAlreadyFound, uint8_t* occ,
+                                          const int32_t* assigned, Middle middle) {
+  const int n = (int)CurrentFrame.mvKeysUn.size();
+  for (int i = 0; i < n; i++)
+    if (CurrentFrame.mvpMapPoints[i]) occ[i] = 1;                         // :1493-1494
+  auto classify = [&](int i) -> uint8_t {
+    auto* pMP = vpMPs[i];
+    if (!pMP) return ORBFE_MP_SKIP;
+    if (pMP->isBad()) return ORBFE_MP_BAD;                                // :1447
+    return sAlreadyFound.count(pMP) ? (uint8_t)ORBFE_MP_SKIP : (uint8_t)0;
+  };
+  const int nmatches = middle(classify);
+  assignFromSources(CurrentFrame, assigned, vpMPs);
+  return nmatches;
+}
+}  // namespace detail
+
 // int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th)   (ORBmatcher.cc:1292-1423)
 template <class Ops = detail::RestatedOps, class FrameT>
 inline int SearchByProjection(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, const FrameT& LastFrame,
                               const float th) {
-  float Rcw[9], tcw[3];
-  detail::poseRt(CurrentFrame.mTcw, Rcw, tcw);
-  const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)LastFrame.N;
-  // the context's page-locked arrays (see SearchByProjection(F, MapPoints) above); valid / flags / levels zeroed
-  float* uv = ctx.scratch<float>(3, (size_t)ns * 2, true);
-  float* ang = ctx.scratch<float>(4, ns, true);
-  int32_t* lvl = ctx.scratch<int32_t>(5, ns, true);
-  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
-  uint8_t* valid = ctx.scratch<uint8_t>(7, ns, true);
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  uint8_t* sdesc = ctx.scratch<uint8_t>(2, (size_t)ns * 32, false);
-  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
-  std::vector<uint8_t> tmp;
-  for (int i = 0; i < n; i++) assigned[i] = -1;
-  for (int i = 0; i < n; i++)
-    if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) occ[i] = 1;   // :1364-1366
-  for (int i = 0; i < ns; i++) {
-    auto* pMP = LastFrame.mvpMapPoints[i];
-    if (!pMP || LastFrame.mvbOutlier[i]) continue;
-    float x3Dw[3], x3Dc[3];
-    detail::vec3(pMP->GetWorldPos(), x3Dw);
-    Ops::gemm3(Rcw, x3Dw, 1.0, tcw, 1.0, x3Dc);                       // Rcw*x3Dw+tcw
-    const float xc = x3Dc[0], yc = x3Dc[1];
-    const float invzc = (float)(1.0 / x3Dc[2]);
-    if (invzc < 0) continue;
-    const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
-    const float v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
-    if (u < CurrentFrame.mnMinX || u > CurrentFrame.mnMaxX) continue;
-    if (v < CurrentFrame.mnMinY || v > CurrentFrame.mnMaxY) continue;
-    uv[2 * i] = u; uv[2 * i + 1] = v;
-    lvl[i] = LastFrame.mvKeys[i].octave;                              // nLastOctave
-    ang[i] = LastFrame.mvKeysUn[i].angle;
-    flags[i] = pMP->Observations() > 0 ? ORBFE_MP_OBSERVED : 0;
-    const auto d = pMP->GetDescriptor();
-    std::memcpy(&sdesc[(size_t)i * 32], d.data, 32);
-    valid[i] = 1;
-  }
-  float b[4];
-  detail::frameBounds(CurrentFrame, b);
-  int nmatches = 0;
-  if (orbfe_frame* rf = ctx.resident(CurrentFrame, 0))
-    check(orbfe_search_by_projection_uv_frame(ctx.get(), rf, CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(),
-                                              occ, uv, lvl, ang, flags, valid, sdesc,
-                                              ns, th, /*TH_HIGH*/ 100, /*skip_any_occupied*/ 0, mbCheckOrientation ? 1 : 0,
-                                              assigned, &nmatches));
-  else
-    check(orbfe_search_by_projection_uv(ctx.get(), reinterpret_cast<const OrbfeKeyPoint*>(CurrentFrame.mvKeysUn.data()),
-                                        detail::packedDescriptors(CurrentFrame.mDescriptors, n, tmp), n, b,
-                                        CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ,
-                                        uv, lvl, ang, flags, valid, sdesc, ns, th,
-                                        /*TH_HIGH*/ 100, /*skip_any_occupied*/ 0, mbCheckOrientation ? 1 : 0, assigned,
-                                        &nmatches));
-  for (int i = 0; i < n; i++) {
-    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[assigned[i]];
-    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;    // rotation check, :1409-1419
-  }
-  return nmatches;
+  return detail::searchByProjectionLastFrameImpl(ctx, CurrentFrame, LastFrame, [&](auto classify, const uint8_t* occ, int32_t* assigned) {
+    float Rcw[9], tcw[3];
+    detail::poseRt(CurrentFrame.mTcw, Rcw, tcw);
+    const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)LastFrame.N;
+    // page-locked as well; valid / flags / levels zeroed
+    float* uv = ctx.scratch<float>(3, (size_t)ns * 2, true);
+    float* ang = ctx.scratch<float>(4, ns, true);
+    int32_t* lvl = ctx.scratch<int32_t>(5, ns, true);
+    uint8_t* valid = ctx.scratch<uint8_t>(7, ns, true);
+    uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
+    uint8_t* sdesc = ctx.scratch<uint8_t>(2, (size_t)ns * 32, false);
+    for (int i = 0; i < n; i++) assigned[i] = -1;
+    // (locals: the byte stores below could alias what the closure refers to, and every source would load it again)
+    const auto fx = CurrentFrame.fx, fy = CurrentFrame.fy, cx = CurrentFrame.cx, cy = CurrentFrame.cy;
+    const auto minX = CurrentFrame.mnMinX, maxX = CurrentFrame.mnMaxX, minY = CurrentFrame.mnMinY, maxY = CurrentFrame.mnMaxY;
+    for (int i = 0; i < ns; i++) {
+      if (classify(i)) continue;
+      auto* pMP = LastFrame.mvpMapPoints[i];
+      float x3Dw[3], x3Dc[3];
+      detail::vec3(pMP->GetWorldPos(), x3Dw);
+      Ops::gemm3(Rcw, x3Dw, 1.0, tcw, 1.0, x3Dc);                       // Rcw*x3Dw+tcw
+      const float xc = x3Dc[0], yc = x3Dc[1];
+      const float invzc = (float)(1.0 / x3Dc[2]);
+      if (invzc < 0) continue;
+      const float u = fx * xc * invzc + cx;
+      const float v = fy * yc * invzc + cy;
+      if (u < minX || u > maxX) continue;
+      if (v < minY || v > maxY) continue;
+      uv[2 * i] = u; uv[2 * i + 1] = v;
+      lvl[i] = LastFrame.mvKeys[i].octave;                              // nLastOctave
+      ang[i] = LastFrame.mvKeysUn[i].angle;
+      flags[i] = pMP->Observations() > 0 ? ORBFE_MP_OBSERVED : 0;
+      const auto d = pMP->GetDescriptor();
+      std::memcpy(&sdesc[(size_t)i * 32], d.data, 32);
+      valid[i] = 1;
+    }
+    return detail::searchProjectedUv(ctx, CurrentFrame, occ, uv, lvl, ang, flags, valid, sdesc, ns, th, /*TH_HIGH*/ 100,
+                                     /*skip_any_occupied*/ 0, mbCheckOrientation, assigned);
+  });
+}
+template <class Ops = detail::RestatedOps, class FrameT, class GeometryFn>
+inline int SearchByProjectionLastFrame(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, const FrameT& LastFrame,
+                                       const float th, GeometryFn geometry) {
+  const int ns = (int)LastFrame.mvKeysUn.size();
+  orbfe_frame* src = ctx.resident(LastFrame, 0);
+  orbfe_frame* cur = src ? ctx.resident(CurrentFrame, 0) : nullptr;   // (never evicts src: the two most recent frames stay)
+  if (!src || !cur || ns != (int)LastFrame.mvpMapPoints.size()) return SearchByProjection<Ops>(ctx, mbCheckOrientation, CurrentFrame, LastFrame, th);
+  return detail::searchByProjectionLastFrameImpl(ctx, CurrentFrame, LastFrame, [&](auto classify, const uint8_t* occ, int32_t* assigned) {
+    auto flag = [&](int i) -> uint8_t {
+      if (const uint8_t f = classify(i)) return f;
+      return LastFrame.mvpMapPoints[i]->Observations() > 0 ? (uint8_t)ORBFE_MP_OBSERVED : (uint8_t)0;
+    };
+    return detail::searchSourcesFrame<Ops>(ctx, cur, src, CurrentFrame, ORBFE_SRC_LAST_FRAME, LastFrame.mvpMapPoints, ns, flag, geometry,
+                                           occ, th, /*TH_HIGH*/ 100, mbCheckOrientation, assigned);
+  });
 }
 
 // int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound,
@@ -1052,262 +1184,183 @@ inline int SearchByProjection(MatcherContext& ctx, bool mbCheckOrientation, Fram
   const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)vpMPs.size();
   std::vector<float> uv((size_t)ns * 2, 0.f), ang(ns, 0.f);
   std::vector<int32_t> lvl(ns, 0), assigned(n > 0 ? n : 1, -1);
-  std::vector<uint8_t> valid(ns, 0), flags(ns, 0), sdesc((size_t)ns * 32, 0), occ(n > 0 ? n : 1, 0), tmp;
-  for (int i = 0; i < n; i++)
-    if (CurrentFrame.mvpMapPoints[i]) occ[i] = 1;                         // :1493-1494
-  for (int i = 0; i < ns; i++) {
-    auto* pMP = vpMPs[i];
-    if (!pMP) continue;
-    if (pMP->isBad() || sAlreadyFound.count(pMP)) continue;
-    float x3Dw[3], x3Dc[3];
-    detail::vec3(pMP->GetWorldPos(), x3Dw);
-    Ops::gemm3(Rcw, x3Dw, 1.0, tcw, 1.0, x3Dc);
-    const float xc = x3Dc[0], yc = x3Dc[1];
-    const float invzc = (float)(1.0 / x3Dc[2]);
-    const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
-    const float v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
-    if (u < CurrentFrame.mnMinX || u > CurrentFrame.mnMaxX) continue;
-    if (v < CurrentFrame.mnMinY || v > CurrentFrame.mnMaxY) continue;
-    const float PO[3] = {x3Dw[0] - Ow[0], x3Dw[1] - Ow[1], x3Dw[2] - Ow[2]};
-    const float dist3D = (float)Ops::norm3(PO);
-    const float maxDistance = pMP->GetMaxDistanceInvariance(), minDistance = pMP->GetMinDistanceInvariance();
-    if (dist3D < minDistance || dist3D > maxDistance) continue;
-    uv[2 * i] = u; uv[2 * i + 1] = v;
-    lvl[i] = pMP->PredictScale(dist3D, CurrentFrame.mfLogScaleFactor);
-    ang[i] = pKF->mvKeysUn[i].angle;
-    const auto d = pMP->GetDescriptor();
-    std::memcpy(&sdesc[(size_t)i * 32], d.data, 32);
-    valid[i] = 1;
-  }
-  float b[4];
-  detail::frameBounds(CurrentFrame, b);
-  int nmatches = 0;
-  if (orbfe_frame* rf = ctx.resident(CurrentFrame, 0))
-    check(orbfe_search_by_projection_uv_frame(ctx.get(), rf, CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(),
-                                              occ.data(), uv.data(), lvl.data(), ang.data(), flags.data(), valid.data(), sdesc.data(),
-                                              ns, th, ORBdist, /*skip_any_occupied*/ 1, mbCheckOrientation ? 1 : 0, assigned.data(),
-                                              &nmatches));
-  else
-    check(orbfe_search_by_projection_uv(ctx.get(), reinterpret_cast<const OrbfeKeyPoint*>(CurrentFrame.mvKeysUn.data()),
-                                        detail::packedDescriptors(CurrentFrame.mDescriptors, n, tmp), n, b,
-                                        CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ.data(),
-                                        uv.data(), lvl.data(), ang.data(), flags.data(), valid.data(), sdesc.data(), ns, th, ORBdist,
-                                        /*skip_any_occupied*/ 1, mbCheckOrientation ? 1 : 0, assigned.data(), &nmatches));
-  for (int i = 0; i < n; i++) {
-    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = vpMPs[assigned[i]];
-    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;
-  }
-  return nmatches;
+  std::vector<uint8_t> valid(ns, 0), flags(ns, 0), sdesc((size_t)ns * 32, 0), occ(n > 0 ? n : 1, 0);
+  return detail::searchByProjectionKeyFrameImpl(CurrentFrame, vpMPs, sAlreadyFound, occ.data(), assigned.data(), [&](auto classify) {
+    for (int i = 0; i < ns; i++) {
+      if (classify(i)) continue;
+      auto* pMP = vpMPs[i];
+      float x3Dw[3], x3Dc[3];
+      detail::vec3(pMP->GetWorldPos(), x3Dw);
+      Ops::gemm3(Rcw, x3Dw, 1.0, tcw, 1.0, x3Dc);
+      const float xc = x3Dc[0], yc = x3Dc[1];
+      const float invzc = (float)(1.0 / x3Dc[2]);
+      const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
+      const float v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
+      if (u < CurrentFrame.mnMinX || u > CurrentFrame.mnMaxX) continue;
+      if (v < CurrentFrame.mnMinY || v > CurrentFrame.mnMaxY) continue;
+      const float PO[3] = {x3Dw[0] - Ow[0], x3Dw[1] - Ow[1], x3Dw[2] - Ow[2]};
+      const float dist3D = (float)Ops::norm3(PO);
+      const float maxDistance = pMP->GetMaxDistanceInvariance(), minDistance = pMP->GetMinDistanceInvariance();
+      if (dist3D < minDistance || dist3D > maxDistance) continue;
+      uv[2 * i] = u; uv[2 * i + 1] = v;
+      lvl[i] = pMP->PredictScale(dist3D, CurrentFrame.mfLogScaleFactor);
+      ang[i] = pKF->mvKeysUn[i].angle;
+      const auto d = pMP->GetDescriptor();
+      std::memcpy(&sdesc[(size_t)i * 32], d.data, 32);
+      valid[i] = 1;
+    }
+    return detail::searchProjectedUv(ctx, CurrentFrame, occ.data(), uv.data(), lvl.data(), ang.data(), flags.data(), valid.data(),
+                                     sdesc.data(), ns, th, ORBdist, /*skip_any_occupied*/ 1, mbCheckOrientation, assigned.data());
+  });
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// The two searches above with their projection loops on the GPU (orbfe_search_by_projection_sources_frame): the source
-// frame's resident copy supplies mvKeys[i].octave and mvKeysUn[i].angle (both copies of one record: Frame::UndistortKeyPoints
-// replaces pt only), the MapPoints' positions, depth ranges and descriptors are rows of the context's local-map table -- the
-// rows SearchLocalPoints uses, so a MapPoint known to either keeps ONE row, and only rows whose content changed are sent.
-// Per call and source keypoint one row number and one flag byte cross PCIe.  `geometry` is SearchLocalPoints' functor.
-// With the frame cache off (or a source that cannot be made resident) they ARE the functions above.
-// ---------------------------------------------------------------------------------------------------------------
-namespace detail {
-template <class FrameT>
-inline void currentCamera(const FrameT& F, OrbfeCamera& cam) {
-  poseRt(F.mTcw, cam.Rcw, cam.tcw);
-  RestatedOps::gemmT3(cam.Rcw, cam.tcw, -1.0, cam.Ow);   // -Rcw.t()*tcw (ORBmatcher.cc:1431; the LastFrame form does not read it)
-  cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy;
-  cam.logScaleFactor = F.mfLogScaleFactor;
-}
-template <class MapPointT, class GeometryFn>
-inline int32_t sourceRow(MatcherContext& ctx, MapPointT* p, GeometryFn& geometry) {
-  float row[16];
-  float& minRaw = row[6];
-  float& maxRaw = row[7];
-  geometry(p, row, row + 3, minRaw, maxRaw);
-  const auto d = p->GetDescriptor();
-  std::memcpy(row + 8, d.data, 32);
-  return ctx.localMapRow(p, reinterpret_cast<const uint8_t*>(row));
-}
-}  // namespace detail
-
-// int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th)   (ORBmatcher.cc:1292-1423)
-template <class FrameT, class GeometryFn>
-inline int SearchByProjectionLastFrame(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, const FrameT& LastFrame,
-                                       const float th, GeometryFn geometry) {
-  const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)LastFrame.mvKeysUn.size();
-  orbfe_frame* src = ctx.resident(LastFrame, 0);
-  orbfe_frame* cur = src ? ctx.resident(CurrentFrame, 0) : nullptr;   // (never evicts src: the two most recent frames stay)
-  if (!src || !cur || ns != (int)LastFrame.mvpMapPoints.size()) return SearchByProjection(ctx, mbCheckOrientation, CurrentFrame, LastFrame, th);
-  uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
-  int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
-  for (int i = 0; i < n; i++)
-    if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) occ[i] = 1;   // :1363-1365
-  ctx.localMapBegin((size_t)ns);
-  for (int i = 0; i < ns; i++) {
-    auto* pMP = LastFrame.mvpMapPoints[i];
-    if (!pMP || LastFrame.mvbOutlier[i]) { flags[i] = ORBFE_MP_SKIP; continue; }   // :1318-1321
-    flags[i] = pMP->Observations() > 0 ? ORBFE_MP_OBSERVED : 0;
-    rows[i] = detail::sourceRow(ctx, pMP, geometry);
-  }
-  ctx.localMapCommit();
-  OrbfeCamera cam;
-  detail::currentCamera(CurrentFrame, cam);
-  int nmatches = 0, nValid = 0;
-  check(orbfe_search_by_projection_sources_frame(ctx.get(), cur, src, ctx.localMap(), &cam, ORBFE_SRC_LAST_FRAME, rows, flags, ns,
-                                                 CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ, th,
-                                                 /*TH_HIGH*/ 100, mbCheckOrientation ? 1 : 0, nullptr, nullptr, nullptr, assigned,
-                                                 &nmatches, &nValid));
-  for (int i = 0; i < n; i++) {
-    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[assigned[i]];
-    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;    // rotation check, :1409-1419
-  }
-  return nmatches;
-}
-
-// int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound,
-//                                    const float th, const int ORBdist)   (ORBmatcher.cc:1425-1552)
-template <class FrameT, class KeyFrameT, class SetT, class GeometryFn>
+template <class Ops = detail::RestatedOps, class FrameT, class KeyFrameT, class SetT, class GeometryFn>
 inline int SearchByProjectionKeyFrame(MatcherContext& ctx, bool mbCheckOrientation, FrameT& CurrentFrame, KeyFrameT* pKF,
                                       const SetT& sAlreadyFound, const float th, const int ORBdist, GeometryFn geometry) {
   const auto vpMPs = pKF->GetMapPointMatches();
   const int n = (int)CurrentFrame.mvKeysUn.size(), ns = (int)vpMPs.size();
   orbfe_frame* src = ns == (int)pKF->mvKeysUn.size() ? ctx.resident(*pKF, 1) : nullptr;
   orbfe_frame* cur = src ? ctx.resident(CurrentFrame, 0) : nullptr;
-  if (!src || !cur) return SearchByProjection(ctx, mbCheckOrientation, CurrentFrame, pKF, sAlreadyFound, th, ORBdist);
+  if (!src || !cur) return SearchByProjection<Ops>(ctx, mbCheckOrientation, CurrentFrame, pKF, sAlreadyFound, th, ORBdist);
   uint8_t* occ = ctx.scratch<uint8_t>(0, n, true);
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
   int32_t* assigned = ctx.scratch<int32_t>(6, n, false);
-  for (int i = 0; i < n; i++)
-    if (CurrentFrame.mvpMapPoints[i]) occ[i] = 1;                         // :1493-1494
-  ctx.localMapBegin((size_t)ns);
-  for (int i = 0; i < ns; i++) {
-    auto* pMP = vpMPs[i];
-    if (!pMP) { flags[i] = ORBFE_MP_SKIP; continue; }
-    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }              // :1447
-    if (sAlreadyFound.count(pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
-    rows[i] = detail::sourceRow(ctx, pMP, geometry);
-  }
-  ctx.localMapCommit();
-  OrbfeCamera cam;
-  detail::currentCamera(CurrentFrame, cam);
-  int nmatches = 0, nValid = 0;
-  check(orbfe_search_by_projection_sources_frame(ctx.get(), cur, src, ctx.localMap(), &cam, ORBFE_SRC_KEYFRAME, rows, flags, ns,
-                                                 CurrentFrame.mvScaleFactors.data(), (int)CurrentFrame.mvScaleFactors.size(), occ, th,
-                                                 ORBdist, mbCheckOrientation ? 1 : 0, nullptr, nullptr, nullptr, assigned, &nmatches,
-                                                 &nValid));
-  for (int i = 0; i < n; i++) {
-    if (assigned[i] >= 0) CurrentFrame.mvpMapPoints[i] = vpMPs[assigned[i]];
-    else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;
-  }
-  return nmatches;
+  return detail::searchByProjectionKeyFrameImpl(CurrentFrame, vpMPs, sAlreadyFound, occ, assigned, [&](auto classify) {
+    return detail::searchSourcesFrame<Ops>(ctx, cur, src, CurrentFrame, ORBFE_SRC_KEYFRAME, vpMPs, ns, classify, geometry, occ, th,
+                                           ORBdist, mbCheckOrientation, assigned);
+  });
 }
 
-// int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
-//                                    vector<MapPoint*>& vpMatched, int th)   (ORBmatcher.cc:285-398)
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
-inline int SearchByProjection(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
-                              std::vector<MapPointT*>& vpMatched, int th) {
+// ---- the four keyframe-side searches.  Their middles hand back bestIdx[ns]: the keypoint of the keyframe each source
+// selected, -1 for none -- and for every source that was not projected.
+namespace detail {
+template <class KeyFrameT>
+inline void keyFrameProjection(KeyFrameT* intr, KeyFrameT* to, const float R[9], const float t[3], const float* Ow,
+                               OrbfeKeyFrameProjection& P) {
+  std::memset(&P, 0, sizeof P);
+  std::memcpy(P.R, R, sizeof P.R);
+  std::memcpy(P.t, t, sizeof P.t);
+  if (Ow) std::memcpy(P.Ow, Ow, sizeof P.Ow);
+  P.fx = intr->fx; P.fy = intr->fy; P.cx = intr->cx; P.cy = intr->cy;
+  P.logScaleFactor = to->mfLogScaleFactor;
+}
+template <class KeyFrameT>
+inline bool fusedKeyFrameLevels(KeyFrameT* pKF, bool chi2) {
+  const size_t nl = pKF->mvScaleFactors.size();
+  return nl >= 1 && nl <= 32 && (!chi2 || pKF->mvInvLevelSigma2.size() == nl);
+}
+// the GPU middle of the keyframe-side searches: projection + windows + best match of the MapPoints pts into the resident
+// keyframe rf; returns bestIdx[pts.size()] (page-locked, valid until the next search through ctx), the matches in *nmatches
+template <class KeyFrameT, class PointsT, class Classify, class GeometryFn>
+inline const int32_t* searchSourcesKeyFrame(MatcherContext& ctx, orbfe_frame* rf, KeyFrameT* to, const OrbfeKeyFrameProjection& P,
+                                            const PointsT& pts, Classify classify, GeometryFn& geometry, float th,
+                                            const uint8_t* kp_skip, int claim, bool chi2, int max_dist, int* nmatches = nullptr) {
+  const int ns = (int)pts.size();
+  uint8_t* flags;
+  int32_t* rows;
+  sourceRows(ctx, pts, ns, classify, geometry, flags, rows);
+  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
+  int nm = 0, nValid = 0;
+  check(orbfe_search_projected_keyframe_frame(ctx.get(), rf, ctx.localMap(), &P, rows, flags, ns, to->mvScaleFactors.data(),
+                                              (int)to->mvScaleFactors.size(), th, kp_skip, claim,
+                                              chi2 ? to->mvInvLevelSigma2.data() : nullptr, 5.99, max_dist, nullptr, nullptr, nullptr,
+                                              bestIdx, nullptr, &nm, &nValid));
+  if (nmatches) *nmatches = nm;
+  return bestIdx;
+}
+
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th).  middle(classify, Rcw, tcw, Ow, nmatches) -> bestIdx
+template <class Ops, class MatT, class MapPointT, class Middle>
+inline int searchByProjectionScwImpl(const MatT& Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched,
+                                     Middle middle) {
   float Rcw[9], tcw[3], Ow[3];
-  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
+  decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
   std::vector<MapPointT*> found(vpMatched.begin(), vpMatched.end());     // spAlreadyFound (:301-302)
   std::sort(found.begin(), found.end());
-  const size_t ns = vpPoints.size();
-  detail::ProjectedSources S(ns);
-  for (size_t i = 0; i < ns; i++) {
+  auto classify = [&](int i) -> uint8_t {
     MapPointT* pMP = vpPoints[i];
-    if (pMP->isBad() || std::binary_search(found.begin(), found.end(), pMP)) continue;
-    detail::projectIntoKeyFrame<Ops>(pKF, pMP, Rcw, tcw, Ow, (float)th, /*invz = 1/z in float*/ false, S, i);
-  }
-  std::vector<uint8_t> skip(vpMatched.size() ? vpMatched.size() : 1, 0);
-  for (size_t i = 0; i < vpMatched.size(); i++) skip[i] = vpMatched[i] ? 1 : 0;   // :366-367
-  const int nmatches = detail::searchProjected(ctx, pKF, S, skip.data(), /*claim*/ 1, /*chi2*/ false, /*TH_LOW*/ 50);
-  for (size_t i = 0; i < ns; i++)
-    if (S.bestIdx[i] >= 0) vpMatched[S.bestIdx[i]] = vpPoints[i];
+    if (pMP->isBad()) return ORBFE_MP_BAD;                                // :312-313
+    return std::binary_search(found.begin(), found.end(), pMP) ? (uint8_t)ORBFE_MP_SKIP : (uint8_t)0;
+  };
+  int nmatches = 0;
+  const int32_t* bestIdx = middle(classify, Rcw, tcw, Ow, nmatches);
+  for (size_t i = 0; i < vpPoints.size(); i++)
+    if (bestIdx[i] >= 0) vpMatched[bestIdx[i]] = vpPoints[i];
   return nmatches;
 }
 
-// int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th)   (ORBmatcher.cc:806-939).
-// Which keypoint a MapPoint selects depends only on the keyframe's keypoints and the point itself, so all windows are
-// searched in one GPU call; the reference's loop is then replayed IN ORDER with its live checks (isBad / IsInKeyFrame
-// change as earlier points are replaced or added).  vpMapPoints holds distinct points, as the reference's callers
-// guarantee (LocalMapping::SearchInNeighbors marks candidates with mnFuseCandidateForKF).
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MapPointT>
-inline int Fuse(MatcherContext& ctx, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th) {
+// Fuse(pKF, vpMapPoints, th).  middle(Rcw, tcw, Ow) -> bestIdx.  Which keypoint a MapPoint selects depends only on the
+// keyframe's keypoints and the point itself, so all windows are searched in one GPU call; the reference's loop is then
+// replayed IN ORDER with its live checks (isBad / IsInKeyFrame change as earlier points are replaced or added).  vpMapPoints
+// holds distinct points, as the reference's callers guarantee (LocalMapping::SearchInNeighbors marks candidates with
+// mnFuseCandidateForKF).  There is no classify here: the host middle projects every non-null point and leaves isBad /
+// IsInKeyFrame to the replay, the GPU middle takes them at entry as well (see FuseKeyFrame).
+template <class KeyFrameT, class MapPointT, class Middle>
+inline int fuseImpl(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, Middle middle) {
   float Rcw[9], tcw[3], Ow[3];
-  detail::mat33(pKF->GetRotation(), Rcw);
-  detail::vec3(pKF->GetTranslation(), tcw);
-  detail::vec3(pKF->GetCameraCenter(), Ow);
-  const size_t ns = vpMapPoints.size();
-  detail::ProjectedSources S(ns);
-  for (size_t i = 0; i < ns; i++)
-    if (vpMapPoints[i]) detail::projectIntoKeyFrame<Ops>(pKF, vpMapPoints[i], Rcw, tcw, Ow, th, false, S, i);
-  detail::searchProjected(ctx, pKF, S, nullptr, 0, /*chi2 gate :896-903*/ true, /*TH_LOW*/ 50);
+  mat33(pKF->GetRotation(), Rcw);
+  vec3(pKF->GetTranslation(), tcw);
+  vec3(pKF->GetCameraCenter(), Ow);
+  const int32_t* bestIdx = middle(Rcw, tcw, Ow);
   int nFused = 0;
-  for (size_t i = 0; i < ns; i++) {
+  for (size_t i = 0; i < vpMapPoints.size(); i++) {
     MapPointT* pMP = vpMapPoints[i];
     if (!pMP) continue;
     if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
-    if (!S.valid[i] || S.bestIdx[i] < 0) continue;
-    const int bestIdx = S.bestIdx[i];
-    MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);
+    if (bestIdx[i] < 0) continue;   // no keypoint selected, or not projected (a source that is not valid keeps bestIdx == -1)
+    const int best = bestIdx[i];
+    MapPointT* pMPinKF = pKF->GetMapPoint(best);
     if (pMPinKF) {
       if (!pMPinKF->isBad()) {
         if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
         else pMPinKF->Replace(pMP);
       }
     } else {
-      pMP->AddObservation(pKF, bestIdx);
-      pKF->AddMapPoint(pMP, bestIdx);
+      pMP->AddObservation(pKF, best);
+      pKF->AddMapPoint(pMP, best);
     }
     nFused++;
   }
   return nFused;
 }
 
-// int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th,
-//                      vector<MapPoint*>& vpReplacePoint)   (ORBmatcher.cc:941-1064)
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
-inline int Fuse(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints, float th,
-                std::vector<MapPointT*>& vpReplacePoint) {
+// Fuse(pKF, Scw, vpPoints, th, vpReplacePoint).  middle(classify, Rcw, tcw, Ow) -> bestIdx
+template <class Ops, class KeyFrameT, class MatT, class MapPointT, class Middle>
+inline int fuseScwImpl(KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
+                       std::vector<MapPointT*>& vpReplacePoint, Middle middle) {
   float Rcw[9], tcw[3], Ow[3];
-  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
+  decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
   const auto spAlreadyFound = pKF->GetMapPoints();
-  const size_t ns = vpPoints.size();
-  detail::ProjectedSources S(ns);
-  for (size_t i = 0; i < ns; i++) {
+  auto classify = [&](int i) -> uint8_t {
     MapPointT* pMP = vpPoints[i];
-    if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
-    detail::projectIntoKeyFrame<Ops>(pKF, pMP, Rcw, tcw, Ow, th, /*invz = 1.0/z*/ true, S, i);
-  }
-  detail::searchProjected(ctx, pKF, S, nullptr, 0, false, /*TH_LOW*/ 50);
+    if (pMP->isBad()) return ORBFE_MP_BAD;                                // :968-969
+    return spAlreadyFound.count(pMP) ? (uint8_t)ORBFE_MP_SKIP : (uint8_t)0;
+  };
+  const int32_t* bestIdx = middle(classify, Rcw, tcw, Ow);
   int nFused = 0;
-  for (size_t i = 0; i < ns; i++) {
-    if (!S.valid[i] || S.bestIdx[i] < 0) continue;
+  for (size_t i = 0; i < vpPoints.size(); i++) {
+    if (bestIdx[i] < 0) continue;   // (as in fuseImpl)
     MapPointT* pMP = vpPoints[i];
-    const int bestIdx = S.bestIdx[i];
-    MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);     // live: an earlier point of this call may have been added here
+    const int best = bestIdx[i];
+    MapPointT* pMPinKF = pKF->GetMapPoint(best);     // live: an earlier point of this call may have been added here
     if (pMPinKF) {
       if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
     } else {
-      pMP->AddObservation(pKF, bestIdx);
-      pKF->AddMapPoint(pMP, bestIdx);
+      pMP->AddObservation(pKF, best);
+      pKF->AddMapPoint(pMP, best);
     }
     nFused++;
   }
   return nFused;
 }
 
-// int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12,
-//                              const cv::Mat& R12, const cv::Mat& t12, const float th)   (ORBmatcher.cc:1066-1290)
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
-inline int SearchBySim3(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12,
-                        const float& s12, const MatT& R12m, const MatT& t12m, const float th) {
-  const float fx = pKF1->fx, fy = pKF1->fy, cx = pKF1->cx, cy = pKF1->cy;
+// SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th).  One direction: the points `pts` of the keyframe with pose
+// (Rfw, tfw) through (sR, tt) into `to`; middle(classify, pts, Rfw, tfw, sR, tt, to, vnMatch) fills vnMatch[pts.size()].
+template <class Ops, class KeyFrameT, class MatT, class MapPointT, class Middle>
+inline int searchBySim3Impl(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, const float& s12,
+                            const MatT& R12m, const MatT& t12m, Middle middle) {
   float R1w[9], t1w[3], R2w[9], t2w[3], R12[9], t12[3], sR12[9], sR21[9], R12t[9], t21[3];
-  detail::mat33(pKF1->GetRotation(), R1w); detail::vec3(pKF1->GetTranslation(), t1w);
-  detail::mat33(pKF2->GetRotation(), R2w); detail::vec3(pKF2->GetTranslation(), t2w);
-  detail::mat33(R12m, R12); detail::vec3(t12m, t12);
+  mat33(pKF1->GetRotation(), R1w); vec3(pKF1->GetTranslation(), t1w);
+  mat33(pKF2->GetRotation(), R2w); vec3(pKF2->GetTranslation(), t2w);
+  mat33(R12m, R12); vec3(t12m, t12);
   Ops::scale(R12, 9, (double)s12, sR12);                                  // s12*R12
   for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R12t[3 * r + c] = R12[3 * c + r];
   Ops::scale(R12t, 9, 1.0 / (double)s12, sR21);                           // (1.0/s12)*R12.t()
@@ -1323,14 +1376,137 @@ inline int SearchBySim3(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, s
       if (idx2 >= 0 && idx2 < N2) vbAlreadyMatched2[idx2] = true;
     }
   }
-  // one direction: points of `from` (camera pose Rfw, tfw) through (sR, t) into `to`
   auto direction = [&](const std::vector<MapPointT*>& pts, const std::vector<bool>& already, const float* Rfw, const float* tfw,
                        const float* sR, const float* tt, KeyFrameT* to, std::vector<int>& vnMatch) {
+    auto classify = [&](int i) -> uint8_t {
+      MapPointT* pMP = pts[i];
+      if (!pMP || already[i]) return ORBFE_MP_SKIP;
+      return pMP->isBad() ? (uint8_t)ORBFE_MP_BAD : (uint8_t)0;
+    };
+    middle(classify, pts, Rfw, tfw, sR, tt, to, vnMatch);
+  };
+  std::vector<int> vnMatch1, vnMatch2;
+  direction(vpMapPoints1, vbAlreadyMatched1, R1w, t1w, sR21, t21, pKF2, vnMatch1);
+  direction(vpMapPoints2, vbAlreadyMatched2, R2w, t2w, sR12, t12, pKF1, vnMatch2);
+  int nFound = 0;
+  for (int i1 = 0; i1 < N1; i1++) {
+    const int idx2 = vnMatch1[i1];
+    if (idx2 >= 0) {
+      const int idx1 = vnMatch2[idx2];
+      if (idx1 == i1) { vpMatches12[i1] = vpMapPoints2[idx2]; nFound++; }
+    }
+  }
+  return nFound;
+}
+}  // namespace detail
+
+// int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+//                                    vector<MapPoint*>& vpMatched, int th)   (ORBmatcher.cc:285-398)
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
+inline int SearchByProjection(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
+                              std::vector<MapPointT*>& vpMatched, int th) {
+  detail::ProjectedSources S(vpPoints.size());
+  std::vector<uint8_t> skip(vpMatched.size() ? vpMatched.size() : 1, 0);
+  return detail::searchByProjectionScwImpl<Ops>(Scw, vpPoints, vpMatched, [&](auto classify, const float* Rcw, const float* tcw,
+                                                                              const float* Ow, int& nmatches) {
+    for (size_t i = 0; i < vpPoints.size(); i++)
+      if (!classify((int)i)) detail::projectIntoKeyFrame<Ops>(pKF, vpPoints[i], Rcw, tcw, Ow, (float)th, /*invz = 1/z in float*/ false, S, i);
+    for (size_t i = 0; i < vpMatched.size(); i++) skip[i] = vpMatched[i] ? 1 : 0;   // :366-367
+    nmatches = detail::searchProjected(ctx, pKF, S, skip.data(), /*claim*/ 1, /*chi2*/ false, /*TH_LOW*/ 50);
+    return S.bestIdx.data();
+  });
+}
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
+inline int SearchByProjectionScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
+                                 std::vector<MapPointT*>& vpMatched, int th, GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return SearchByProjection<Ops>(ctx, pKF, Scw, vpPoints, vpMatched, th);
+  return detail::searchByProjectionScwImpl<Ops>(Scw, vpPoints, vpMatched, [&](auto classify, const float* Rcw, const float* tcw,
+                                                                              const float* Ow, int& nmatches) {
+    uint8_t* skip = ctx.scratch<uint8_t>(0, vpMatched.size(), true);
+    for (size_t i = 0; i < vpMatched.size(); i++) skip[i] = vpMatched[i] ? 1 : 0;   // :366-367
+    OrbfeKeyFrameProjection P;
+    detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+    P.invz_in_double = 0; P.check_viewing_angle = 1;
+    return detail::searchSourcesKeyFrame(ctx, rf, pKF, P, vpPoints, classify, geometry, (float)th, skip, /*claim*/ 1, false, /*TH_LOW*/ 50,
+                                         &nmatches);
+  });
+}
+
+// int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th)   (ORBmatcher.cc:806-939)
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MapPointT>
+inline int Fuse(MatcherContext& ctx, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th) {
+  detail::ProjectedSources S(vpMapPoints.size());
+  return detail::fuseImpl(pKF, vpMapPoints, [&](const float* Rcw, const float* tcw, const float* Ow) {
+    for (size_t i = 0; i < vpMapPoints.size(); i++)
+      if (vpMapPoints[i]) detail::projectIntoKeyFrame<Ops>(pKF, vpMapPoints[i], Rcw, tcw, Ow, th, false, S, i);
+    detail::searchProjected(ctx, pKF, S, nullptr, 0, /*chi2 gate :896-903*/ true, /*TH_LOW*/ 50);
+    return S.bestIdx.data();
+  });
+}
+// The GPU middle's flags are taken at entry, which is exact: a point that is bad stays bad, and a point that sits in the
+// keyframe at entry can only leave it by being Replace()d, which makes it bad -- the reference's live check (:822-823) skips it
+// either way.  The replay keeps the live checks for points that change DURING the call.
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MapPointT, class GeometryFn>
+inline int FuseKeyFrame(MatcherContext& ctx, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th,
+                        GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, true) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return Fuse<Ops>(ctx, pKF, vpMapPoints, th);
+  return detail::fuseImpl(pKF, vpMapPoints, [&](const float* Rcw, const float* tcw, const float* Ow) {
+    auto classify = [&](int i) -> uint8_t {
+      MapPointT* pMP = vpMapPoints[i];
+      if (!pMP) return ORBFE_MP_SKIP;
+      if (pMP->isBad()) return ORBFE_MP_BAD;
+      return pMP->IsInKeyFrame(pKF) ? (uint8_t)ORBFE_MP_SKIP : (uint8_t)0;
+    };
+    OrbfeKeyFrameProjection P;
+    detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+    P.invz_in_double = 0; P.check_viewing_angle = 1;
+    return detail::searchSourcesKeyFrame(ctx, rf, pKF, P, vpMapPoints, classify, geometry, th, nullptr, 0, /*chi2 gate :896-903*/ true,
+                                         /*TH_LOW*/ 50);
+  });
+}
+
+// int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th,
+//                      vector<MapPoint*>& vpReplacePoint)   (ORBmatcher.cc:941-1064)
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
+inline int Fuse(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints, float th,
+                std::vector<MapPointT*>& vpReplacePoint) {
+  detail::ProjectedSources S(vpPoints.size());
+  return detail::fuseScwImpl<Ops>(pKF, Scw, vpPoints, vpReplacePoint, [&](auto classify, const float* Rcw, const float* tcw, const float* Ow) {
+    for (size_t i = 0; i < vpPoints.size(); i++)
+      if (!classify((int)i)) detail::projectIntoKeyFrame<Ops>(pKF, vpPoints[i], Rcw, tcw, Ow, th, /*invz = 1.0/z*/ true, S, i);
+    detail::searchProjected(ctx, pKF, S, nullptr, 0, false, /*TH_LOW*/ 50);
+    return S.bestIdx.data();
+  });
+}
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
+inline int FuseScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints, float th,
+                   std::vector<MapPointT*>& vpReplacePoint, GeometryFn geometry) {
+  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
+  if (!rf) return Fuse<Ops>(ctx, pKF, Scw, vpPoints, th, vpReplacePoint);
+  return detail::fuseScwImpl<Ops>(pKF, Scw, vpPoints, vpReplacePoint, [&](auto classify, const float* Rcw, const float* tcw, const float* Ow) {
+    OrbfeKeyFrameProjection P;
+    detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
+    P.invz_in_double = 1; P.check_viewing_angle = 1;
+    return detail::searchSourcesKeyFrame(ctx, rf, pKF, P, vpPoints, classify, geometry, th, nullptr, 0, false, /*TH_LOW*/ 50);
+  });
+}
+
+// int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12,
+//                              const cv::Mat& R12, const cv::Mat& t12, const float th)   (ORBmatcher.cc:1066-1290):
+// one search per direction, then the vnMatch agreement on the host.
+template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT>
+inline int SearchBySim3(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12,
+                        const float& s12, const MatT& R12m, const MatT& t12m, const float th) {
+  const float fx = pKF1->fx, fy = pKF1->fy, cx = pKF1->cx, cy = pKF1->cy;
+  return detail::searchBySim3Impl<Ops>(pKF1, pKF2, vpMatches12, s12, R12m, t12m, [&](auto classify, const std::vector<MapPointT*>& pts,
+                                                                                     const float* Rfw, const float* tfw, const float* sR,
+                                                                                     const float* tt, KeyFrameT* to, std::vector<int>& vnMatch) {
     detail::ProjectedSources S(pts.size());
     for (size_t i = 0; i < pts.size(); i++) {
+      if (classify((int)i)) continue;
       MapPointT* pMP = pts[i];
-      if (!pMP || already[i]) continue;
-      if (pMP->isBad()) continue;
       float p3Dw[3], pa[3], pb[3];
       detail::vec3(pMP->GetWorldPos(), p3Dw);
       Ops::gemm3(Rfw, p3Dw, 1.0, tfw, 1.0, pa);
@@ -1353,194 +1529,8 @@ inline int SearchBySim3(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, s
     }
     detail::searchProjected(ctx, to, S, nullptr, 0, false, /*TH_HIGH*/ 100);
     vnMatch.assign(S.bestIdx.begin(), S.bestIdx.end());
-  };
-  std::vector<int> vnMatch1, vnMatch2;
-  direction(vpMapPoints1, vbAlreadyMatched1, R1w, t1w, sR21, t21, pKF2, vnMatch1);
-  direction(vpMapPoints2, vbAlreadyMatched2, R2w, t2w, sR12, t12, pKF1, vnMatch2);
-  int nFound = 0;
-  for (int i1 = 0; i1 < N1; i1++) {
-    const int idx2 = vnMatch1[i1];
-    if (idx2 >= 0) {
-      const int idx1 = vnMatch2[idx2];
-      if (idx1 == i1) { vpMatches12[i1] = vpMapPoints2[idx2]; nFound++; }
-    }
-  }
-  return nFound;
+  });
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// The four keyframe-side searches above with their projection loops on the GPU (orbfe_search_projected_keyframe_frame): the
-// MapPoints' positions, normals, depth ranges and descriptors are rows of the context's local-map table -- the rows
-// SearchLocalPoints and the two frame-side forms use, so a MapPoint known to any of them keeps ONE row, and only rows whose
-// content changed are sent.  Per call and MapPoint one row number and one flag byte cross PCIe.  The matrices are computed
-// once per call with Ops, as in the functions above; `geometry` is SearchLocalPoints' functor.  The bookkeeping that follows
-// the search is the functions' own, unchanged.  With the frame cache off (ctx.resident returns null) they ARE the functions
-// above.  The fused call refuses a valid point whose predicted level lies outside the keyframe's pyramid (the reference
-// would index mvScaleFactors out of range with it).
-// ---------------------------------------------------------------------------------------------------------------
-namespace detail {
-template <class KeyFrameT>
-inline void keyFrameProjection(KeyFrameT* intr, KeyFrameT* to, const float R[9], const float t[3], const float* Ow,
-                               OrbfeKeyFrameProjection& P) {
-  std::memset(&P, 0, sizeof P);
-  std::memcpy(P.R, R, sizeof P.R);
-  std::memcpy(P.t, t, sizeof P.t);
-  if (Ow) std::memcpy(P.Ow, Ow, sizeof P.Ow);
-  P.fx = intr->fx; P.fy = intr->fy; P.cx = intr->cx; P.cy = intr->cy;
-  P.logScaleFactor = to->mfLogScaleFactor;
-}
-template <class KeyFrameT>
-inline bool fusedKeyFrameLevels(KeyFrameT* pKF, bool chi2) {
-  const size_t nl = pKF->mvScaleFactors.size();
-  return nl >= 1 && nl <= 32 && (!chi2 || pKF->mvInvLevelSigma2.size() == nl);
-}
-// projection + windows + best match of ns MapPoints (rows / flags) into the resident keyframe rf; bestIdx[ns]
-template <class KeyFrameT>
-inline int searchProjectedKeyFrame(MatcherContext& ctx, orbfe_frame* rf, KeyFrameT* to, const OrbfeKeyFrameProjection& P,
-                                   const int32_t* rows, const uint8_t* flags, int ns, float th, const uint8_t* kp_skip, int claim,
-                                   bool chi2, int max_dist, int32_t* bestIdx) {
-  int nm = 0, nValid = 0;
-  check(orbfe_search_projected_keyframe_frame(ctx.get(), rf, ctx.localMap(), &P, rows, flags, ns, to->mvScaleFactors.data(),
-                                              (int)to->mvScaleFactors.size(), th, kp_skip, claim,
-                                              chi2 ? to->mvInvLevelSigma2.data() : nullptr, 5.99, max_dist, nullptr, nullptr, nullptr,
-                                              bestIdx, nullptr, &nm, &nValid));
-  return nm;
-}
-}  // namespace detail
-
-// int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
-//                                    vector<MapPoint*>& vpMatched, int th)   (ORBmatcher.cc:285-398)
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
-inline int SearchByProjectionScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints,
-                                 std::vector<MapPointT*>& vpMatched, int th, GeometryFn geometry) {
-  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
-  if (!rf) return SearchByProjection<Ops>(ctx, pKF, Scw, vpPoints, vpMatched, th);
-  float Rcw[9], tcw[3], Ow[3];
-  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
-  std::vector<MapPointT*> found(vpMatched.begin(), vpMatched.end());     // spAlreadyFound (:301-302)
-  std::sort(found.begin(), found.end());
-  const int ns = (int)vpPoints.size();
-  uint8_t* skip = ctx.scratch<uint8_t>(0, vpMatched.size(), true);
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
-  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
-  ctx.localMapBegin((size_t)ns);
-  for (int i = 0; i < ns; i++) {
-    MapPointT* pMP = vpPoints[i];
-    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                                        // :312-313
-    if (std::binary_search(found.begin(), found.end(), pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
-    rows[i] = detail::sourceRow(ctx, pMP, geometry);
-  }
-  ctx.localMapCommit();
-  for (size_t i = 0; i < vpMatched.size(); i++) skip[i] = vpMatched[i] ? 1 : 0;                     // :366-367
-  OrbfeKeyFrameProjection P;
-  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
-  P.invz_in_double = 0; P.check_viewing_angle = 1;
-  const int nmatches = detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, (float)th, skip, /*claim*/ 1, false,
-                                                       /*TH_LOW*/ 50, bestIdx);
-  for (int i = 0; i < ns; i++)
-    if (bestIdx[i] >= 0) vpMatched[bestIdx[i]] = vpPoints[i];
-  return nmatches;
-}
-
-// int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th)   (ORBmatcher.cc:806-939).
-// The flags are taken at entry, which is exact: a point that is bad stays bad, and a point that sits in the keyframe at entry
-// can only leave it by being Replace()d, which makes it bad -- the reference's live check (:822-823) skips it either way.
-// The replay keeps the live checks for points that change DURING the call.
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MapPointT, class GeometryFn>
-inline int FuseKeyFrame(MatcherContext& ctx, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th,
-                        GeometryFn geometry) {
-  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, true) ? ctx.resident(*pKF, 1) : nullptr;
-  if (!rf) return Fuse<Ops>(ctx, pKF, vpMapPoints, th);
-  float Rcw[9], tcw[3], Ow[3];
-  detail::mat33(pKF->GetRotation(), Rcw);
-  detail::vec3(pKF->GetTranslation(), tcw);
-  detail::vec3(pKF->GetCameraCenter(), Ow);
-  const int ns = (int)vpMapPoints.size();
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
-  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
-  ctx.localMapBegin((size_t)ns);
-  for (int i = 0; i < ns; i++) {
-    MapPointT* pMP = vpMapPoints[i];
-    if (!pMP) { flags[i] = ORBFE_MP_SKIP; continue; }
-    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }
-    if (pMP->IsInKeyFrame(pKF)) { flags[i] = ORBFE_MP_SKIP; continue; }
-    rows[i] = detail::sourceRow(ctx, pMP, geometry);
-  }
-  ctx.localMapCommit();
-  OrbfeKeyFrameProjection P;
-  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
-  P.invz_in_double = 0; P.check_viewing_angle = 1;
-  detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, th, nullptr, 0, /*chi2 gate :896-903*/ true, /*TH_LOW*/ 50, bestIdx);
-  int nFused = 0;
-  for (int i = 0; i < ns; i++) {
-    MapPointT* pMP = vpMapPoints[i];
-    if (!pMP) continue;
-    if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
-    if (bestIdx[i] < 0) continue;
-    const int best = bestIdx[i];
-    MapPointT* pMPinKF = pKF->GetMapPoint(best);
-    if (pMPinKF) {
-      if (!pMPinKF->isBad()) {
-        if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
-        else pMPinKF->Replace(pMP);
-      }
-    } else {
-      pMP->AddObservation(pKF, best);
-      pKF->AddMapPoint(pMP, best);
-    }
-    nFused++;
-  }
-  return nFused;
-}
-
-// int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th,
-//                      vector<MapPoint*>& vpReplacePoint)   (ORBmatcher.cc:941-1064)
-template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
-inline int FuseScw(MatcherContext& ctx, KeyFrameT* pKF, const MatT& Scw, const std::vector<MapPointT*>& vpPoints, float th,
-                   std::vector<MapPointT*>& vpReplacePoint, GeometryFn geometry) {
-  orbfe_frame* rf = detail::fusedKeyFrameLevels(pKF, false) ? ctx.resident(*pKF, 1) : nullptr;
-  if (!rf) return Fuse<Ops>(ctx, pKF, Scw, vpPoints, th, vpReplacePoint);
-  float Rcw[9], tcw[3], Ow[3];
-  detail::decomposeScw<Ops>(Scw, Rcw, tcw, Ow);
-  const auto spAlreadyFound = pKF->GetMapPoints();
-  const int ns = (int)vpPoints.size();
-  uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-  int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
-  int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
-  ctx.localMapBegin((size_t)ns);
-  for (int i = 0; i < ns; i++) {
-    MapPointT* pMP = vpPoints[i];
-    if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }                        // :968-969
-    if (spAlreadyFound.count(pMP)) { flags[i] = ORBFE_MP_SKIP; continue; }
-    rows[i] = detail::sourceRow(ctx, pMP, geometry);
-  }
-  ctx.localMapCommit();
-  OrbfeKeyFrameProjection P;
-  detail::keyFrameProjection(pKF, pKF, Rcw, tcw, Ow, P);
-  P.invz_in_double = 1; P.check_viewing_angle = 1;
-  detail::searchProjectedKeyFrame(ctx, rf, pKF, P, rows, flags, ns, th, nullptr, 0, false, /*TH_LOW*/ 50, bestIdx);
-  int nFused = 0;
-  for (int i = 0; i < ns; i++) {
-    if (bestIdx[i] < 0) continue;
-    MapPointT* pMP = vpPoints[i];
-    const int best = bestIdx[i];
-    MapPointT* pMPinKF = pKF->GetMapPoint(best);     // live: an earlier point of this call may have been added here
-    if (pMPinKF) {
-      if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
-    } else {
-      pMP->AddObservation(pKF, best);
-      pKF->AddMapPoint(pMP, best);
-    }
-    nFused++;
-  }
-  return nFused;
-}
-
-// int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12,
-//                              const cv::Mat& R12, const cv::Mat& t12, const float th)   (ORBmatcher.cc:1066-1290):
-// two fused calls, one per direction, then the vnMatch agreement on the host.
 template <class Ops = detail::RestatedOps, class KeyFrameT, class MatT, class MapPointT, class GeometryFn>
 inline int SearchBySim3Device(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12,
                               const float& s12, const MatT& R12m, const MatT& t12m, const float th, GeometryFn geometry) {
@@ -1548,61 +1538,19 @@ inline int SearchBySim3Device(MatcherContext& ctx, KeyFrameT* pKF1, KeyFrameT* p
   orbfe_frame* rf2 = levels ? ctx.resident(*pKF2, 1) : nullptr;
   orbfe_frame* rf1 = rf2 ? ctx.resident(*pKF1, 1) : nullptr;   // (never evicts rf2: the two most recent frames stay)
   if (!rf1 || !rf2) return SearchBySim3<Ops>(ctx, pKF1, pKF2, vpMatches12, s12, R12m, t12m, th);
-  float R1w[9], t1w[3], R2w[9], t2w[3], R12[9], t12[3], sR12[9], sR21[9], R12t[9], t21[3];
-  detail::mat33(pKF1->GetRotation(), R1w); detail::vec3(pKF1->GetTranslation(), t1w);
-  detail::mat33(pKF2->GetRotation(), R2w); detail::vec3(pKF2->GetTranslation(), t2w);
-  detail::mat33(R12m, R12); detail::vec3(t12m, t12);
-  Ops::scale(R12, 9, (double)s12, sR12);                                  // s12*R12
-  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R12t[3 * r + c] = R12[3 * c + r];
-  Ops::scale(R12t, 9, 1.0 / (double)s12, sR21);                           // (1.0/s12)*R12.t()
-  Ops::gemm3(sR21, t12, -1.0, nullptr, 0.0, t21);                         // -sR21*t12
-  const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
-  const int N1 = (int)vpMapPoints1.size(), N2 = (int)vpMapPoints2.size();
-  std::vector<bool> vbAlreadyMatched1(N1, false), vbAlreadyMatched2(N2, false);
-  for (int i = 0; i < N1; i++) {
-    MapPointT* pMP = vpMatches12[i];
-    if (pMP) {
-      vbAlreadyMatched1[i] = true;
-      const int idx2 = pMP->GetIndexInKeyFrame(pKF2);
-      if (idx2 >= 0 && idx2 < N2) vbAlreadyMatched2[idx2] = true;
-    }
-  }
-  // one direction: points of `from` (camera pose Rfw, tfw) through (sR, t) into `to`, pKF1's intrinsics in both (:1069-1072)
-  auto direction = [&](const std::vector<MapPointT*>& pts, const std::vector<bool>& already, const float* Rfw, const float* tfw,
-                       const float* sR, const float* tt, KeyFrameT* to, orbfe_frame* rf, std::vector<int>& vnMatch) {
-    const int ns = (int)pts.size();
-    uint8_t* flags = ctx.scratch<uint8_t>(1, ns, true);
-    int32_t* rows = ctx.scratch<int32_t>(2, ns, true);
-    int32_t* bestIdx = ctx.scratch<int32_t>(5, ns, false);
-    ctx.localMapBegin((size_t)ns);
-    for (int i = 0; i < ns; i++) {
-      MapPointT* pMP = pts[i];
-      if (!pMP || already[i]) { flags[i] = ORBFE_MP_SKIP; continue; }
-      if (pMP->isBad()) { flags[i] = ORBFE_MP_BAD; continue; }
-      rows[i] = detail::sourceRow(ctx, pMP, geometry);
-    }
-    ctx.localMapCommit();
+  return detail::searchBySim3Impl<Ops>(pKF1, pKF2, vpMatches12, s12, R12m, t12m, [&](auto classify, const std::vector<MapPointT*>& pts,
+                                                                                     const float* Rfw, const float* tfw, const float* sR,
+                                                                                     const float* tt, KeyFrameT* to, std::vector<int>& vnMatch) {
     OrbfeKeyFrameProjection P;
-    detail::keyFrameProjection(pKF1, to, Rfw, tfw, nullptr, P);
+    detail::keyFrameProjection(pKF1, to, Rfw, tfw, nullptr, P);           // pKF1's intrinsics in both directions (:1069-1072)
     P.has_second = 1;
     std::memcpy(P.sR, sR, sizeof P.sR);
     std::memcpy(P.t2, tt, sizeof P.t2);
     P.invz_in_double = 1; P.check_viewing_angle = 0; P.distance_from_camera_point = 1;
-    detail::searchProjectedKeyFrame(ctx, rf, to, P, rows, flags, ns, th, nullptr, 0, false, /*TH_HIGH*/ 100, bestIdx);
-    vnMatch.assign(bestIdx, bestIdx + ns);
-  };
-  std::vector<int> vnMatch1, vnMatch2;
-  direction(vpMapPoints1, vbAlreadyMatched1, R1w, t1w, sR21, t21, pKF2, rf2, vnMatch1);
-  direction(vpMapPoints2, vbAlreadyMatched2, R2w, t2w, sR12, t12, pKF1, rf1, vnMatch2);
-  int nFound = 0;
-  for (int i1 = 0; i1 < N1; i1++) {
-    const int idx2 = vnMatch1[i1];
-    if (idx2 >= 0) {
-      const int idx1 = vnMatch2[idx2];
-      if (idx1 == i1) { vpMatches12[i1] = vpMapPoints2[idx2]; nFound++; }
-    }
-  }
-  return nFound;
+    const int32_t* bestIdx = detail::searchSourcesKeyFrame(ctx, to == pKF1 ? rf1 : rf2, to, P, pts, classify, geometry, th, nullptr, 0,
+                                                           false, /*TH_HIGH*/ 100);
+    vnMatch.assign(bestIdx, bestIdx + pts.size());
+  });
 }
 
 // void Frame::UndistortKeyPoints()   (Frame.cc:286-320) and void Frame::ComputeImageBounds(const cv::Mat& imLeft)

@@ -8,7 +8,8 @@
 //   Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)           ORBmatcher.cc:941-1064
 //   SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)     ORBmatcher.cc:1066-1290
 // Each scene is searched twice, by the existing host-projection template on one copy of the model and by the new template
-// on another; both must equal the oracle.  Prints one line per function, a statistics line, and PASS / FAIL; exit code 0 iff
+// on another; both must equal the oracle.  Then all four run once more with the frame cache off, where the new templates are
+// the existing ones: same counts, same oracle comparison.  Prints one line per function, a statistics line, and PASS / FAIL; exit code 0 iff
 // every comparison is exact.
 //   build: g++ -std=c++17 -O1 -ffp-contract=off -Iinclude -Ioracle tests/cpp/keyframe_projection_test.cpp os1_amd/liborbfe.so
 //          oracle/liborb_oracle.so
@@ -178,15 +179,21 @@ int main(int argc, char** argv) {
   for (int which = 0; which < 3; which++)
     if (oneKeyFrame(ctx, seed + 1, which, ths[which], true) < 0) failures++;
   const float scales[2] = {1.0f, 1.1f};
+  int sim3Found[2] = {0, 0};
   for (int k = 0; k < 2; k++) {
     const int a = sim3(ctx, seed, scales[k], 7.5f, false);
     const int b = sim3(ctx, seed, scales[k], 7.5f, true);
     if (a != b || b < 0) failures++;
+    sim3Found[k] = b;
     total[3] += b;
   }
-  // with the frame cache off the new templates are the existing functions
+  // with the frame cache off the new templates are the existing functions: the same counts, and the oracle comparisons
+  // inside oneKeyFrame / sim3 hold again
   ctx.setFrameCacheCapacity(0);
-  if (oneKeyFrame(ctx, seed, 1, 3.0f, true) != total[1]) failures++;
+  for (int which = 0; which < 3; which++)
+    if (oneKeyFrame(ctx, seed, which, ths[which], true) != total[which]) failures++;
+  for (int k = 0; k < 2; k++)
+    if (sim3(ctx, seed, scales[k], 7.5f, true) != sim3Found[k]) failures++;
   printf("sbp_scw %d fuse %d fuse_scw %d sim3 %d rows_sent %d\n", total[0], total[1], total[2], total[3], (int)rowsOnce);
   printf("%s\n", failures ? "FAIL" : "PASS");
   return failures ? 1 : 0;

@@ -5,7 +5,8 @@
 //   per frame      Frame::Frame: ExtractORB -> the frame's resident copy (from the extractor's arena)
 //   frame 0        the initial map: a MapPoint for about half of the keypoints
 //   frames >= 1    Tracking::TrackWithMotionModel: SearchByProjection(Cur, Last, 15); on frame 2 the 2*th call follows on the
-//                  same frame (Tracking.cc:596-614) and must send no row
+//                  same frame (Tracking.cc:596-614) and must send no row; on frame 1 both searches run a second time through a
+//                  context whose frame cache is off (their host-projection form) and must equal the oracle as well
 //                  Tracking::Relocalization's SearchByProjection(Cur, pKF, sAlreadyFound, 10, 100) against frame 0 as KeyFrame
 //                  (Tracking.cc:1456) on a copy of the frame's matches
 //                  Tracking::SearchLocalPoints through the same context: its MapPoints share the rows
@@ -137,6 +138,8 @@ int main(int argc, char** argv) {
   const int device = orbfe::detail::defaultDevice();
   orbfe::Extractor extractor(nfeat, 1.2f, 8, 20, 7, device);
   orbfe::MatcherContext ctx(device);
+  orbfe::MatcherContext ctxOff(device);   // frame cache off: the two searches take their host-projection form (checked at frame 1)
+  ctxOff.setFrameCacheCapacity(0);
   const std::vector<float> sf = extractor.GetScaleFactors();
   const float logSf = std::log(1.2f);
   Frame::mnMinX = 0; Frame::mnMaxX = (float)W; Frame::mnMinY = 0; Frame::mnMaxY = (float)H;
@@ -269,6 +272,15 @@ int main(int argc, char** argv) {
       for (int i = 0; i < cur.N && same; i++) same = (cur.mvpMapPoints[i] ? cur.mvpMapPoints[i]->id : -1) == curIds[i];
       expect(same, attempt ? "SearchByProjectionLastFrame(Cur, Last, 2*th)" : "SearchByProjectionLastFrame(Cur, Last, th)", k, got, want);
       if (attempt) expect(ctx.localMapRowsSent() == sentBefore, "the 2*th call on the same frame sends no row", k, (long)ctx.localMapRowsSent(), (long)sentBefore);
+      if (k == 1) {   // the same call through the context without a frame cache, on a copy of the frame's matches
+        const std::vector<MapPoint*> keep = cur.mvpMapPoints;
+        std::fill(cur.mvpMapPoints.begin(), cur.mvpMapPoints.end(), static_cast<MapPoint*>(nullptr));
+        const int gotOff = orbfe::SearchByProjectionLastFrame(ctxOff, true, cur, last, th, geometry);
+        bool sameOff = gotOff == want;
+        for (int i = 0; i < cur.N && sameOff; i++) sameOff = (cur.mvpMapPoints[i] ? cur.mvpMapPoints[i]->id : -1) == curIds[i];
+        expect(sameOff, "SearchByProjectionLastFrame(Cur, Last, th), frame cache off", k, gotOff, want);
+        cur.mvpMapPoints = keep;
+      }
       lastCalls++;
       totalLast += got;
     }
@@ -288,10 +300,18 @@ int main(int argc, char** argv) {
       table(P);
       const int want = orc_sbp_keyframe(&cv, cur.mTcw.v, reinterpret_cast<const OrcKp*>(kf->mvKeysUn.data()), (int)kfIds.size(), kfIds.data(),
                                         already.data(), &P, ids.data(), 10.f, 100, 1);
+      const std::vector<MapPoint*> before = cur.mvpMapPoints;
       const int got = orbfe::SearchByProjectionKeyFrame(ctx, true, cur, kf, sFound, 10.f, 100, geometry);
       bool same = got == want;
       for (int i = 0; i < cur.N && same; i++) same = (cur.mvpMapPoints[i] ? cur.mvpMapPoints[i]->id : -1) == ids[i];
       expect(same, "SearchByProjectionKeyFrame(Cur, pKF, sAlreadyFound, 10, 100)", k, got, want);
+      if (k == 1) {   // the same call through the context without a frame cache, from the same matches
+        cur.mvpMapPoints = before;
+        const int gotOff = orbfe::SearchByProjectionKeyFrame(ctxOff, true, cur, kf, sFound, 10.f, 100, geometry);
+        bool sameOff = gotOff == want;
+        for (int i = 0; i < cur.N && sameOff; i++) sameOff = (cur.mvpMapPoints[i] ? cur.mvpMapPoints[i]->id : -1) == ids[i];
+        expect(sameOff, "SearchByProjectionKeyFrame(Cur, pKF, sAlreadyFound, 10, 100), frame cache off", k, gotOff, want);
+      }
       kfCalls++;
       totalKf += got;
       cur.mvpMapPoints = keep;
