@@ -1092,6 +1092,40 @@ int orbfe_score_init_hypotheses_frames(orbfe_matcher* m, orbfe_frame* f1, orbfe_
                                        float* scores_f, int32_t* best_h, int32_t* best_f, float* best_score_h,
                                        float* best_score_f, uint8_t* inliers_h, uint8_t* inliers_f, int* n_matches);
 
+/* ---------------------------------------------------------------------------------------------
+ * RANSAC scoring.  The inlier tests of the two solvers that follow the BoW searches: Sim3Solver::CheckInliers with its two
+ * Project calls (src/Sim3Solver.cc:343-367, :385-406; LoopClosing::ComputeSim3) and PnPsolver::CheckInliers
+ * (src/PnPsolver.cc:313-344; Tracking::Relocalization), for a flat list of hypotheses in one call.  The minimal-set solvers
+ * (Sim3Solver::ComputeSim3 with cv::eigen, EPnP's compute_pose) stay with the caller; what comes here are their results.  The
+ * selection among the counts (Sim3Solver::iterate, PnPsolver::iterate) is include/orbfe/RansacScoring.h.
+ *
+ * A call covers n_seg SEGMENTS.  A segment is one solver -- one loop or relocalisation candidate -- with its own correspondences
+ * [seg_off[s], seg_off[s + 1]) of corr and its own camera(s); hypothesis k belongs to segment hyp_seg[k].  N of a segment may be 0.
+ * counts[k]: mnInliersi of hypothesis k.  masks: mvbInliersi as 64-bit words, bit (i & 63) of word (i >> 6) for correspondence
+ * i of the hypothesis' segment, ceil(N / 64) words per hypothesis (none for N = 0), bits at and above N are 0.  The words of
+ * hypothesis k start at masks + mask_off[k]; with mask_off == NULL they follow those of hypothesis k - 1, and
+ * orbfe_ransac_mask_words gives the total.  counts and masks may each be NULL.  All arrays are host memory.  Inlier bits are the
+ * reference's bit for bit: the same expressions without contraction; a NaN error is an outlier; the sign of z is not tested.
+ * ORBFE_ERR_INVALID (nothing is sent, no output is written): a NULL matcher, n_seg < 1, n_hyp < 1, a NULL array, seg_off[0] < 0
+ * or a decreasing seg_off, hyp_seg[k] outside [0, n_seg), a negative mask_off[k], more than (2^31 - 1) / 12 correspondences
+ * or more than 2^31 - 1 mask words in one call.
+ * ------------------------------------------------------------------------------------------- */
+/* Sim3Solver.cc:343-367.  corr: 12 floats per correspondence -- mvX3Dc1[i] (3), mvX3Dc2[i] (3), mvP1im1[i] (2), mvP2im2[i] (2),
+ * (float)mvnMaxError1[i], (float)mvnMaxError2[i].  cams: fx fy cx cy of mK1, then of mK2, per segment.  T12 / T21: per hypothesis
+ * the first 12 floats of mT12i / mT21i, i.e. the top three rows of the 4x4, row-major (r00 r01 r02 t0 r10 ...). */
+int orbfe_score_sim3_hypotheses(orbfe_matcher* m, int n_seg, const int32_t* seg_off /* n_seg + 1 */, const float* corr,
+                                const float* cams /* 8 * n_seg */, int n_hyp, const int32_t* hyp_seg /* n_hyp */,
+                                const float* T12 /* 12 * n_hyp */, const float* T21 /* 12 * n_hyp */, int32_t* counts /* n_hyp */,
+                                const int64_t* mask_off /* n_hyp or NULL */, uint64_t* masks);
+/* PnPsolver.cc:313-344.  corr: 6 floats per correspondence -- mvP3Dw[i] (3), mvP2D[i] (2), mvMaxError[i].  cams: uc vc fu fv per
+ * segment, in double.  Rt: per hypothesis mRi (9, row-major) then mti (3), in double. */
+int orbfe_score_pnp_hypotheses(orbfe_matcher* m, int n_seg, const int32_t* seg_off /* n_seg + 1 */, const float* corr,
+                               const double* cams /* 4 * n_seg */, int n_hyp, const int32_t* hyp_seg /* n_hyp */,
+                               const double* Rt /* 12 * n_hyp */, int32_t* counts /* n_hyp */,
+                               const int64_t* mask_off /* n_hyp or NULL */, uint64_t* masks);
+/* The number of mask words a packed call writes; 0 (and orbfe_last_error) for a layout the scoring calls refuse. */
+size_t orbfe_ransac_mask_words(int n_seg, const int32_t* seg_off, int n_hyp, const int32_t* hyp_seg);
+
 /* int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t,size_t>>&
  * vMatchedPairs)  (ORBmatcher.cc:652-804, with CheckDistEpipolarLine :135-152), from the epipole onwards: the caller
  * computes (ex, ey) (:657-666) and passes F12 row-major.  has_mpX[i] != 0: the keypoint already has a MapPoint and is

@@ -168,6 +168,10 @@ def load_library():
     L.orbfe_score_init_hypotheses.argtypes = [vp, vp, ci] + tail
     L.orbfe_score_init_hypotheses_kps.argtypes = [vp, vp, ci, vp, ci, vp] + tail + [C.POINTER(ci)]
     L.orbfe_score_init_hypotheses_frames.argtypes = [vp, vp, vp, vp] + tail + [C.POINTER(ci)]
+    L.orbfe_score_sim3_hypotheses.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_score_pnp_hypotheses.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_ransac_mask_words.argtypes = [ci, vp, ci, vp]
+    L.orbfe_ransac_mask_words.restype = C.c_size_t
     L.orbfe_search_by_bow.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp,
                                       C.POINTER(ci)]
     L.orbfe_search_by_bow_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, ci, ci, vp, vp]
@@ -773,8 +777,66 @@ class _InitScoreCall:
         return r
 
 
+class _RansacCall:
+    """Layout and outputs of one orbfe_score_sim3_hypotheses / orbfe_score_pnp_hypotheses call."""
+
+    def __init__(self, L, row, corr, seg_off, hyp_seg, n_hyp):
+        self.corr = np.ascontiguousarray(corr, np.float32).reshape(-1, row)
+        if seg_off is None:                      # one segment: all correspondences, all hypotheses
+            seg_off = [0, len(self.corr)]
+            hyp_seg = np.zeros(n_hyp, np.int32) if hyp_seg is None else hyp_seg
+        self.seg_off = np.ascontiguousarray(seg_off, np.int32)
+        self.hyp_seg = np.ascontiguousarray(hyp_seg, np.int32)
+        if len(self.hyp_seg) != n_hyp:
+            raise ValueError('hyp_seg has one entry per hypothesis')
+        if len(self.seg_off) < 2 or self.seg_off[-1] > len(self.corr):
+            raise ValueError('seg_off has n_seg + 1 entries and ends inside corr')
+        self.n_seg, self.n_hyp = len(self.seg_off) - 1, n_hyp
+        words = L.orbfe_ransac_mask_words(self.n_seg, _p(self.seg_off), n_hyp, _p(self.hyp_seg))
+        self.counts = np.zeros(max(n_hyp, 1), np.int32)
+        self.words = np.zeros(max(int(words), 1), np.uint64)
+
+    def result(self):
+        """(counts [n_hyp] int32, masks: per hypothesis a bool array over its segment's correspondences)"""
+        n = np.diff(self.seg_off.astype(np.int64))[self.hyp_seg]
+        w = (n + 63) // 64
+        start = np.concatenate([[0], np.cumsum(w)])
+        bits = np.unpackbits(self.words.view(np.uint8), bitorder='little')
+        masks = [bits[64 * start[k]:64 * start[k] + n[k]].astype(bool) for k in range(self.n_hyp)]
+        return self.counts[:self.n_hyp].copy(), masks
+
+
 class Matcher:
     """Hot subset of ORBmatcher on one GPU."""
+
+    def score_sim3_hypotheses(self, corr, cams, T12, T21, seg_off=None, hyp_seg=None):
+        """Sim3Solver::CheckInliers for every hypothesis of every solver (segment) in one call.  corr: [N][12] = X3Dc1, X3Dc2,
+        P1im1, P2im2, maxErr1, maxErr2; cams: [n_seg][8] = fx fy cx cy of mK1, of mK2; T12 / T21: [K][12] float32, the top three
+        rows of the 4x4; seg_off [n_seg + 1] / hyp_seg [K] (default: one segment).  -> (counts, per-hypothesis bool masks)."""
+        T12 = np.ascontiguousarray(T12, np.float32).reshape(-1, 12)
+        T21 = np.ascontiguousarray(T21, np.float32).reshape(-1, 12)
+        if len(T12) != len(T21):
+            raise ValueError('T12 and T21 hold the same number of hypotheses')
+        c = _RansacCall(self.L, 12, corr, seg_off, hyp_seg, len(T12))
+        cams = np.ascontiguousarray(cams, np.float32).reshape(-1, 8)
+        if len(cams) != c.n_seg:
+            raise ValueError('cams has one row per segment')
+        _check(self.L.orbfe_score_sim3_hypotheses(self.h, c.n_seg, _p(c.seg_off), _p(c.corr), _p(cams), c.n_hyp, _p(c.hyp_seg), _p(T12),
+                                                  _p(T21), _p(c.counts), None, _p(c.words)))
+        return c.result()
+
+    def score_pnp_hypotheses(self, corr, cams, Rt, seg_off=None, hyp_seg=None):
+        """PnPsolver::CheckInliers for every hypothesis of every solver (segment) in one call.  corr: [N][6] = P3Dw, P2D, maxErr;
+        cams: [n_seg][4] = uc vc fu fv (float64); Rt: [K][12] float64 = mRi row-major, then mti.  -> (counts, per-hypothesis
+        bool masks)."""
+        Rt = np.ascontiguousarray(Rt, np.float64).reshape(-1, 12)
+        c = _RansacCall(self.L, 6, corr, seg_off, hyp_seg, len(Rt))
+        cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 4)
+        if len(cams) != c.n_seg:
+            raise ValueError('cams has one row per segment')
+        _check(self.L.orbfe_score_pnp_hypotheses(self.h, c.n_seg, _p(c.seg_off), _p(c.corr), _p(cams), c.n_hyp, _p(c.hyp_seg), _p(Rt),
+                                                 _p(c.counts), None, _p(c.words)))
+        return c.result()
 
     def score_init_hypotheses(self, pts, sigma, H21=None, H12=None, F21=None):
         """Initializer::CheckHomography / CheckFundamental for every hypothesis and the selection of FindHomography /

@@ -481,6 +481,7 @@ struct orbfe_matcher {
   std::shared_ptr<void> initscore;   // scratch of orbfe_score_init_hypotheses* (orbfe_initscore.hip)
   std::shared_ptr<void> covis;   // scratch of orbfe_covisibility_counts (orbfe_covis.hip)
   std::shared_ptr<void> culling;   // scratch of orbfe_redundant_observations (orbfe_culling.hip)
+  std::shared_ptr<void> ransac;   // scratch of orbfe_score_sim3_hypotheses / orbfe_score_pnp_hypotheses (orbfe_ransac.hip)
   DevBuf<uint8_t> d_in;    // packed upload arena
   PinBuf<uint8_t> h_in;
   DevBuf<uint32_t> d_out;  // [total(1) pad][qcount nq][qoff nq]
