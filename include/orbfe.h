@@ -173,7 +173,9 @@ int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* g
  * handle's stream and returns at once; _collect waits for it and fills the outputs exactly as
  * orbfe_extract_batch does.  One batch may be outstanding per handle; the frames (and, for host input,
  * the host buffers) must stay valid until _collect returns.  Lets a caller overlap the GPU extraction of
- * batch k+1 with the matching of batch k. */
+ * batch k+1 with the matching of batch k.  (A geometry outside the GPU quadtree's limits -- a strip wider than
+ * 4.5 : 1, more than 2 044 features on a level -- is selected by the host quadtree inside _submit, which then
+ * returns only when pyramid, FAST and compaction have run: same results and the same calls, less overlap.) */
 int orbfe_extract_batch_submit(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory,
                                int rows, int cols, size_t stride_bytes);
 int orbfe_extract_batch_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out);
@@ -257,9 +259,11 @@ int orbfe_debug_level_copy(orbfe_extractor* h, int frame, int level, uint8_t* ou
  * a cell): triples (x, y, score) with x,y relative to (minBorderX,minBorderY) = (16,16) as in
  * vToDistributeKeys (ORBextractor.cc:861-866). */
 int orbfe_debug_candidates(orbfe_extractor* h, int frame, int level, int32_t* xys, int cap, int* n_out);
-/* Host wall-clock milliseconds of the last call: [0]=waiting for stage 1 (pyramid+FAST+compaction) and
- * the candidate D2H, [1]=host quadtrees + selection packing, [2]=tail wait for stage 2
- * (orientation+blur+rBRIEF), [3]=output assembly, [4]=total. */
+/* Host wall-clock milliseconds of the last collected batch: [0]=enqueue (the submit call), [1]=GPU wait inside the
+ * collect call, [2]=host selection -- 0 unless the host quadtree selected the batch (geometries outside the GPU
+ * quadtree's limits, ORBFE_HOST_QUADTREE=1): then the wait for pyramid+FAST+compaction, the candidate D2H, the
+ * quadtrees and the upload of the selection, all of which happen inside the submit call and are part of [0] too --
+ * [3]=output assembly (with the host-side matching of a host-selected batch), [4]=total. */
 int orbfe_debug_stage_ms(const orbfe_extractor* h, float out[5]);
 /* GPU time (HIP events recorded on the launch stream) accumulated per kernel group since the last
  * reset: out_ms[0]=pyramid (k_resize x (nlevels-1)), [1]=k_fast_tasks, [2]=k_compact,

@@ -2,10 +2,12 @@
 //
 // Behaviour contract: ORB_SLAM2::ORBextractor of the reference (src/ORBextractor.cc:442-502 ctor,
 // :907-969 operator(), :971-996 ComputePyramid, :797-895 ComputeKeyPointsOctTree).  The pixel work
-// runs in the kernels of orbfe_kernels.hip, the order-defining quadtree in orbfe_quadtree.hip (one
-// stream submission per batch, submitGpuQt); a second, host-side quadtree (quadtree.h, run()) serves
-// geometries the kernel does not hold (more than 4 roots or 2044 features per level) and
-// ORBFE_HOST_QUADTREE=1.  There is no CPU fallback for the kernels.
+// runs in the kernels of orbfe_kernels.hip.  Every call takes ONE path, submit() + collect(): frames to the device, front (pyramid,
+// FAST, compaction), selection, describe, mvKeysUn, vocabulary descent, match chain, one arena copy.  Only the selection stage has
+// two forms (extract_plan.h decides): the order-defining quadtree of orbfe_quadtree.hip, inside the one stream submission, or -- for
+// geometries that kernel does not hold (more than 4 roots or 2044 features per level) and with ORBFE_HOST_QUADTREE=1 -- the host
+// quadtree (quadtree.h, selectOnHost), which writes the same slots of the same arena and blocks inside submit.  There is no CPU
+// fallback for the kernels.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
 #include <sched.h>
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "extract_plan.h"
 #include "glibc_sincosf.h"
 #include "host_pool.h"
 #include "orbfe_internal.h"
@@ -39,8 +42,6 @@ void launch_fast(const PyramidParams& P, int nframes, hipStream_t st);
 uint32_t fast_cell_geo(int wCell, int hCell);
 void launch_compact(const PyramidParams& P, int nframes, hipStream_t st);
 void launch_compact_local(const PyramidParams& P, int nframes, hipStream_t st, int level0, int level1);
-void launch_describe(const PyramidParams& P, const SelKp* sel, int nsel, float* angle, uint8_t* desc,
-                     hipStream_t st);
 void launch_sincos(const float* deg, int n, float* c, float* s, hipStream_t st);
 void launch_spin(unsigned long long ticks, hipStream_t st);
 void launch_describe_slots(const PyramidParams& P, const SelKp* sel, int nslots, float* angle, uint8_t* desc,
@@ -132,16 +133,15 @@ struct orbfe_sfi_chain {
   DevBuf<uint8_t> desc[2];
   DevBuf<float> xyUn[2];       // mvKeysUn of the carried level-0 keypoints (allocated by the first batch of a handle with a camera)
   bool camera = false;         // the last batch was matched on mvKeysUn (a batch of the other kind starts the chain over: its carry lacks them)
-  std::vector<float> hostPrevXyUn;   // host-quadtree route, with a camera
   DevBuf<uint32_t> count;      // [0],[1]: level-0 count of the buffers; [2]: constant 0xffffffff ("none")
   hipEvent_t ready[2] = {};
   long long seq = 0;           // batches submitted so far
   bool isolated = false;       // orbfe_sfi_chain_set_isolated: no batch has a predecessor (frame 0 of every batch reports no match)
   bool restart = false;        // orbfe_sfi_chain_restart: the next batch's frame 0 has no predecessor in the chain
-  // host-quadtree route (geometries outside the GPU quadtree's limits): the predecessor frame lives on the host and the
-  // searches go through an ordinary matcher handle
+  // host-selected batches (geometries outside the GPU quadtree's limits, ORBFE_HOST_QUADTREE=1) are matched when they are collected:
+  // the predecessor frame lives on the host and the searches go through an ordinary matcher handle
   orbfe_matcher* hostMatcher = nullptr;
-  std::vector<OrbfeKeyPoint> hostPrevKps;
+  std::vector<OrbfeKeyPoint> hostPrevKps;   // coordinates = mvKeysUn
   std::vector<uint8_t> hostPrevDesc;
   bool hostPrevValid = false;
   // equidistant camera, GPU route: the settled predecessor on the host (a collect that patched a point redoes match rows there), and
@@ -184,18 +184,14 @@ struct orbfe_extractor {
   double scaleFactor;  // the reference keeps the float ctor argument in a double member (ORBextractor.h:313)
   std::vector<float> sf, isf, sigma2, isigma2;
   std::vector<int> nfeat;
-  static constexpr int kMaxSub = 4;
-  hipStream_t stream = nullptr;          // == streams[0]
-  hipStream_t streams[kMaxSub] = {};
-  static constexpr int subBatches = 4;   // host-quadtree route: sub-batches in flight (one HIP stream each)
+  hipStream_t stream = nullptr;          // the one stream of the handle
   hipEvent_t evUpload = nullptr;
   bool lastLocalCand = false, submitLocalCand = false;   // candidate lists of the last collected / submitted batch are level-local (k_compact_local)
   bool localLists = true;         // (experiments build, ORBFE_LOCAL_LISTS=0: the packed list of k_compact in latency-bound calls too)
-  hipEvent_t evFrame0 = nullptr, evS1[kMaxSub] = {};
-  int subSel[kMaxSub] = {};
-  size_t candHostCap = 0;
-  // GPU quadtree path (default): everything from the frame to descriptors in one stream submission
-  bool gpuQuadtree = true;
+  size_t candHostCap = 0;         // host selection: candidates per frame the page-locked list holds (grown on demand)
+  bool forceHostQt = false;       // ORBFE_HOST_QUADTREE=1: quadtree.h selects whatever the geometry
+  bool submitHostSel = false;     // the submitted batch was selected on the host (and, if matched, is matched at collect)
+  double hostSelMs = 0;           // its selection stage: wait for the front + candidate copy + quadtrees + upload
   // Frame::ComputeBoW fused behind k_describe (orbfe_extractor_set_vocabulary): the descent runs on the descriptors
   // while they are still in HBM; (leaf, node) pairs of the last collected batch in keypoint order, per frame
   orbfe_vocabulary* voc = nullptr;
@@ -205,13 +201,13 @@ struct orbfe_extractor {
   PinBuf<uint2> h_bow;
   std::vector<std::vector<uint2>> bowKp;
   int kpPerFrameCap = 0;     // internal per-frame keypoint capacity of the result arena (set by setGeometry)
-  bool geomGpuQtOk = true;   // every level of the current image size has 1..4 quadtree roots (aspect ratio < 4.5)
+  bool geomGpuQtOk = true;   // k_quadtree3 holds the current image size (extract_plan.h)
   QtParams QP{};
-  int selOff[kMaxLevels + 1] = {};
+  int selOff[kMaxLevels + 1] = {};   // slot layout of the current image size (extract_plan.h, set by setGeometry)
   int selPerFrame = 0;
+  int n0cap = 0;            // level-0 slots of a geometry the GPU quadtree holds: what a match chain is sized by (fixed at create)
   DevBuf<uint16_t> d_own;   // node id per candidate (quadtree)
   hipEvent_t evQt[2] = {};
-  std::vector<int> frameKpBase, frameKpCount;
 
   int rows = 0, cols = 0, batchCap = 0;
   PyramidParams P{};
@@ -251,7 +247,7 @@ struct orbfe_extractor {
   CameraModel cam{};
   View<float> d_xyUn, h_xyUn;
   bool lastCam = false, submitCam = false;   // the last collected / submitted batch carries mvKeysUn
-  DevBuf<float> d_unTmp;                     // orbfe_extractor_undistort and the host-quadtree route: points of the caller
+  DevBuf<float> d_unTmp;                     // orbfe_extractor_undistort: points of the caller
   PinBuf<float> h_unTmp;
   // orbfe_extractor_set_camera_equidistant: k_undistort_equidistant in k_undistort's place (camActive is then set too).  The
   // kernel's undecided points (equidistant_tan.h) are settled on the host with orbfe_undistort_equidistant when the batch is
@@ -286,24 +282,13 @@ struct orbfe_extractor {
   DevBuf<uint8_t> d_gray;   // level 0 of colour input
   bool inLinear = false;   // host frames are uploaded with linear copies (inPitch == host stride)
   int lastFrames = 0;
-  // deferred route of _submit / _submit_matched when the GPU quadtree cannot take the geometry: the batch is extracted by the
-  // blocking host-quadtree path at submit time (and matched through a matcher handle), _collect hands the results out
-  int deferredFrames = 0, deferredCap = 0;
-  bool deferredMatched = false;
-  std::vector<OrbfeKeyPoint> defKps;
-  std::vector<uint8_t> defDesc;
-  std::vector<int> defN, defNm;
-  std::vector<int32_t> defM12;
-  std::vector<float> defXyUn;   // [frames][deferredCap][2] mvKeysUn, only with a distorting camera (deferredCam)
-  bool deferredCam = false;
-  bool lastGpuQt = false, lastZeroCopy = false, submitZeroCopy = false;   // route of the last collected / submitted batch
+  bool lastZeroCopy = false, submitZeroCopy = false;   // output route of the last collected / submitted batch
   bool describe4 = true;         // ORBFE_DESCRIBE_WAVES=1: one wave per keypoint in one- / two-frame calls too
   float stageMs[5] = {0, 0, 0, 0, 0};
-  hipEvent_t ev[kMaxSub][6] = {};
+  hipEvent_t ev[6] = {};
   double kernMs[5] = {0, 0, 0, 0, 0};
   long long kernBatches = 0, kernFrames = 0;
 
-  struct Meta { int16_t x, y; uint8_t score, level; };
   struct Worker {  // per-thread quadtree scratch
     QuadTree qt;
     std::vector<int16_t> qx, qy;
@@ -313,27 +298,24 @@ struct orbfe_extractor {
   std::unique_ptr<HostPool> pool;
   int hostThreads = 1;
   std::vector<Worker> workers;
-  std::vector<std::vector<Meta>> taskOut;  // [frame*nlevels + level]
-  std::vector<Meta> meta;
 
   ~orbfe_extractor() {
     (void)hipSetDevice(device);
-    for (auto& st : streams) if (st) (void)hipStreamSynchronize(st);   // a batch may still be in flight
+    if (stream) (void)hipStreamSynchronize(stream);   // a batch may still be in flight
     d_bow.release(); h_bow.release();
     d_tables.release(); d_coneTab.release(); d_coneTailTab.release(); d_slab.release(); d_in.release(); d_cellCount.release();
     d_sfiOrder.release(); d_sfiOrderCount.release(); d_sfiPool.release(); d_sfiPcount.release();
     d_cells.release(); d_zeros.release(); d_slots.release(); d_cand.release(); d_frame0.release(); d_gray.release(); d_outArena.release(); h_outArena.release();
     d_f32tmp.release(); d_unTmp.release(); h_unTmp.release();
     h_frame0.release(); h_cand.release();
-    for (auto& es : ev) for (auto& e : es) if (e) (void)hipEventDestroy(e);
-    for (auto& e : evS1) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : evQt) if (e) (void)hipEventDestroy(e);
     d_own.release();
-    if (evFrame0) (void)hipEventDestroy(evFrame0);
     if (evUpload) (void)hipEventDestroy(evUpload);
-
-    for (auto& st : streams) if (st) (void)hipStreamDestroy(st);
+    if (stream) (void)hipStreamDestroy(stream);
   }
+
+  bool hostSelect() const { return forceHostQt || !geomGpuQtOk; }   // who selects for the current image size
 
   // Level sizes, FAST cell grids, bilinear tables.  ORBextractor.cc:975-976 (sizes), :807-823 (cells).
   int setGeometry(int r, int c) {
@@ -342,8 +324,6 @@ struct orbfe_extractor {
       set_err("image %dx%d exceeds the 4095-pixel coordinate packing limit", c, r);
       return ORBFE_ERR_INVALID;
     }
-    bool qtOk = true;
-    int kpSum = 8;
     PyramidParams Q{};
     Q.nlevels = nlevels;
     Q.iniTh = iniTh;
@@ -365,11 +345,6 @@ struct orbfe_extractor {
       }
       L.wCell = (int)std::ceil(width / L.nCols);
       L.hCell = (int)std::ceil(height / L.nRows);
-      {   // root nodes of DistributeOctTree (ORBextractor.cc:574-578); k_quadtree2 holds up to 4 of them
-        const int nIni = (int)roundf(static_cast<float>(L.w - 2 * kBorder) / (L.h - 2 * kBorder));
-        if (nIni < 1 || nIni > 4) qtOk = false;
-        kpSum += std::max(nfeat[l] + 4, 4 * std::max(nIni, 4));
-      }
       L.cellBase = cellBase;
       cellBase += L.nCols * L.nRows;
       L.slotCap = (((L.wCell + 1) / 2) * ((L.hCell + 1) / 2) + 3) & ~3;   // the strict-local-max bound, rounded up so that every cell's slots start 16-byte aligned
@@ -386,7 +361,6 @@ struct orbfe_extractor {
     Q.slabBytes = off;
     Q.slotsPerFrame = slot;
     Q.candCap = slot;
-    if (slot >= (1ll << 24)) qtOk = false;   // k_quadtree3 packs a candidate index into 24 bits (not reachable below 4096 x 4096)
 
     // bilinear tables, SURVEY.md Appendix B.2 (float/double arithmetic exactly as cv::resize)
     std::vector<uint8_t> tab(tableBytes);
@@ -561,21 +535,17 @@ struct orbfe_extractor {
     Q.cells = d_cells.p;
     P = Q;
     rows = r;
-    geomGpuQtOk = qtOk;
-    // keypoints one frame can yield: a level returns at most max(N_l + 2, 4 * roots) (ORBextractor.cc:620-773)
-    const int kpCap = std::max(kpSum, selPerFrame);
-    if (kpCap > kpPerFrameCap) {
-      kpPerFrameCap = kpCap;
-      batchCap = 0;   // the result arena is carved again
+    {   // slot layout of the result arena and who selects (extract_plan.h)
+      int levW[kMaxLevels], levH[kMaxLevels];
+      for (int l = 0; l < nlevels; l++) { levW[l] = Q.lv[l].w; levH[l] = Q.lv[l].h; }
+      const ExtractPlan plan = extract_plan(nlevels, levW, levH, nfeat.data(), Q.candCap);
+      memcpy(selOff, plan.selOff, sizeof selOff);
+      selPerFrame = plan.selPerFrame;
+      geomGpuQtOk = plan.gpuQuadtree;
     }
+    kpPerFrameCap = std::max(kpPerFrameCap, selPerFrame + 8);
     cols = c;
-    batchCap = 0;
-    return ORBFE_OK;
-  }
-
-  int ensureSubStreams(int nsub) {
-    for (int s = 1; s < nsub; s++)
-      if (!streams[s]) HIP_TRY(hipStreamCreateWithFlags(&streams[s], hipStreamNonBlocking));
+    batchCap = 0;   // the result arena is carved again
     return ORBFE_OK;
   }
 
@@ -615,12 +585,13 @@ struct orbfe_extractor {
         d_xyUn.p = camActive ? (float*)(D + oXy) : nullptr; h_xyUn.p = camActive ? (float*)(Hh + oXy) : nullptr;
         d_undec.p = camEqui ? (uint32_t*)(D + oUd) : nullptr; h_undec.p = camEqui ? (uint32_t*)(Hh + oUd) : nullptr;
       }
-      if (gpuQuadtree) {
+      if (!hostSelect()) {
         if ((rc = d_own.ensure((size_t)P.candCap * nframes))) return rc;
+      } else {
+        if (candHostCap == 0) candHostCap = 96 * 1024;
+        if ((rc = h_cand.ensure(candHostCap * (size_t)nframes))) return rc;
       }
       batchCap = nframes;
-      if (candHostCap == 0) candHostCap = 96 * 1024;
-      if ((rc = h_cand.ensure(candHostCap * (size_t)batchCap))) return rc;
     }
     if (inChannels() > 1) {
       grayPitch = align_up(cols, 256);
@@ -643,9 +614,6 @@ struct orbfe_extractor {
     return ORBFE_OK;
   }
 
-  // GPU-quadtree path: frame -> pyramid -> FAST -> compaction -> quadtree -> orientation/blur/rBRIEF in ONE
-  // stream submission, one synchronisation, fixed-size D2H of the selection slots.
-  // H2D of host frames [f0, f0+nf) into d_in on `st`
   // H2D of host frames [f0, f0+nf) on `st`.  devAt[f] receives the device address frame f lands at.  Frames that tile
   // one contiguous host block -- in ANY order: a ring buffer read forwards, backwards or rotated -- travel as ONE DMA
   // (a 66 MB copy runs at 56.8 GB/s on this link, 32 separate 2 MB copies at 28 GB/s); otherwise ascending runs are
@@ -689,32 +657,14 @@ struct orbfe_extractor {
     return ORBFE_OK;
   }
 
-  // host-quadtree path: frame f always lands in slot f of d_in (the pointer table is uploaded before the frames)
-  int uploadSlots(int f0, int nf, const uint8_t* const* gray, size_t stride, int r, int c, hipStream_t st) {
-    for (int f = f0; f < f0 + nf; f++) {
-      if (inLinear)
-        HIP_TRY(hipMemcpyAsync(d_in.p + (size_t)inPitch * rows * f, gray[f], stride * (size_t)(r - 1) + c, hipMemcpyHostToDevice, st));
-      else
-        HIP_TRY(hipMemcpy2DAsync(d_in.p + (size_t)inPitch * rows * f, inPitch, gray[f], stride, c, r, hipMemcpyHostToDevice, st));
-    }
-    return ORBFE_OK;
-  }
-
-  int runGpuQt(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, OrbfeKeyPoint* kps,
-               uint8_t* desc, int cap, int* n_out, float* xy_un = nullptr) {
-    int rc = submitGpuQt(nframes, gray, onDevice, r, c, stride);
-    if (rc) return rc;
-    return waitGpuQt(kps, desc, cap, n_out, nullptr, nullptr, xy_un);
-  }
-
-  // k_undistort on n points of the caller (in place): orbfe_extractor_undistort, and the host-quadtree route, whose keypoints are
-  // assembled on the host.  Runs the stored coefficients whatever they are (the identity case is the CALLERS' to skip).
+  // k_undistort on n points of the caller (in place): orbfe_extractor_undistort.  Runs the stored coefficients whatever they are
+  // (the identity case is the CALLERS' to skip).
   int undistortPoints(float* xy, int n) {
     if (n <= 0) return ORBFE_OK;
     if (camEqui) return equidistantPoints(xy, n, nullptr, nullptr);
     int rc;
     if ((rc = d_unTmp.ensure(2 * (size_t)n)) || (rc = h_unTmp.ensure(2 * (size_t)n))) return rc;
-    hipStream_t st = streams[0];
+    hipStream_t st = stream;
     memcpy(h_unTmp.p, xy, 2 * sizeof(float) * (size_t)n);
     HIP_TRY(hipMemcpyAsync(d_unTmp.p, h_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
     UndistortArgs U{};
@@ -736,7 +686,7 @@ struct orbfe_extractor {
     if ((rc = d_unTmp.ensure(2 * (size_t)n)) || (rc = h_unTmp.ensure(2 * (size_t)n)) || (rc = d_undecTmp.ensure(words)) ||
         (rc = h_undecTmp.ensure(words)) || (rc = d_flagTmp.ensure((size_t)n)) || (rc = h_flagTmp.ensure((size_t)n)))
       return rc;
-    hipStream_t st = streams[0];
+    hipStream_t st = stream;
     memcpy(h_unTmp.p, xy, 2 * sizeof(float) * (size_t)n);
     HIP_TRY(hipMemcpyAsync(d_unTmp.p, h_unTmp.p, 2 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_undecTmp.p, 0, sizeof(uint32_t) * words, st));
@@ -793,16 +743,70 @@ struct orbfe_extractor {
       memcpy(slot, p, sizeof p);   // (the latency route's arena IS this page-locked memory)
       eqStats[1]++;
       eqFrameChanged[f] = 1;
-      if (!submitZeroCopy) { HIP_TRY(hipMemcpyAsync(d_xyUn.p + 2 * (size_t)i, slot, sizeof p, hipMemcpyHostToDevice, streams[0])); patched = true; }
+      if (!submitZeroCopy) { HIP_TRY(hipMemcpyAsync(d_xyUn.p + 2 * (size_t)i, slot, sizeof p, hipMemcpyHostToDevice, stream)); patched = true; }
     }
-    if (patched) HIP_TRY(hipStreamSynchronize(streams[0]));
+    if (patched) HIP_TRY(hipStreamSynchronize(stream));
+    return ORBFE_OK;
+  }
+
+  // The assembled frames with mvKeysUn for coordinates (Frame.cc:284-319): what a search on the host runs on.  kps / xy: [nframes][cap].
+  const OrbfeKeyPoint* undistortedKeypoints(int nframes, const OrbfeKeyPoint* kps, int cap, const int* n_out, const float* xy) {
+    eqUn.assign(kps, kps + (size_t)nframes * cap);
+    for (int f = 0; f < nframes; f++)
+      for (int j = 0; j < n_out[f]; j++) { eqUn[(size_t)f * cap + j].x = xy[((size_t)f * cap + j) * 2]; eqUn[(size_t)f * cap + j].y = xy[((size_t)f * cap + j) * 2 + 1]; }
+    return eqUn.data();
+  }
+
+  // Rows of a collected, matched batch searched on the host, through the chain's matcher handle, as one batched call: row f is frame f
+  // against frame f - 1 (pairs are independent: vbPrevMatched := F1's mvKeysUn each time, Tracking.cc:355-357), row 0 against the
+  // chain's host-side predecessor (prev == nullptr: none, the row is left alone).  un: undistortedKeypoints(), or the keypoints
+  // themselves where they are mvKeysUn.  take(f): is row f searched.  *nrows: rows searched.
+  struct HostPrev { const OrbfeKeyPoint* kps; const uint8_t* desc; int n; };
+  template <class Take>
+  int searchRowsOnHost(int nframes, const OrbfeKeyPoint* un, const uint8_t* desc, int cap, const int* n_out, const HostPrev* prev,
+                       int32_t* matches12, int* nmatches, Take take, int* nrows) {
+    orbfe_sfi_chain& ch = *submitChain;
+    std::vector<const OrbfeKeyPoint*> k1, k2;
+    std::vector<const uint8_t*> d1, d2;
+    std::vector<int> n1, n2, rowOf;
+    size_t words = 0;
+    for (int f = 0; f < nframes; f++) {
+      if (!take(f) || (f == 0 && !prev)) continue;
+      k1.push_back(f ? un + (size_t)(f - 1) * cap : prev->kps); d1.push_back(f ? desc + (size_t)(f - 1) * cap * 32 : prev->desc); n1.push_back(f ? n_out[f - 1] : prev->n);
+      k2.push_back(un + (size_t)f * cap); d2.push_back(desc + (size_t)f * cap * 32); n2.push_back(n_out[f]);
+      rowOf.push_back(f);
+      words += (size_t)std::max(n1.back(), 1);
+    }
+    *nrows = (int)rowOf.size();
+    if (rowOf.empty()) return ORBFE_OK;
+    int rc;
+    if (!ch.hostMatcher && (rc = orbfe_matcher_create(device, &ch.hostMatcher))) return rc;
+    eqXy.resize(2 * words);
+    eqRow.assign(words, -1);
+    std::vector<float*> pxy;
+    std::vector<int32_t*> m12;
+    std::vector<int> nm(rowOf.size(), 0);
+    size_t at = 0;
+    for (size_t p = 0; p < rowOf.size(); p++) {
+      pxy.push_back(eqXy.data() + 2 * at);
+      m12.push_back(eqRow.data() + at);
+      for (int j = 0; j < n1[p]; j++) { pxy[p][2 * j] = k1[p][j].x; pxy[p][2 * j + 1] = k1[p][j].y; }
+      at += (size_t)std::max(n1[p], 1);
+    }
+    if ((rc = orbfe_search_for_initialization_batch(ch.hostMatcher, (int)rowOf.size(), k1.data(), d1.data(), n1.data(), k2.data(), d2.data(), n2.data(),
+                                                    submitMs.bounds, pxy.data(), m12.data(), submitMs.window, submitMs.nnratio, submitMs.checkOri, nm.data())))
+      return rc;
+    for (size_t p = 0; p < rowOf.size(); p++) {
+      int32_t* row = matches12 + (size_t)rowOf[p] * cap;
+      for (int i = 0; i < cap; i++) row[i] = i < n1[p] ? m12[p][i] : -1;
+      nmatches[rowOf[p]] = nm[p];
+    }
     return ORBFE_OK;
   }
 
   // A matched batch of an equidistant handle, after output assembly.  The GPU searched on the kernel's provisional values: when the
-  // settle changed a point of frame f, rows f and f + 1 are searched again on the host (pairs are independent: vbPrevMatched := F1's
-  // mvKeysUn each time), and when it changed one of the PREVIOUS batch's last frame (eqCarryStale: the device carry this batch read)
-  // row 0 is.  kps / xy: the assembled frames ([nframes][cap]).
+  // settle changed a point of frame f, rows f and f + 1 are searched again on the host, and when it changed one of the PREVIOUS batch's
+  // last frame (eqCarryStale: the device carry this batch read) row 0 is.  kps / xy: the assembled frames ([nframes][cap]).
   int rematchEquidistant(int nframes, const OrbfeKeyPoint* kps, const uint8_t* desc, int cap, const int* n_out, const float* xy,
                          int32_t* matches12, int* nmatches) {
     orbfe_sfi_chain& ch = *submitChain;
@@ -810,36 +814,41 @@ struct orbfe_extractor {
     for (int f = 0; f < nframes; f++) any = any || eqFrameChanged[f];
     const bool stale = ch.eqCarryStale;
     ch.eqCarryStale = eqFrameChanged[nframes - 1] != 0 && !ch.isolated;
-    eqUn.assign(kps, kps + (size_t)nframes * cap);
-    for (int f = 0; f < nframes; f++)
-      for (int j = 0; j < n_out[f]; j++) { eqUn[(size_t)f * cap + j].x = xy[((size_t)f * cap + j) * 2]; eqUn[(size_t)f * cap + j].y = xy[((size_t)f * cap + j) * 2 + 1]; }
+    const OrbfeKeyPoint* un = undistortedKeypoints(nframes, kps, cap, n_out, xy);
     int rc = ORBFE_OK;
     if ((any || stale) && matches12 && nmatches) {
-      if (!ch.hostMatcher && (rc = orbfe_matcher_create(device, &ch.hostMatcher))) return rc;
-      for (int f = 0; f < nframes; f++) {   // a row takes part when one of its two frames changed
-        if (f == 0 && !((stale || eqFrameChanged[0]) && submitHasPred && ch.eqPrevValid)) continue;
-        if (f > 0 && !(eqFrameChanged[f - 1] || eqFrameChanged[f])) continue;
-        const OrbfeKeyPoint* k1 = f ? eqUn.data() + (size_t)(f - 1) * cap : ch.eqPrevKps.data();
-        const uint8_t* d1 = f ? desc + (size_t)(f - 1) * cap * 32 : ch.eqPrevDesc.data();
-        const int n1 = f ? n_out[f - 1] : (int)ch.eqPrevKps.size();
-        eqXy.resize((size_t)std::max(n1, 1) * 2);
-        for (int j = 0; j < n1; j++) { eqXy[2 * j] = k1[j].x; eqXy[2 * j + 1] = k1[j].y; }
-        eqRow.assign((size_t)std::max(n1, 1), -1);
-        int nm = 0;
-        if ((rc = orbfe_search_for_initialization(ch.hostMatcher, k1, d1, n1, eqUn.data() + (size_t)f * cap, desc + (size_t)f * cap * 32, n_out[f],
-                                                  submitMs.bounds, eqXy.data(), eqRow.data(), submitMs.window, submitMs.nnratio, submitMs.checkOri, &nm)))
-          return rc;
-        int32_t* row = matches12 + (size_t)f * cap;
-        for (int i = 0; i < cap; i++) row[i] = i < n1 ? eqRow[i] : -1;
-        nmatches[f] = nm;
-        eqStats[2]++;
-      }
+      const HostPrev prev{ch.eqPrevKps.data(), ch.eqPrevDesc.data(), (int)ch.eqPrevKps.size()};
+      int nrows = 0;
+      rc = searchRowsOnHost(nframes, un, desc, cap, n_out, submitHasPred && ch.eqPrevValid ? &prev : nullptr, matches12, nmatches,
+                            [&](int f) { return f ? eqFrameChanged[f - 1] || eqFrameChanged[f] : stale || eqFrameChanged[0]; }, &nrows);   // a row takes part when one of its two frames changed
+      if (rc) return rc;
+      eqStats[2] += nrows;
     }
     const int last = nframes - 1;
-    ch.eqPrevKps.assign(eqUn.begin() + (size_t)last * cap, eqUn.begin() + (size_t)last * cap + n_out[last]);
+    ch.eqPrevKps.assign(un + (size_t)last * cap, un + (size_t)last * cap + n_out[last]);
     ch.eqPrevDesc.assign(desc + (size_t)last * cap * 32, desc + ((size_t)last * cap + n_out[last]) * 32);
     ch.eqPrevValid = !ch.isolated;
     return rc;
+  }
+
+  // A matched, host-selected batch, after output assembly: SearchForInitialization of every frame against its predecessor on the
+  // caller's arrays, frame 0 against the chain's host-side carry (the previous host-selected batch's last frame), which this
+  // batch's last frame then replaces.  hasPred: what submit saw of the chain's rules (restart, isolated, another camera).
+  int matchOnHost(int nframes, const OrbfeKeyPoint* kps, const uint8_t* desc, int cap, const int* n_out, const float* xy,
+                  int32_t* matches12, int* nmatches) {
+    orbfe_sfi_chain& ch = *submitChain;
+    const OrbfeKeyPoint* un = submitCam ? undistortedKeypoints(nframes, kps, cap, n_out, xy) : kps;
+    const HostPrev prev{ch.hostPrevKps.data(), ch.hostPrevDesc.data(), (int)ch.hostPrevKps.size()};
+    int nrows = 0, rc;
+    if (matches12 && nmatches &&
+        (rc = searchRowsOnHost(nframes, un, desc, cap, n_out, submitHasPred && ch.hostPrevValid ? &prev : nullptr, matches12, nmatches,
+                               [](int) { return true; }, &nrows)))
+      return rc;
+    const int last = nframes - 1;
+    ch.hostPrevKps.assign(un + (size_t)last * cap, un + (size_t)last * cap + n_out[last]);
+    ch.hostPrevDesc.assign(desc + (size_t)last * cap * 32, desc + ((size_t)last * cap + n_out[last]) * 32);
+    ch.hostPrevValid = !ch.isolated;
+    return ORBFE_OK;
   }
 
   bool submitProfiled = false, fastTimed = false;
@@ -850,24 +859,68 @@ struct orbfe_extractor {
   struct MatchSpec { orbfe_sfi_chain* chain; float bounds[4]; int window; float nnratio; int checkOri; };
   MatchSpec submitMs{};
 
-  int submitGpuQt(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride,
-                  const MatchSpec* ms = nullptr) {
+  // How the submitted batch travels.  A host-selected batch always takes the packed candidate lists and the copy-command output.
+  struct Route { bool small, hostSel, zeroCopy, kernelOut, localCand, prof; };
+
+  // The one path: frame -> pyramid -> FAST -> compaction -> selection -> orientation/blur/rBRIEF [-> mvKeysUn -> vocabulary descent ->
+  // match chain] -> one D2H of the result arena.  With the GPU quadtree all of it is ONE stream submission and returns at once; a
+  // host-selected batch waits for the front inside (selectOnHost), then enqueues the rest.
+  int submit(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, const MatchSpec* ms = nullptr) {
     if (pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
     HIP_TRY(hipSetDevice(device));
     int rc;
     if ((rc = setGeometry(r, c))) return rc;
-    if (!geomGpuQtOk) {
-      set_err("image %dx%d: a pyramid level has more than 4 (or no) quadtree root nodes; only the blocking "
-              "orbfe_extract / orbfe_extract_batch calls (host quadtree path) handle such aspect ratios", c, r);
-      return ORBFE_ERR_INVALID;
-    }
     if ((rc = setBatch(nframes, !onDevice, stride))) return rc;
     const double t0 = now_ms();
-    hipStream_t st = streams[0];
-    const int ch = inChannels();
-    const int rowBytes = c * ch;
+    hipStream_t st = stream;
     for (int f = 0; f < nframes; f++)
       if (!gray[f]) { set_err("frame %d is NULL", f); return ORBFE_ERR_INVALID; }
+    Route R{};
+    R.small = nframes <= coneMaxFrames;
+    R.hostSel = hostSelect();
+    // Latency-bound plain extraction: the kernels write the results straight into the page-locked host arena
+    // (the quadtree a second copy of its selection, the descriptor kernel its only copy), so no copy command follows
+    // the last kernel.  Matching and bag-of-words read angles / descriptors on the device and keep the copy.
+    R.zeroCopy = zeroCopyOut && R.small && !voc && !(ms && ms->chain) && !R.hostSel;
+    // Batches, ORBFE_ZERO_COPY=2 (round 6): the kernels that produce a result store a second copy of it into the page-locked arena -- the
+    // quadtree its selection, the descriptor kernel angles and descriptors, SearchForInitialization its match vectors (their only copy)
+    // -- so no copy command follows the batch (16 % of the GPU's kernel time in round 5's profile); the first copies stay in HBM for the
+    // matching chain, the bag-of-words descent and resident frames.  Measured equal to the copy command (92.0 against 92.1 k frames/s
+    // with four batches in flight, 88.6 against 89.0 k with three) -- the stores cost what the copy costs -- so the copy
+    // command stays the default for batches.
+    R.kernelOut = zeroCopyBatches && !R.small && !R.hostSel;
+    // a latency-bound call compacts per level (k_compact_local: level-local lists, every wave's prefix in one memory round trip)
+    R.localCand = R.small && localLists && !R.hostSel;
+    R.prof = profileKernels;
+    submitZeroCopy = R.zeroCopy;
+    submitLocalCand = R.localCand;
+    submitHostSel = R.hostSel;
+    submitCam = camActive;
+    submitEqui = camEqui;
+    if ((rc = framesToDevice(nframes, gray, onDevice, r, c, stride, st))) return rc;
+    if ((rc = level0AndGray(nframes, gray, onDevice, r, c, stride, st))) return rc;
+    if ((rc = front(nframes, R, st))) return rc;
+    if ((rc = R.hostSel ? selectOnHost(nframes, st) : selectOnGpu(nframes, R, st))) return rc;
+    if ((rc = describe(nframes, R, st))) return rc;
+    if (camActive && (rc = undistortSlots(nframes, R, st))) return rc;
+    pendingBow = false;
+    if (voc && (rc = descendVocabulary(nframes, st))) return rc;
+    pendingMatched = false;
+    submitChain = nullptr;
+    if (ms && ms->chain && (rc = matchChain(*ms, nframes, R, st))) return rc;
+    if (!R.zeroCopy && !R.kernelOut) HIP_TRY(hipMemcpyAsync(h_outArena.p, d_outArena.p, outArenaBytes, hipMemcpyDeviceToHost, st));   // all results, one copy
+    submitProfiled = R.prof;
+    tSubmit0 = t0;
+    tSubmit1 = now_ms();
+    pendingFrames = nframes;
+    return ORBFE_OK;
+  }
+
+  // ---- the steps of submit(), in order -------------------------------------------------------------------------------------------
+  // Frames to the device: in place (device input), by this stream's own copies, by k_ingest, or over the shared upload lane.
+  int framesToDevice(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, hipStream_t st) {
+    int rc;
+    const int rowBytes = c * inChannels();
     devAt.resize(nframes);
     // Where the host frames live decides how they travel.  EVERY frame is looked at (a one- or two-frame call may mix a
     // page-locked frame with a pageable one, or hand over a view that runs past a registered range):
@@ -913,6 +966,13 @@ struct orbfe_extractor {
       HIP_TRY(hipEventRecord(evUpload, lane->stream));
       HIP_TRY(hipStreamWaitEvent(st, evUpload, 0));
     }
+    return ORBFE_OK;
+  }
+
+  // Level-0 pointers of the batch (in the kernel arguments for one or two grey frames, else a table) and, for colour input, the grey
+  // conversion in front of the pyramid.
+  int level0AndGray(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, hipStream_t st) {
+    const int ch = inChannels();
     bool rawAligned = ((onDevice ? (long long)stride : inPitch) & 3) == 0;
     for (int f = 0; f < nframes; f++) {
       const uint8_t* raw = onDevice ? gray[f] : devAt[f];
@@ -940,158 +1000,228 @@ struct orbfe_extractor {
       const int coef[3] = {rgb ? cr : cb, cg, rgb ? cb : cr};
       launch_to_gray(d_frame0.p + nframes, rawStride, d_frame0.p, grayPitch, r, c, ch, coef, q15 ? 15 : 14, rawAligned, nframes, st);
     }
-    const bool prof = profileKernels;
+    return ORBFE_OK;
+  }
+
+  // Front: pyramid, FAST, compaction -- the same launches whoever selects.
+  int front(int nframes, const Route& R, hipStream_t st) {
+    if (R.prof) HIP_TRY(hipEventRecord(ev[0], st));
+    if (launch_pyramid(P, nframes, st, coneOk && R.small ? &cone : (tailOk && !R.small ? &coneTail : nullptr))) { set_err("cannot configure the pyramid kernel"); return ORBFE_ERR_HIP; }
+    // the dominant kernel is timed in every batch (bench.py roofline); a latency-bound one- or two-frame call does
+    // without the two markers (each costs a few microseconds of dependent-launch gap) unless profiling is on
+    const bool timeFast = R.prof || !R.small;
+    fastTimed = timeFast;
+    if (timeFast) HIP_TRY(hipEventRecord(ev[1], st));
+    launch_fast(P, nframes, st);
+    if (timeFast) HIP_TRY(hipEventRecord(ev[2], st));
+    if (R.localCand) launch_compact_local(P, nframes, st, 0, nlevels);
+    else launch_compact(P, nframes, st);
+    if (R.prof) HIP_TRY(hipEventRecord(ev[3], st));
+    return ORBFE_OK;
+  }
+
+  // Selection, on the GPU: k_quadtree3 behind the compaction, in the same submission.
+  int selectOnGpu(int nframes, const Route& R, hipStream_t st) {
     QP.cand = d_cand.p; QP.levelStart = d_levelStart.p; QP.candCap = P.candCap; QP.nlevels = nlevels; QP.frameBase = 0;
     QP.own = d_own.p;
     QP.sel = d_sel.p; QP.selCount = d_selCount.p; QP.selPerFrame = selPerFrame;
-    // Latency-bound plain extraction: the kernels write the results straight into the page-locked host arena
-    // (the quadtree a second copy of its selection, the descriptor kernel its only copy), so no copy command follows
-    // the last kernel.  Matching and bag-of-words read angles / descriptors on the device and keep the copy.
-    const bool small = nframes <= coneMaxFrames;
-    const bool zeroCopy = zeroCopyOut && small && !voc && !(ms && ms->chain);
-    submitZeroCopy = zeroCopy;
     QP.jump = qtJump ? 1 : 0;
-    // Batches, ORBFE_ZERO_COPY=2 (round 6): the kernels that produce a result store a second copy of it into the page-locked arena -- the
-    // quadtree its selection, the descriptor kernel angles and descriptors, SearchForInitialization its match vectors (their only copy)
-    // -- so no copy command follows the batch (16 % of the GPU's kernel time in round 5's profile); the first copies stay in HBM for the
-    // matching chain, the bag-of-words descent and resident frames.  Measured equal to the copy command (92.0 against 92.1 k frames/s
-    // with four batches in flight, 88.6 against 89.0 k with three: gpurun r06l) -- the stores cost what the copy costs -- so the copy
-    // command stays the default for batches.
-    const bool kernelOut = zeroCopyBatches && !small;
-    QP.selHost = (zeroCopy || kernelOut) ? h_sel.p : nullptr;
-    QP.selCountHost = (zeroCopy || kernelOut) ? h_selCount.p : nullptr;
+    QP.selHost = (R.zeroCopy || R.kernelOut) ? h_sel.p : nullptr;
+    QP.selCountHost = (R.zeroCopy || R.kernelOut) ? h_selCount.p : nullptr;
     for (int l = 0; l < nlevels; l++) {
       QP.levW[l] = P.lv[l].w; QP.levH[l] = P.lv[l].h; QP.nfeat[l] = nfeat[l]; QP.selOff[l] = selOff[l];
       QP.candBase[l] = P.lv[l].slotBase;
     }
-    float* angOut = zeroCopy ? h_angle.p : d_angle.p;
-    uint8_t* descOut = zeroCopy ? h_desc.p : d_desc.p;
-    // a one- or two-frame call is latency-bound and alone on the chip: the quadtree keeps its candidates in LDS, four waves share a keypoint
-    const int qtLds = small ? qtLdsBudget : 0;
-    const bool four = describe4 && small;
-    // a latency-bound call compacts per level (k_compact_local: level-local lists, every wave's prefix in one memory round trip)
-    const bool localCand = small && localLists;
-    submitLocalCand = localCand;
-    QP.levelLocal = localCand ? 1 : 0;
-    {
-      if (prof) HIP_TRY(hipEventRecord(ev[0][0], st));
-      if (launch_pyramid(P, nframes, st, coneOk && small ? &cone : (tailOk && !small ? &coneTail : nullptr))) { set_err("cannot configure the pyramid kernel"); return ORBFE_ERR_HIP; }
-      // the dominant kernel is timed in every batch (bench.py roofline); a latency-bound one- or two-frame call does
-      // without the two markers (each costs a few microseconds of dependent-launch gap) unless profiling is on
-      const bool timeFast = prof || !small;
-      fastTimed = timeFast;
-      if (timeFast) HIP_TRY(hipEventRecord(ev[0][1], st));
-      launch_fast(P, nframes, st);
-      if (timeFast) HIP_TRY(hipEventRecord(ev[0][2], st));
-      if (localCand) launch_compact_local(P, nframes, st, 0, nlevels);
-      else launch_compact(P, nframes, st);
-      if (prof) HIP_TRY(hipEventRecord(ev[0][3], st));
-      if (prof) HIP_TRY(hipEventRecord(evQt[0], st));
-      if (launch_quadtree(QP, nframes, st, qtLds)) { set_err("cannot configure the quadtree kernel"); return ORBFE_ERR_HIP; }
-      if (prof) HIP_TRY(hipEventRecord(evQt[1], st));
-      if (prof) HIP_TRY(hipEventRecord(ev[0][4], st));
-      launch_describe_slots(P, d_sel.p, nframes * selPerFrame, angOut, descOut, d_selCount.p, selPerFrame, selOff, st, four,
-                            kernelOut ? h_angle.p : nullptr, kernelOut ? h_desc.p : nullptr);
-      if (prof) HIP_TRY(hipEventRecord(ev[0][5], st));
-      HIP_TRY(hipGetLastError());
+    QP.levelLocal = R.localCand ? 1 : 0;
+    // a one- or two-frame call is latency-bound and alone on the chip: the quadtree keeps its candidates in LDS
+    const int qtLds = R.small ? qtLdsBudget : 0;
+    if (R.prof) HIP_TRY(hipEventRecord(evQt[0], st));
+    if (launch_quadtree(QP, nframes, st, qtLds)) { set_err("cannot configure the quadtree kernel"); return ORBFE_ERR_HIP; }
+    if (R.prof) HIP_TRY(hipEventRecord(evQt[1], st));
+    return ORBFE_OK;
+  }
+
+  // Selection, on the host: wait for the front, levelStart and the candidates to the host, DistributeOctTree (quadtree.h,
+  // ORBextractor.cc:876-877) per (frame, level) on the pool, straight into the level's slots of the page-locked arena -- SelKp as
+  // k_quadtree3 encodes it, the count into selCount -- and both uploaded where the kernels behind read them.
+  int selectOnHost(int nframes, hipStream_t st) {
+    const double ta = now_ms();
+    int rc;
+    HIP_TRY(hipMemcpyAsync(h_levelStart.p, d_levelStart.p, sizeof(uint32_t) * (kMaxLevels + 1) * nframes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t need = 0;
+    for (int f = 0; f < nframes; f++) need = std::max(need, h_levelStart.p[(size_t)f * (kMaxLevels + 1) + nlevels]);
+    if (need > candHostCap) {
+      candHostCap = (size_t)need + need / 4 + 1024;
+      if ((rc = h_cand.ensure(candHostCap * (size_t)batchCap))) return rc;
     }
-    const int nslots = nframes * selPerFrame;
-    submitCam = camActive;
-    submitEqui = camEqui;
-    if (camActive) {   // mvKeysUn of every live slot (Frame.cc:284-319), where the other results go
-      UndistortSlots S{};
-      S.in = nullptr; S.sel = d_sel.p; S.selCount = d_selCount.p;
-      S.out = zeroCopy ? h_xyUn.p : d_xyUn.p;
-      S.n = nslots; S.selPerFrame = selPerFrame; S.nlevels = nlevels;
-      for (int l = 0; l <= nlevels; l++) S.selOff[l] = selOff[l];
-      for (int l = 0; l < nlevels; l++) S.sf[l] = sf[l];
-      if (camEqui) {
-        HIP_TRY(hipMemsetAsync(d_undec.p, 0, sizeof(uint32_t) * (1 + kUndecidedCap), st));
-        EquidistantArgs E{};
-        static_cast<UndistortSlots&>(E) = S;
-        E.cam = camE; E.undecided = d_undec.p; E.flags = nullptr;
-        launch_undistort_equidistant(E, st);
-        // (the counter and the list are always written in HBM; the routes that skip the arena copy fetch them on their own)
-        if (zeroCopy || kernelOut) HIP_TRY(hipMemcpyAsync(h_undec.p, d_undec.p, sizeof(uint32_t) * (1 + kUndecidedCap), hipMemcpyDeviceToHost, st));
-      } else {
-        UndistortArgs U{};
-        static_cast<UndistortSlots&>(U) = S;
-        U.cam = cam;
-        launch_undistort(U, st);
+    for (int f = 0; f < nframes; f++) {
+      const size_t n = h_levelStart.p[(size_t)f * (kMaxLevels + 1) + nlevels];
+      if (n) HIP_TRY(hipMemcpyAsync(h_cand.p + candHostCap * f, d_cand.p + (size_t)P.candCap * f, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!pool) {
+      pool.reset(new HostPool(hostThreads));
+      workers.resize(hostThreads);
+    }
+    pool->parallelFor(nframes * nlevels, [&](int task, int wid) {
+      const int f = task / nlevels, l = task % nlevels;
+      uint32_t& count = h_selCount.p[(size_t)f * kMaxLevels + l];
+      count = 0;
+      const uint32_t* ls = h_levelStart.p + (size_t)f * (kMaxLevels + 1);
+      const int n = (int)(ls[l + 1] - ls[l]);
+      if (n <= 0) return;
+      Worker& w = workers[wid];
+      const uint32_t* cd = h_cand.p + candHostCap * f + ls[l];
+      w.qx.resize(n); w.qy.resize(n); w.qs.resize(n);
+      for (int i = 0; i < n; i++) {
+        const uint32_t v = cd[i];
+        w.qx[i] = (int16_t)((int)(v & 0xfff) - kBorder);
+        w.qy[i] = (int16_t)((int)((v >> 12) & 0xfff) - kBorder);
+        w.qs[i] = (uint8_t)(v >> 24);
       }
-      HIP_TRY(hipGetLastError());
-      if (kernelOut) HIP_TRY(hipMemcpyAsync(h_xyUn.p, d_xyUn.p, 2 * sizeof(float) * (size_t)nslots, hipMemcpyDeviceToHost, st));
-    }
-    pendingBow = false;
-    if (voc) {
-      if ((rc = d_bow.ensure(nslots)) || (rc = h_bow.ensure(nslots))) return rc;
-      if ((rc = bow_launch_descend(voc, d_desc.p, nslots, vocLevelsup, d_bow.p, st))) return rc;   // dead slots descend too
-      HIP_TRY(hipMemcpyAsync(h_bow.p, d_bow.p, sizeof(uint2) * nslots, hipMemcpyDeviceToHost, st));
-      pendingBow = true;
-    }
-    pendingMatched = false;
-    submitChain = nullptr;
-    if (ms && ms->chain) {
-      submitChain = ms->chain;
-      submitMs = *ms;
-      {   // a carry written under another model, or under another equidistant camera, is no predecessor
-        orbfe_sfi_chain& c = *ms->chain;
-        if (c.equi != camEqui || (camEqui && memcmp(c.eqCam, camF, sizeof camF))) {
-          if (c.seq > 0) c.restart = true;
-          c.eqPrevValid = c.eqCarryStale = false;
+      const LevelGeom& L = P.lv[l];
+      w.qt.distribute(w.qx.data(), w.qy.data(), w.qs.data(), n, kBorder, L.w - kBorder, kBorder, L.h - kBorder, nfeat[l], w.qsel);
+      SelKp* out = h_sel.p + (size_t)f * selPerFrame + selOff[l];
+      const int room = selOff[l + 1] - selOff[l];
+      count = (uint32_t)w.qsel.size();   // (more than the level's slots: reported below, nothing written past them)
+      for (int i = 0; i < (int)w.qsel.size() && i < room; i++) {
+        const uint32_t v = cd[w.qsel[i]];
+        out[i].xy = (v & 0xfff) | (((v >> 12) & 0xfff) << 16);
+        out[i].lf = (uint32_t)l | ((uint32_t)f << 8) | ((v >> 24) << 24);
+      }
+    });
+    for (int f = 0; f < nframes; f++)
+      for (int l = 0; l < nlevels; l++)
+        if ((int)h_selCount.p[(size_t)f * kMaxLevels + l] > selOff[l + 1] - selOff[l]) {
+          set_err("frame %d level %d: the quadtree returned %u keypoints for %d slots", f, l, h_selCount.p[(size_t)f * kMaxLevels + l], selOff[l + 1] - selOff[l]);
+          return ORBFE_ERR_OVERFLOW;
         }
-        c.equi = camEqui;
-        memcpy(c.eqCam, camF, sizeof camF);
-      }
-      submitHasPred = !(ms->chain->seq == 0 || ms->chain->isolated || ms->chain->restart);
-      // SearchForInitialization of every frame against its predecessor, on the data that is already in HBM
-      orbfe_sfi_chain& ch = *ms->chain;
-      const int n0cap = selOff[1] - selOff[0];
-      if (ch.n0cap != n0cap || ch.device != device) { set_err("match chain belongs to a different extractor configuration"); return ORBFE_ERR_INVALID; }
-      if ((rc = d_sfiOrder.ensure((size_t)batchCap * n0cap))) return rc;
-      if ((rc = d_sfiOrderCount.ensure(batchCap))) return rc;
-      if ((rc = d_sfiPool.ensure((size_t)batchCap * n0cap * n0cap))) return rc;
-      if ((rc = d_sfiPcount.ensure((size_t)batchCap * n0cap))) return rc;
-      SfiParams SP{};
-      SP.sel = d_sel.p; SP.angle = d_angle.p; SP.desc = d_desc.p; SP.selCount = d_selCount.p;
-      SP.selPerFrame = selPerFrame; SP.n0cap = n0cap; SP.frameBase = 0;
-      const int prev = (int)((ch.seq + 1) & 1), cur = (int)(ch.seq & 1);   // buffer written by the previous / this batch
-      SP.carrySel = ch.sel[prev].p; SP.carryAngle = ch.angle[prev].p; SP.carryDesc = ch.desc[prev].p;
-      const bool iso = ch.isolated;   // every batch stands alone: no carry in, no carry out
-      if (camActive) {
-        for (int i = 0; i < 2; i++)
-          if ((rc = ch.xyUn[i].ensure(2 * (size_t)n0cap))) return rc;
-      }
-      if (ch.camera != camActive && ch.seq > 0) ch.restart = true;   // the carry was written on the other kind of coordinates
-      ch.camera = camActive;
-      SP.xyUn = camActive ? d_xyUn.p : nullptr;
-      SP.carryXyUn = camActive ? ch.xyUn[prev].p : nullptr;
-      // (after a restart the carry is not read, but the batch still waits for the one before: it overwrites the buffer that one reads)
-      SP.carryCount = ch.count.p + ((ch.seq == 0 || iso || ch.restart) ? 2 : prev);
-      ch.restart = false;
-      SP.minX = ms->bounds[0]; SP.minY = ms->bounds[2];
-      SP.invW = static_cast<float>(64) / static_cast<float>(ms->bounds[1] - ms->bounds[0]);   // Frame.cc:98
-      SP.invH = static_cast<float>(48) / static_cast<float>(ms->bounds[3] - ms->bounds[2]);   // Frame.cc:99
-      SP.window = (float)ms->window; SP.nnratio = ms->nnratio; SP.checkOri = ms->checkOri;
-      SP.order = d_sfiOrder.p; SP.orderCount = d_sfiOrderCount.p; SP.pool = d_sfiPool.p; SP.pcount = d_sfiPcount.p;
-      SP.matches12 = kernelOut ? h_m12.p : d_m12.p; SP.nmatches = kernelOut ? h_nm.p : d_nm.p;
-      if (ch.seq > 0 && !iso) HIP_TRY(hipStreamWaitEvent(st, ch.ready[prev], 0));
-      launch_sfi(SP, nframes, st);
-      HIP_TRY(hipGetLastError());
-      if (!iso) {
-        // hand the last frame's level-0 data to the next batch
-        launch_sfi_carry(SP, nframes - 1, ch.sel[cur].p, ch.angle[cur].p, ch.desc[cur].p, ch.count.p + cur, camActive ? ch.xyUn[cur].p : nullptr, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ch.ready[cur], st));
-      }
-      ch.seq++;
-      pendingMatched = true;
+    HIP_TRY(hipMemcpyAsync(d_selCount.p, h_selCount.p, sizeof(uint32_t) * kMaxLevels * nframes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_sel.p, h_sel.p, sizeof(SelKp) * (size_t)nframes * selPerFrame, hipMemcpyHostToDevice, st));
+    hostSelMs = now_ms() - ta;
+    return ORBFE_OK;
+  }
+
+  // Orientation, blur and rBRIEF of every live slot; a one- or two-frame call is latency-bound: four waves share a keypoint.
+  int describe(int nframes, const Route& R, hipStream_t st) {
+    if (R.prof) HIP_TRY(hipEventRecord(ev[4], st));
+    launch_describe_slots(P, d_sel.p, nframes * selPerFrame, R.zeroCopy ? h_angle.p : d_angle.p, R.zeroCopy ? h_desc.p : d_desc.p, d_selCount.p,
+                          selPerFrame, selOff, st, describe4 && R.small, R.kernelOut ? h_angle.p : nullptr, R.kernelOut ? h_desc.p : nullptr);
+    if (R.prof) HIP_TRY(hipEventRecord(ev[5], st));
+    HIP_TRY(hipGetLastError());
+    return ORBFE_OK;
+  }
+
+  // mvKeysUn of every live slot (Frame.cc:284-319), where the other results go.
+  int undistortSlots(int nframes, const Route& R, hipStream_t st) {
+    const int nslots = nframes * selPerFrame;
+    const bool zeroCopy = R.zeroCopy, kernelOut = R.kernelOut;
+    UndistortSlots S{};
+    S.in = nullptr; S.sel = d_sel.p; S.selCount = d_selCount.p;
+    S.out = zeroCopy ? h_xyUn.p : d_xyUn.p;
+    S.n = nslots; S.selPerFrame = selPerFrame; S.nlevels = nlevels;
+    for (int l = 0; l <= nlevels; l++) S.selOff[l] = selOff[l];
+    for (int l = 0; l < nlevels; l++) S.sf[l] = sf[l];
+    if (camEqui) {
+      HIP_TRY(hipMemsetAsync(d_undec.p, 0, sizeof(uint32_t) * (1 + kUndecidedCap), st));
+      EquidistantArgs E{};
+      static_cast<UndistortSlots&>(E) = S;
+      E.cam = camE; E.undecided = d_undec.p; E.flags = nullptr;
+      launch_undistort_equidistant(E, st);
+      // (the counter and the list are always written in HBM; the routes that skip the arena copy fetch them on their own)
+      if (zeroCopy || kernelOut) HIP_TRY(hipMemcpyAsync(h_undec.p, d_undec.p, sizeof(uint32_t) * (1 + kUndecidedCap), hipMemcpyDeviceToHost, st));
+    } else {
+      UndistortArgs U{};
+      static_cast<UndistortSlots&>(U) = S;
+      U.cam = cam;
+      launch_undistort(U, st);
     }
-    if (!zeroCopy && !kernelOut) HIP_TRY(hipMemcpyAsync(h_outArena.p, d_outArena.p, outArenaBytes, hipMemcpyDeviceToHost, st));   // all results, one copy
-    submitProfiled = prof;
-    tSubmit0 = t0;
-    tSubmit1 = now_ms();
-    pendingFrames = nframes;
+    HIP_TRY(hipGetLastError());
+    if (kernelOut) HIP_TRY(hipMemcpyAsync(h_xyUn.p, d_xyUn.p, 2 * sizeof(float) * (size_t)nslots, hipMemcpyDeviceToHost, st));
+    return ORBFE_OK;
+  }
+
+  // Frame::ComputeBoW behind k_describe: the descent on the descriptors while they are still in HBM.
+  int descendVocabulary(int nframes, hipStream_t st) {
+    const int nslots = nframes * selPerFrame;
+    int rc;
+    if ((rc = d_bow.ensure(nslots)) || (rc = h_bow.ensure(nslots))) return rc;
+    if ((rc = bow_launch_descend(voc, d_desc.p, nslots, vocLevelsup, d_bow.p, st))) return rc;   // dead slots descend too
+    HIP_TRY(hipMemcpyAsync(h_bow.p, d_bow.p, sizeof(uint2) * nslots, hipMemcpyDeviceToHost, st));
+    pendingBow = true;
+    return ORBFE_OK;
+  }
+
+  // The match chain.  GPU-selected batch: SearchForInitialization of every frame against its predecessor on the data that is already
+  // in HBM (k_sfi_*, sized by n0cap), and the last frame's level-0 data handed to the next batch.  Host-selected batch: no chain
+  // kernel (k_sfi has not run beyond the GPU quadtree's limits); the chain's rules are read here, in submit order, and the searches
+  // run when the batch is collected (matchOnHost).  The two kinds keep a carry each.
+  int matchChain(const MatchSpec& spec, int nframes, const Route& R, hipStream_t st) {
+    const MatchSpec* ms = &spec;
+    const bool kernelOut = R.kernelOut;
+    int rc;
+    submitChain = ms->chain;
+    submitMs = *ms;
+    orbfe_sfi_chain& ch = *ms->chain;
+    // a carry written under another model, or under another equidistant camera, is no predecessor
+    const bool otherModel = ch.equi != camEqui || (camEqui && memcmp(ch.eqCam, camF, sizeof camF));
+    if (R.hostSel) {
+      // (the carry holds the coordinates of the camera it was written under: a batch of the other kind has no predecessor either)
+      submitHasPred = !(ch.isolated || ch.restart || otherModel || ch.camera != camActive);
+      ch.camera = camActive;
+      ch.equi = camEqui;
+      memcpy(ch.eqCam, camF, sizeof camF);
+      ch.restart = false;
+      pendingMatched = true;
+      return ORBFE_OK;
+    }
+    if (otherModel) {
+      if (ch.seq > 0) ch.restart = true;
+      ch.eqPrevValid = ch.eqCarryStale = false;
+    }
+    ch.equi = camEqui;
+    memcpy(ch.eqCam, camF, sizeof camF);
+    submitHasPred = !(ch.seq == 0 || ch.isolated || ch.restart);
+    if (ch.n0cap != n0cap || ch.device != device) { set_err("match chain belongs to a different extractor configuration"); return ORBFE_ERR_INVALID; }
+    if ((rc = d_sfiOrder.ensure((size_t)batchCap * n0cap))) return rc;
+    if ((rc = d_sfiOrderCount.ensure(batchCap))) return rc;
+    if ((rc = d_sfiPool.ensure((size_t)batchCap * n0cap * n0cap))) return rc;
+    if ((rc = d_sfiPcount.ensure((size_t)batchCap * n0cap))) return rc;
+    SfiParams SP{};
+    SP.sel = d_sel.p; SP.angle = d_angle.p; SP.desc = d_desc.p; SP.selCount = d_selCount.p;
+    SP.selPerFrame = selPerFrame; SP.n0cap = n0cap; SP.frameBase = 0;
+    const int prev = (int)((ch.seq + 1) & 1), cur = (int)(ch.seq & 1);   // buffer written by the previous / this batch
+    SP.carrySel = ch.sel[prev].p; SP.carryAngle = ch.angle[prev].p; SP.carryDesc = ch.desc[prev].p;
+    const bool iso = ch.isolated;   // every batch stands alone: no carry in, no carry out
+    if (camActive) {
+      for (int i = 0; i < 2; i++)
+        if ((rc = ch.xyUn[i].ensure(2 * (size_t)n0cap))) return rc;
+    }
+    if (ch.camera != camActive && ch.seq > 0) ch.restart = true;   // the carry was written on the other kind of coordinates
+    ch.camera = camActive;
+    SP.xyUn = camActive ? d_xyUn.p : nullptr;
+    SP.carryXyUn = camActive ? ch.xyUn[prev].p : nullptr;
+    // (after a restart the carry is not read, but the batch still waits for the one before: it overwrites the buffer that one reads)
+    SP.carryCount = ch.count.p + ((ch.seq == 0 || iso || ch.restart) ? 2 : prev);
+    ch.restart = false;
+    SP.minX = ms->bounds[0]; SP.minY = ms->bounds[2];
+    SP.invW = static_cast<float>(64) / static_cast<float>(ms->bounds[1] - ms->bounds[0]);   // Frame.cc:98
+    SP.invH = static_cast<float>(48) / static_cast<float>(ms->bounds[3] - ms->bounds[2]);   // Frame.cc:99
+    SP.window = (float)ms->window; SP.nnratio = ms->nnratio; SP.checkOri = ms->checkOri;
+    SP.order = d_sfiOrder.p; SP.orderCount = d_sfiOrderCount.p; SP.pool = d_sfiPool.p; SP.pcount = d_sfiPcount.p;
+    SP.matches12 = kernelOut ? h_m12.p : d_m12.p; SP.nmatches = kernelOut ? h_nm.p : d_nm.p;
+    if (ch.seq > 0 && !iso) HIP_TRY(hipStreamWaitEvent(st, ch.ready[prev], 0));
+    launch_sfi(SP, nframes, st);
+    HIP_TRY(hipGetLastError());
+    if (!iso) {
+      // hand the last frame's level-0 data to the next batch
+      launch_sfi_carry(SP, nframes - 1, ch.sel[cur].p, ch.angle[cur].p, ch.desc[cur].p, ch.count.p + cur, camActive ? ch.xyUn[cur].p : nullptr, st);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(ch.ready[cur], st));
+    }
+    ch.seq++;
+    pendingMatched = true;
     return ORBFE_OK;
   }
 
@@ -1099,7 +1229,7 @@ struct orbfe_extractor {
   int waitOnly() {
     if (!pendingFrames) return ORBFE_OK;
     HIP_TRY(hipSetDevice(device));
-    hipStream_t st = streams[0];
+    hipStream_t st = stream;
     if (pollWaitUs > 0) {
       hipError_t q;
       while ((q = hipStreamQuery(st)) == hipErrorNotReady) usleep((useconds_t)pollWaitUs);
@@ -1110,13 +1240,13 @@ struct orbfe_extractor {
   }
 
   // xy_un ([nframes][cap][2], optional): mvKeysUn -- from the arena with a distorting camera, else the keypoints' own coordinates
-  int waitGpuQt(OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int32_t* matches12 = nullptr,
-                int* nmatches = nullptr, float* xy_un = nullptr) {
+  int collect(OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int32_t* matches12 = nullptr,
+              int* nmatches = nullptr, float* xy_un = nullptr) {
     if (!pendingFrames) { set_err("no submitted batch to collect"); return ORBFE_ERR_INVALID; }
     HIP_TRY(hipSetDevice(device));
     const int nframes = pendingFrames;
     pendingFrames = 0;
-    hipStream_t st = streams[0];
+    hipStream_t st = stream;
     const double t0 = tSubmit0, t1 = tSubmit1;
     const double t1b = now_ms();
     if (pollWaitUs > 0) {   // sleep-poll instead of the runtime's spinning wait (pipelined callers: the wake-up delay is hidden)
@@ -1128,12 +1258,12 @@ struct orbfe_extractor {
     const double t2 = now_ms();
     {
       float ms = 0;
-      if (fastTimed && hipEventElapsedTime(&ms, ev[0][1], ev[0][2]) == hipSuccess) kernMs[1] += ms;
+      if (fastTimed && hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) kernMs[1] += ms;
       if (submitProfiled) {
-        if (hipEventElapsedTime(&ms, ev[0][0], ev[0][1]) == hipSuccess) kernMs[0] += ms;
-        if (hipEventElapsedTime(&ms, ev[0][2], ev[0][3]) == hipSuccess) kernMs[2] += ms;
-        if (hipEventElapsedTime(&ms, ev[0][4], ev[0][5]) == hipSuccess) kernMs[3] += ms;
-        if (hipEventElapsedTime(&ms, evQt[0], evQt[1]) == hipSuccess) kernMs[4] += ms;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) kernMs[0] += ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) kernMs[2] += ms;
+        if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess) kernMs[3] += ms;
+        if (!submitHostSel && hipEventElapsedTime(&ms, evQt[0], evQt[1]) == hipSuccess) kernMs[4] += ms;
       }
       if (fastTimed) {
         kernBatches++;
@@ -1143,7 +1273,7 @@ struct orbfe_extractor {
     int status = ORBFE_OK;
     if (submitEqui && (status = settleEquidistant(nframes))) return status;
     std::vector<float> xyOwn;
-    if (submitEqui && pendingMatched && !xy_un) {   // the re-match below needs mvKeysUn of the assembled keypoints
+    if (pendingMatched && !xy_un && (submitEqui || (submitHostSel && submitCam))) {   // the host searches below need mvKeysUn of the assembled keypoints
       xyOwn.resize((size_t)nframes * cap * 2);
       xy_un = xyOwn.data();
     }
@@ -1188,245 +1318,38 @@ struct orbfe_extractor {
         status = ORBFE_ERR_OVERFLOW;
       }
     }
+    const bool gpuMatched = pendingMatched && !submitHostSel;   // the arena holds k_sfi's rows ([nframes][n0cap])
     if (matches12 && nmatches) {
-      const int n0cap = selOff[1] - selOff[0];
       for (int f = 0; f < nframes; f++) {
         int32_t* row = matches12 + (size_t)f * cap;
         const int m = std::min(cap, n0cap);
-        if (pendingMatched) {
+        if (gpuMatched) {
           memcpy(row, h_m12.p + (size_t)f * n0cap, sizeof(int32_t) * m);
           nmatches[f] = h_nm.p[f];
         } else {
           nmatches[f] = 0;
         }
-        for (int i = pendingMatched ? m : 0; i < cap; i++) row[i] = -1;
+        for (int i = gpuMatched ? m : 0; i < cap; i++) row[i] = -1;
       }
     }
-    if (submitEqui && pendingMatched && status == ORBFE_OK) {
+    if (pendingMatched && submitHostSel) {
+      const int rc = status == ORBFE_OK ? matchOnHost(nframes, kps, desc, cap, n_out, xy_un, matches12, nmatches) : ORBFE_OK;
+      if (status != ORBFE_OK) submitChain->hostPrevValid = false;   // (truncated frames are nobody's predecessor)
+      if (rc) return rc;
+    } else if (submitEqui && pendingMatched && status == ORBFE_OK) {
       const int rc = rematchEquidistant(nframes, kps, desc, cap, n_out, xy_un, matches12, nmatches);
       if (rc) return rc;
     }
     const double t3 = now_ms();
-    stageMs[0] = (float)(t1 - t0);   // enqueue
+    stageMs[0] = (float)(t1 - t0);   // enqueue (a host-selected batch: with the selection inside)
     stageMs[1] = (float)(t2 - t1b);  // GPU wait inside the collect call
-    stageMs[2] = 0;
+    stageMs[2] = submitHostSel ? (float)hostSelMs : 0;   // host selection
     stageMs[3] = (float)(t3 - t2);   // output assembly
     stageMs[4] = (float)(t3 - t0);
     lastFrames = nframes;
-    lastGpuQt = true;
     lastZeroCopy = submitZeroCopy;
     lastLocalCand = submitLocalCand;
     lastCam = submitCam;
-    return status;
-  }
-
-  // One batch = up to kMaxSub sub-batches, each on its own HIP stream, software-pipelined so that the
-  // host-side work of sub-batch s (candidate D2H, quadtrees) overlaps the GPU work of the others:
-  //   all s : [upload] pyramid -> FAST -> compaction -> D2H level offsets        (enqueued up front)
-  //   per s : wait -> D2H candidates -> host quadtrees -> H2D selection -> describe -> D2H (async)
-  //   all s : wait, assemble cv::KeyPoint-compatible outputs.
-  int run(int nframes, const uint8_t* const* gray, bool onDevice, int r, int c, size_t stride, OrbfeKeyPoint* kps,
-          uint8_t* desc, int cap, int* n_out, float* xy_un = nullptr) {
-    if (pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(device));
-    int rc;
-    if ((rc = setGeometry(r, c))) return rc;
-    if ((rc = setBatch(nframes, !onDevice, stride))) return rc;
-    const double t0 = now_ms();
-    if (!pool) {
-      pool.reset(new HostPool(hostThreads));
-      workers.resize(hostThreads);
-    }
-    if (inChannels() != 1) { set_err("colour input needs the GPU quadtree path (unset ORBFE_HOST_QUADTREE)"); return ORBFE_ERR_INVALID; }
-    const int nsub = std::min(nframes, std::min(kMaxSub, std::max(1, subBatches)));
-    const int maxKp = kpPerFrameCap;
-    if ((rc = ensureSubStreams(nsub))) return rc;
-    int subF0[kMaxSub + 1];
-    for (int s = 0; s <= nsub; s++) subF0[s] = (int)((long long)nframes * s / nsub);
-
-    devAt.resize(nframes);
-    for (int f = 0; f < nframes; f++) {
-      if (!gray[f]) { set_err("frame %d is NULL", f); return ORBFE_ERR_INVALID; }
-      // per-frame copies on this path (sub-batches upload on their own streams): frame f lands in slot f
-      h_frame0.p[f] = onDevice ? gray[f] : d_in.p + (size_t)inPitch * rows * f;
-    }
-    P.stride0 = onDevice ? (long long)stride : inPitch;
-    P.gaussVariant = gaussVariant;   // (the host-quadtree route describes with launch_describe: same kernel, same variant)
-    P.frame0 = d_frame0.p;
-    HIP_TRY(hipMemcpyAsync(d_frame0.p, h_frame0.p, sizeof(void*) * nframes, hipMemcpyHostToDevice, streams[0]));
-    HIP_TRY(hipEventRecord(evFrame0, streams[0]));
-    // ---- stage 1 for every sub-batch -----------------------------------------------------
-    for (int s = 0; s < nsub; s++) {
-      hipStream_t st = streams[s];
-      const int f0 = subF0[s], nf = subF0[s + 1] - f0;
-      if (s) HIP_TRY(hipStreamWaitEvent(st, evFrame0, 0));
-      if (!onDevice && (rc = uploadSlots(f0, nf, gray, stride, r, c, st))) return rc;
-      PyramidParams Q = P;
-      Q.frameBase = f0;
-      HIP_TRY(hipEventRecord(ev[s][0], st));
-      if (launch_pyramid(Q, nf, st, coneOk && nf <= coneMaxFrames ? &cone : nullptr)) { set_err("cannot configure the pyramid kernel"); return ORBFE_ERR_HIP; }
-      HIP_TRY(hipEventRecord(ev[s][1], st));
-      launch_fast(Q, nf, st);
-      HIP_TRY(hipEventRecord(ev[s][2], st));
-      launch_compact(Q, nf, st);
-      HIP_TRY(hipEventRecord(ev[s][3], st));
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(h_levelStart.p + (size_t)f0 * (kMaxLevels + 1), d_levelStart.p + (size_t)f0 * (kMaxLevels + 1),
-                             sizeof(uint32_t) * (kMaxLevels + 1) * nf, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipEventRecord(evS1[s], st));
-    }
-    // ---- per sub-batch: candidates to the host, quadtrees, stage 2 ----------------------------
-    double tHostQt = 0, tWait = 0;
-    meta.assign((size_t)nframes * maxKp, Meta{});
-    frameKpCount.assign(nframes, 0);
-    frameKpBase.assign(nframes, 0);
-    if ((int)taskOut.size() < nframes * nlevels) taskOut.resize((size_t)nframes * nlevels);
-    for (int s = 0; s < nsub; s++) {
-      hipStream_t st = streams[s];
-      const int f0 = subF0[s], nf = subF0[s + 1] - f0;
-      double ta = now_ms();
-      HIP_TRY(hipEventSynchronize(evS1[s]));
-      // candidates: per-frame host regions of candHostCap entries (grown on demand)
-      uint32_t need = 0;
-      for (int f = f0; f < f0 + nf; f++) need = std::max(need, h_levelStart.p[(size_t)f * (kMaxLevels + 1) + nlevels]);
-      if (need > candHostCap) {
-        for (int q = 0; q < nsub; q++) HIP_TRY(hipStreamSynchronize(streams[q]));  // nobody may be writing h_cand
-        // sub-batches < s are already consumed, later ones have not copied yet: nothing to preserve
-        candHostCap = (size_t)need + need / 4 + 1024;
-        if ((rc = h_cand.ensure(candHostCap * (size_t)batchCap))) return rc;
-      }
-      for (int f = f0; f < f0 + nf; f++) {
-        const size_t n = h_levelStart.p[(size_t)f * (kMaxLevels + 1) + nlevels];
-        if (n)
-          HIP_TRY(hipMemcpyAsync(h_cand.p + candHostCap * f, d_cand.p + (size_t)P.candCap * f, n * sizeof(uint32_t),
-                                 hipMemcpyDeviceToHost, st));
-      }
-      HIP_TRY(hipStreamSynchronize(st));
-      double tb = now_ms();
-      tWait += tb - ta;
-      // host quadtree per (frame, level): DistributeOctTree, ORBextractor.cc:876-877
-      pool->parallelFor(nf * nlevels, [&](int task, int wid) {
-        const int f = f0 + task / nlevels, l = task % nlevels;
-        std::vector<Meta>& out = taskOut[(size_t)f * nlevels + l];
-        out.clear();
-        const uint32_t* ls = h_levelStart.p + (size_t)f * (kMaxLevels + 1);
-        const int n = (int)(ls[l + 1] - ls[l]);
-        if (n <= 0) return;
-        Worker& w = workers[wid];
-        const uint32_t* cd = h_cand.p + candHostCap * f + ls[l];
-        w.qx.resize(n); w.qy.resize(n); w.qs.resize(n);
-        for (int i = 0; i < n; i++) {
-          const uint32_t v = cd[i];
-          w.qx[i] = (int16_t)((int)(v & 0xfff) - kBorder);
-          w.qy[i] = (int16_t)((int)((v >> 12) & 0xfff) - kBorder);
-          w.qs[i] = (uint8_t)(v >> 24);
-        }
-        const LevelGeom& L = P.lv[l];
-        w.qt.distribute(w.qx.data(), w.qy.data(), w.qs.data(), n, kBorder, L.w - kBorder, kBorder, L.h - kBorder,
-                        nfeat[l], w.qsel);
-        out.reserve(w.qsel.size());
-        for (int k : w.qsel) {
-          Meta m;
-          m.x = (int16_t)(w.qx[k] + kBorder);
-          m.y = (int16_t)(w.qy[k] + kBorder);
-          m.score = w.qs[k];
-          m.level = (uint8_t)l;
-          out.push_back(m);
-        }
-      });
-      // selection of this sub-batch, packed from entry f0*maxKp
-      const int selBase = f0 * maxKp;
-      int nsel = 0;
-      for (int f = f0; f < f0 + nf; f++) {
-        frameKpBase[f] = selBase + nsel;
-        for (int l = 0; l < nlevels; l++) {
-          for (const Meta& m : taskOut[(size_t)f * nlevels + l]) {
-            meta[selBase + nsel] = m;
-            SelKp sk;
-            sk.xy = (uint32_t)m.x | ((uint32_t)m.y << 16);
-            sk.lf = (uint32_t)l | ((uint32_t)f << 8);
-            h_sel.p[selBase + nsel++] = sk;
-          }
-        }
-        frameKpCount[f] = selBase + nsel - frameKpBase[f];
-      }
-      subSel[s] = nsel;
-      tHostQt += now_ms() - tb;
-      // stage 2: orientation + blur + rBRIEF for this sub-batch (asynchronous)
-      if (nsel > 0) {
-        HIP_TRY(hipMemcpyAsync(d_sel.p + selBase, h_sel.p + selBase, sizeof(SelKp) * nsel, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ev[s][4], st));
-        launch_describe(P, d_sel.p + selBase, nsel, d_angle.p + selBase, d_desc.p + (size_t)selBase * 32, st);
-        HIP_TRY(hipEventRecord(ev[s][5], st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_angle.p + selBase, d_angle.p + selBase, sizeof(float) * nsel, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_desc.p + (size_t)selBase * 32, d_desc.p + (size_t)selBase * 32, (size_t)32 * nsel,
-                               hipMemcpyDeviceToHost, st));
-      }
-    }
-    const double t3 = now_ms();
-    for (int s = 0; s < nsub; s++) HIP_TRY(hipStreamSynchronize(streams[s]));
-    const double t4 = now_ms();
-    for (int s = 0; s < nsub; s++) {  // per-kernel GPU time (HIP events on the launch streams)
-      float ms = 0;
-      for (int i = 0; i < 3; i++)
-        if (hipEventElapsedTime(&ms, ev[s][i], ev[s][i + 1]) == hipSuccess) kernMs[i] += ms;
-      if (subSel[s] > 0 && hipEventElapsedTime(&ms, ev[s][4], ev[s][5]) == hipSuccess) kernMs[3] += ms;
-      kernBatches++;
-    }
-    kernFrames += nframes;
-    // ---- assemble cv::KeyPoint-compatible outputs (ORBextractor.cc:879-889, 959-967) --------
-    int status = ORBFE_OK;
-    for (int f = 0; f < nframes; f++) {
-      const int b = frameKpBase[f], n = frameKpCount[f];
-      n_out[f] = n;
-      if (n > cap) {
-        set_err("frame %d produced %d keypoints, cap is %d", f, n, cap);
-        status = ORBFE_ERR_OVERFLOW;
-      }
-      const int m = n < cap ? n : cap;
-      OrbfeKeyPoint* ko = kps + (size_t)f * cap;
-      for (int i = 0; i < m; i++) {
-        const Meta& mt = meta[b + i];
-        OrbfeKeyPoint kp;
-        kp.x = (float)mt.x;
-        kp.y = (float)mt.y;
-        if (mt.level != 0) {
-          const float scale = sf[mt.level];
-          kp.x *= scale;
-          kp.y *= scale;
-        }
-        kp.size = (float)(int)(31 * sf[mt.level]);
-        kp.angle = h_angle.p[b + i];
-        kp.response = (float)mt.score;
-        kp.octave = mt.level;
-        kp.class_id = -1;
-        ko[i] = kp;
-      }
-      if (m > 0) memcpy(desc + (size_t)f * cap * 32, h_desc.p + (size_t)b * 32, (size_t)m * 32);
-    }
-    if (xy_un && !camActive) {
-      for (int f = 0; f < nframes; f++)
-        for (int i = 0; i < std::min(frameKpCount[f], cap); i++) { xy_un[((size_t)f * cap + i) * 2] = kps[(size_t)f * cap + i].x; xy_un[((size_t)f * cap + i) * 2 + 1] = kps[(size_t)f * cap + i].y; }
-    } else if (xy_un) {   // mvKeysUn of the assembled keypoints: the same kernel, on one packed list of the whole batch
-      std::vector<float> pts;
-      for (int f = 0; f < nframes; f++)
-        for (int i = 0; i < std::min(frameKpCount[f], cap); i++) { pts.push_back(kps[(size_t)f * cap + i].x); pts.push_back(kps[(size_t)f * cap + i].y); }
-      if ((rc = undistortPoints(pts.data(), (int)(pts.size() / 2)))) return rc;
-      size_t q = 0;
-      for (int f = 0; f < nframes; f++)
-        for (int i = 0; i < std::min(frameKpCount[f], cap); i++, q += 2) { xy_un[((size_t)f * cap + i) * 2] = pts[q]; xy_un[((size_t)f * cap + i) * 2 + 1] = pts[q + 1]; }
-    }
-    const double t5 = now_ms();
-    stageMs[0] = (float)tWait;          // waiting for stage 1 + candidate D2H
-    stageMs[1] = (float)tHostQt;        // host quadtrees + selection packing
-    stageMs[2] = (float)(t4 - t3);      // tail wait for stage 2
-    stageMs[3] = (float)(t5 - t4);      // output assembly
-    stageMs[4] = (float)(t5 - t0);
-    lastFrames = nframes;
-    lastGpuQt = false;
-    lastLocalCand = false;
-    lastCam = false;
     return status;
   }
 };
@@ -1443,10 +1366,6 @@ int extractor_view(orbfe_extractor* h, int frame, ExtractView* out) {
   if (!h || !out) { set_err("NULL argument"); return ORBFE_ERR_INVALID; }
   if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   if (frame < 0 || frame >= h->lastFrames) { set_err("frame %d is not part of the last collected batch (%d frames)", frame, h->lastFrames); return ORBFE_ERR_INVALID; }
-  if (!h->lastGpuQt) {
-    set_err("the last batch took the host-quadtree route, whose selections are not kept per slot: build the frame with orbfe_frame_create");
-    return ORBFE_ERR_INVALID;
-  }
   const size_t base = (size_t)frame * h->selPerFrame;
   const bool z = h->lastZeroCopy;
   out->sel = (z ? h->h_sel.p : h->d_sel.p) + base;
@@ -1462,7 +1381,7 @@ int extractor_view(orbfe_extractor* h, int frame, ExtractView* out) {
     out->n += out->count[l];
   }
   out->device = h->device;
-  out->stream = (void*)h->streams[0];
+  out->stream = (void*)h->stream;
   return ORBFE_OK;
 }
 }  // namespace orbfe
@@ -1668,25 +1587,21 @@ int orbfe_extractor_create(int nfeatures, float scaleFactor, int nlevels, int in
   }
   h->nfeat[nlevels - 1] = nfeatures - sum > 0 ? nfeatures - sum : 0;
   // One HIP stream per handle.  The runtime multiplexes streams onto a few hardware queues (4 by default) and two
-  // streams on one queue serialise, so nothing is created that the chosen path does not use: the extra streams of the
-  // host-quadtree path appear on its first call (ensureSubStreams), the quadtree stream only with ORBFE_QT_STREAM=1.
+  // streams on one queue serialise, so a handle has this one and no other: every route works on it (frames of host batches
+  // additionally cross on the device's shared upload lane).
   {
-    hipError_t e = hipStreamCreateWithFlags(&h->streams[0], hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
       set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
       delete h;
       return ORBFE_ERR_HIP;
     }
   }
-  h->stream = h->streams[0];
-  bool evOk = hipEventCreate(&h->evFrame0) == hipSuccess &&
-              hipEventCreateWithFlags(&h->evUpload, hipEventDisableTiming) == hipSuccess;
-  for (auto& e : h->evS1) evOk = evOk && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-  for (auto& es : h->ev) for (auto& e : es) evOk = evOk && hipEventCreate(&e) == hipSuccess;
-  if (!evOk) { set_err("hipEventCreate failed"); delete h; return ORBFE_ERR_HIP; }
+  bool evOk = hipEventCreateWithFlags(&h->evUpload, hipEventDisableTiming) == hipSuccess;
+  for (auto& e : h->ev) evOk = evOk && hipEventCreate(&e) == hipSuccess;
   for (auto& e : h->evQt) evOk = evOk && hipEventCreate(&e) == hipSuccess;
   if (!evOk) { set_err("hipEventCreate failed"); delete h; return ORBFE_ERR_HIP; }
-  if (const char* hv = getenv("ORBFE_HOST_QUADTREE")) h->gpuQuadtree = atoi(hv) == 0;
+  if (const char* hv = getenv("ORBFE_HOST_QUADTREE")) h->forceHostQt = atoi(hv) != 0;
   if (const char* cv = getenv("ORBFE_CONE_MAX_FRAMES")) h->coneMaxFrames = atoi(cv);
   if (const char* pv = getenv("ORBFE_POLL_WAIT_US")) h->pollWaitUs = atoi(pv);
   if (const char* dw = ORBFE_EXP_ENV("ORBFE_DESCRIBE_WAVES")) h->describe4 = atoi(dw) != 1;
@@ -1700,23 +1615,14 @@ int orbfe_extractor_create(int nfeatures, float scaleFactor, int nlevels, int in
   if (const char* cv = ORBFE_EXP_ENV("ORBFE_CONE_TILE")) h->coneTile = atoi(cv) <= 0 ? 0 : std::max(8, atoi(cv));
   if (const char* pv = ORBFE_EXP_ENV("ORBFE_PROFILE_KERNELS")) h->profileKernels = atoi(pv) != 0;
   if (const char* gv = getenv("ORBFE_GAUSS_VARIANT")) h->gaussVariant = atoi(gv) == ORBFE_GAUSS_ROUNDED ? ORBFE_GAUSS_ROUNDED : ORBFE_GAUSS_ED;
-  h->selPerFrame = 0;
-  for (int l = 0; l < nlevels; l++) {
-    h->selOff[l] = h->selPerFrame;
-    // a level returns at most max(N_l + 2, 4 * roots) keypoints: the first sweep of DistributeOctTree divides every root
-    // before any size check (ORBextractor.cc:620-700), later ones overshoot N_l by at most 2; roots <= 4 on this path
-    h->selPerFrame += std::max(h->nfeat[l] + 4, 16);
-    // k_quadtree3 holds at most kQtNodeCap - 4 features per level; beyond that the handle uses the host quadtree
-    // (blocking orbfe_extract / orbfe_extract_batch only, like ORBFE_HOST_QUADTREE=1)
-    if (h->nfeat[l] + 4 > kQtNodeCap) h->gpuQuadtree = false;
-  }
-  h->selOff[nlevels] = h->selPerFrame;
+  // (the slot layout itself follows the image size: setGeometry)
+  h->n0cap = extract_level_slots(h->nfeat[0], kExtractGpuRoots);
   // host workers for the per-(frame, level) quadtrees: ORBFE_HOST_THREADS, default min(cores, 16)
   int nthreads = (int)std::thread::hardware_concurrency();
   if (nthreads > 16) nthreads = 16;
   if (const char* ev = getenv("ORBFE_HOST_THREADS")) nthreads = atoi(ev);
   if (nthreads < 1) nthreads = 1;
-  h->hostThreads = nthreads;   // the pool itself is created on first use (host-quadtree path only)
+  h->hostThreads = nthreads;   // the pool itself is created on first use (host selection only)
   *out = h;
   return ORBFE_OK;
 }
@@ -1734,16 +1640,16 @@ extern "C++" int orbfe_concurrent_streams(orbfe_extractor* const* hs, int n) {
   if (!hs || n < 1) return ORBFE_ERR_INVALID;
   HIP_TRY(hipSetDevice(hs[0]->device));
   constexpr unsigned long long kTicks = 20000;   // 200 us of the 100 MHz reference clock
-  for (int i = 0; i < n; i++) launch_spin(100, hs[i]->streams[0]);   // (code object loaded, queues created)
-  for (int i = 0; i < n; i++) HIP_TRY(hipStreamSynchronize(hs[i]->streams[0]));
+  for (int i = 0; i < n; i++) launch_spin(100, hs[i]->stream);   // (code object loaded, queues created)
+  for (int i = 0; i < n; i++) HIP_TRY(hipStreamSynchronize(hs[i]->stream));
   // do the first k streams run side by side?
   auto overlap = [&](int k, bool& yes) -> int {
     double best = 1e30;
     for (int rep = 0; rep < 3 && best >= 0.2 * 1.6; rep++) {   // (the best of up to three: a delayed wake-up of this thread must not read as a shared queue)
       const double t0 = now_ms();
-      for (int i = 0; i < k; i++) launch_spin(kTicks, hs[i]->streams[0]);
+      for (int i = 0; i < k; i++) launch_spin(kTicks, hs[i]->stream);
       HIP_TRY(hipGetLastError());
-      for (int i = 0; i < k; i++) HIP_TRY(hipStreamSynchronize(hs[i]->streams[0]));
+      for (int i = 0; i < k; i++) HIP_TRY(hipStreamSynchronize(hs[i]->stream));
       best = std::min(best, now_ms() - t0);
     }
     yes = best < 0.2 * 1.6;   // (two on one queue: >= 0.4 ms)
@@ -1762,9 +1668,8 @@ extern "C++" int orbfe_concurrent_streams(orbfe_extractor* const* hs, int n) {
       orbfe_extractor* h = hs[k];
       hipStream_t fresh = nullptr;
       HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
-      HIP_TRY(hipStreamSynchronize(h->streams[0]));
-      (void)hipStreamDestroy(h->streams[0]);
-      h->streams[0] = fresh;
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      (void)hipStreamDestroy(h->stream);
       h->stream = fresh;
       launch_spin(100, fresh);
       HIP_TRY(hipStreamSynchronize(fresh));
@@ -1815,16 +1720,13 @@ int orbfe_extractor_features_per_level(const orbfe_extractor* h, int32_t* out) {
 }
 int orbfe_extractor_max_keypoints(const orbfe_extractor* h) {
   if (!h) return 0;
-  int n = 0;   // per level max(N_l + 2, 4 * roots) with up to 4 roots (aspect ratio < 4.5); == nfeatures + 2 * nlevels when N_l >= 14
-  for (int l = 0; l < h->nlevels; l++) n += std::max(h->nfeat[l] + 2, 16);
-  return n;
+  return extract_max_keypoints(h->nlevels, h->nfeat.data());   // up to 4 roots (aspect ratio < 4.5); == nfeatures + 2 * nlevels when N_l >= 14
 }
 
 int orbfe_extractor_set_vocabulary(orbfe_extractor* h, orbfe_vocabulary* v, int levelsup) {
   if (!h) { set_err("extractor is NULL"); return ORBFE_ERR_INVALID; }
   if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   if (v && bow_device(v) != h->device) { set_err("vocabulary lives on device %d, extractor on %d", bow_device(v), h->device); return ORBFE_ERR_INVALID; }
-  if (v && !h->gpuQuadtree) { set_err("the fused bag-of-words path needs the GPU quadtree path"); return ORBFE_ERR_INVALID; }
   h->voc = v;
   h->vocLevelsup = levelsup;
   return ORBFE_OK;
@@ -1861,14 +1763,9 @@ int orbfe_extract_bow_raw(orbfe_extractor* h, int frame, uint32_t* leaf_node, ui
 
 int orbfe_extractor_max_keypoints_for_size(const orbfe_extractor* h, int rows, int cols) {
   if (!h || rows <= 0 || cols <= 0) return 0;
-  int n = 0;
-  for (int l = 0; l < h->nlevels; l++) {
-    const int w = cv_round_f((float)cols * h->isf[l]), hh = cv_round_f((float)rows * h->isf[l]);
-    int roots = hh > 2 * kBorder ? (int)roundf(static_cast<float>(w - 2 * kBorder) / (hh - 2 * kBorder)) : 0;
-    if (roots < 0) roots = 0;
-    n += std::max(h->nfeat[l] + 2, 4 * roots);
-  }
-  return n;
+  int levW[kMaxLevels], levH[kMaxLevels];
+  for (int l = 0; l < h->nlevels; l++) { levW[l] = cv_round_f((float)cols * h->isf[l]); levH[l] = cv_round_f((float)rows * h->isf[l]); }
+  return extract_max_keypoints(h->nlevels, h->nfeat.data(), levW, levH);
 }
 
 static int extract_batch_impl(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows,
@@ -1883,14 +1780,9 @@ static int extract_batch_impl(orbfe_extractor* h, int nframes, const uint8_t* co
   }
   // a blocking call between _submit and _collect would re-carve the arenas the pending batch still writes
   if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
-  {
-    HIP_TRY(hipSetDevice(h->device));
-    const int rc = h->setGeometry(rows, cols);
-    if (rc) return rc;
-  }
-  if (h->gpuQuadtree && h->geomGpuQtOk)
-    return h->runGpuQt(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out, xy_un);
-  return h->run(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, kps, desc, cap, n_out, xy_un);
+  const int rc = h->submit(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes);
+  if (rc) return rc;
+  return h->collect(kps, desc, cap, n_out, nullptr, nullptr, xy_un);
 }
 
 int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows,
@@ -1908,7 +1800,7 @@ int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, fl
             "(or undistort those keypoints with orbfe_undistort_equidistant on the host)");
     return ORBFE_ERR_UNSUPPORTED;
   }
-  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   CameraModel C{};
   for (int i = 0; i < ndist; i++) C.k[i] = dist[i];
   C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy;
@@ -1924,7 +1816,7 @@ int orbfe_extractor_set_camera(orbfe_extractor* h, int camera_mode, float fx, fl
 
 int orbfe_extractor_set_camera_equidistant(orbfe_extractor* h, float fx, float fy, float cx, float cy) {
   if (!h) { set_err("bad camera"); return ORBFE_ERR_INVALID; }
-  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   if (!h->camActive || !h->camEqui) h->batchCap = 0;   // the result arena is carved again: mvKeysUn and the undecided list
   h->camE = EquidistantCamera{fx, fy, cx, cy};
   h->camF[0] = fx; h->camF[1] = fy; h->camF[2] = cx; h->camF[3] = cy;
@@ -1935,7 +1827,7 @@ int orbfe_extractor_set_camera_equidistant(orbfe_extractor* h, float fx, float f
 int orbfe_extractor_undistort_verdict(orbfe_extractor* h, const float* xy, int n, float* out, uint8_t* undecided) {
   if (!h || n < 0 || (n && (!xy || !out || !undecided))) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
   if (!h->camEqui) { set_err("the extractor has no equidistant camera (orbfe_extractor_set_camera_equidistant)"); return ORBFE_ERR_INVALID; }
-  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
+  if (h->pendingFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(h->device));
   return h->equidistantPoints(const_cast<float*>(xy), n, out, undecided);
 }
@@ -1955,95 +1847,31 @@ int orbfe_extractor_undistort(orbfe_extractor* h, float* xy, int n) {
 }
 
 // The GPU quadtree takes 1..4 root nodes per level and at most 2 044 features per level; outside that (very wide strips,
-// nfeatures beyond about 9 000) the asynchronous entry points run the batch through the blocking host-quadtree path at
-// submit time and keep the results for _collect: same results, no overlap.
-static bool gpu_route_ok(orbfe_extractor* h, int rows, int cols, int* rc) {
-  *rc = ORBFE_OK;
-  if (!h->gpuQuadtree) return false;
-  if (hipSetDevice(h->device) != hipSuccess) { set_err("hipSetDevice failed"); *rc = ORBFE_ERR_HIP; return false; }
-  if (h->pendingFrames || h->deferredFrames) return true;   // reported by the submit itself
-  *rc = h->setGeometry(rows, cols);
-  return *rc == ORBFE_OK && h->geomGpuQtOk;
-}
-
-static int deferred_extract(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory, int rows, int cols,
-                            size_t stride_bytes) {
-  if (h->pendingFrames || h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
-  const int cap = orbfe_extractor_max_keypoints_for_size(h, rows, cols);
-  h->deferredCap = cap;
-  h->defKps.resize((size_t)nframes * cap);
-  h->defDesc.resize((size_t)nframes * cap * 32);
-  h->defN.assign(nframes, 0);
-  if (h->camActive) h->defXyUn.resize((size_t)nframes * cap * 2);   // (without a distorting camera mvKeysUn are the keypoints themselves)
-  const int rc = extract_batch_impl(h, nframes, gray, in_device_memory, rows, cols, stride_bytes, h->defKps.data(), h->defDesc.data(),
-                                    cap, h->defN.data(), h->camActive ? h->defXyUn.data() : nullptr);
-  h->deferredCam = h->camActive;
-  if (rc) return rc;
-  h->deferredFrames = nframes;
-  h->deferredMatched = false;
-  return ORBFE_OK;
-}
-
-static int deferred_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int32_t* matches12,
-                            int* nmatches, float* xy_un = nullptr) {
-  const int nframes = h->deferredFrames, dcap = h->deferredCap;
-  h->deferredFrames = 0;
-  int status = ORBFE_OK;
-  for (int f = 0; f < nframes; f++) {
-    const int n = h->defN[f];
-    n_out[f] = n;
-    if (n > cap) { set_err("frame %d produced %d keypoints, cap is %d", f, n, cap); status = ORBFE_ERR_OVERFLOW; }
-    const int m = std::min(n, cap);
-    memcpy(kps + (size_t)f * cap, h->defKps.data() + (size_t)f * dcap, sizeof(OrbfeKeyPoint) * (size_t)m);
-    memcpy(desc + (size_t)f * cap * 32, h->defDesc.data() + (size_t)f * dcap * 32, 32 * (size_t)m);
-    if (xy_un && h->deferredCam) memcpy(xy_un + (size_t)f * cap * 2, h->defXyUn.data() + (size_t)f * dcap * 2, 2 * sizeof(float) * (size_t)m);
-    else if (xy_un)
-      for (int i = 0; i < m; i++) { xy_un[((size_t)f * cap + i) * 2] = h->defKps[(size_t)f * dcap + i].x; xy_un[((size_t)f * cap + i) * 2 + 1] = h->defKps[(size_t)f * dcap + i].y; }
-    if (matches12 && nmatches) {
-      int32_t* row = matches12 + (size_t)f * cap;
-      for (int i = 0; i < cap; i++) row[i] = -1;
-      nmatches[f] = 0;
-      if (h->deferredMatched) {
-        memcpy(row, h->defM12.data() + (size_t)f * dcap, sizeof(int32_t) * (size_t)std::min(cap, dcap));
-        nmatches[f] = h->defNm[f];
-      }
-    }
-  }
-  return status;
-}
-
+// nfeatures beyond about 9 000) a batch is selected by the host quadtree inside the submit call, which then blocks until
+// the front has run: same results, no overlap.
 int orbfe_extract_batch_submit(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory,
                                int rows, int cols, size_t stride_bytes) {
   if (!h || !gray || nframes <= 0 || rows <= 0 || cols <= 0 || stride_bytes < (size_t)cols * h->inChannels()) {
     set_err("invalid arguments");
     return ORBFE_ERR_INVALID;
   }
-  int rc;
-  if (!gpu_route_ok(h, rows, cols, &rc)) {
-    if (rc) return rc;
-    return deferred_extract(h, nframes, gray, in_device_memory, rows, cols, stride_bytes);
-  }
-  if (h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
-  return h->submitGpuQt(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes);
+  return h->submit(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes);
 }
 
 int orbfe_extract_batch_wait(orbfe_extractor* h) {
   if (!h) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
-  if (h->deferredFrames) return ORBFE_OK;   // (a batch that took the blocking host-quadtree route at submit time is done already)
   return h->waitOnly();
 }
 
 int orbfe_extract_batch_collect(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out) {
   if (!h || !kps || !desc || !n_out || cap <= 0) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
-  if (h->deferredFrames) return deferred_collect(h, kps, desc, cap, n_out, nullptr, nullptr);
-  return h->waitGpuQt(kps, desc, cap, n_out);
+  return h->collect(kps, desc, cap, n_out);
 }
 
 int orbfe_extract_batch_collect_undistorted(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out, float* xy_un,
                                             int32_t* matches12, int* nmatches) {
   if (!h || !kps || !desc || !n_out || !xy_un || cap <= 0 || (!matches12) != (!nmatches)) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
-  if (h->deferredFrames) return deferred_collect(h, kps, desc, cap, n_out, matches12, nmatches, xy_un);
-  return h->waitGpuQt(kps, desc, cap, n_out, matches12, nmatches, xy_un);
+  return h->collect(kps, desc, cap, n_out, matches12, nmatches, xy_un);
 }
 
 int orbfe_sfi_chain_create(const orbfe_extractor* h, orbfe_sfi_chain** out) {
@@ -2052,7 +1880,7 @@ int orbfe_sfi_chain_create(const orbfe_extractor* h, orbfe_sfi_chain** out) {
   HIP_TRY(hipSetDevice(h->device));
   orbfe_sfi_chain* c = new orbfe_sfi_chain();
   c->device = h->device;
-  c->n0cap = h->selOff[1] - h->selOff[0];
+  c->n0cap = h->n0cap;
   int rc = ORBFE_OK;
   for (int i = 0; i < 2 && rc == ORBFE_OK; i++) {
     if ((rc = c->sel[i].ensure(c->n0cap))) break;
@@ -2096,92 +1924,19 @@ int orbfe_extract_batch_submit_matched(orbfe_extractor* h, orbfe_sfi_chain* chai
     return ORBFE_ERR_INVALID;
   }
   if (!(bounds[1] > bounds[0] && bounds[3] > bounds[2])) { set_err("empty image bounds"); return ORBFE_ERR_INVALID; }
-  int rc;
-  if (!gpu_route_ok(h, rows, cols, &rc)) {
-    if (rc) return rc;
-    // host-quadtree route: extract now, then SearchForInitialization of every frame against its predecessor (the chain
-    // carries the previous batch's last frame on the host) as one batched matcher call
-    if ((rc = deferred_extract(h, nframes, gray, in_device_memory, rows, cols, stride_bytes))) return rc;
-    if (!chain->hostMatcher && (rc = orbfe_matcher_create(h->device, &chain->hostMatcher))) { h->deferredFrames = 0; return rc; }
-    const int cap = h->deferredCap;
-    h->defM12.assign((size_t)nframes * cap, -1);
-    h->defNm.assign(nframes, 0);
-    std::vector<const OrbfeKeyPoint*> k1, k2;
-    std::vector<const uint8_t*> d1, d2;
-    std::vector<int> n1, n2, frameOf, nm;
-    std::vector<std::vector<float>> pxy;
-    std::vector<float*> prev;
-    std::vector<int32_t*> m12;
-    // with a distorting camera the searches run on mvKeysUn: the keypoints with their coordinates replaced (Frame.cc:284-319)
-    const bool cam = h->camActive;
-    if (cam != chain->camera) chain->hostPrevValid = false;   // the carry holds the other kind of coordinates
-    chain->camera = cam;
-    if (chain->equi != h->camEqui || (h->camEqui && memcmp(chain->eqCam, h->camF, sizeof h->camF))) chain->hostPrevValid = false;
-    chain->equi = h->camEqui;
-    memcpy(chain->eqCam, h->camF, sizeof h->camF);
-    std::vector<OrbfeKeyPoint> unKps, unPrev;
-    if (cam) {
-      unKps = h->defKps;
-      for (int f = 0; f < nframes; f++)
-        for (int j = 0; j < h->defN[f]; j++) {
-          unKps[(size_t)f * cap + j].x = h->defXyUn[((size_t)f * cap + j) * 2];
-          unKps[(size_t)f * cap + j].y = h->defXyUn[((size_t)f * cap + j) * 2 + 1];
-        }
-      unPrev = chain->hostPrevKps;
-      if (chain->hostPrevValid)
-        for (size_t j = 0; j < unPrev.size(); j++) { unPrev[j].x = chain->hostPrevXyUn[2 * j]; unPrev[j].y = chain->hostPrevXyUn[2 * j + 1]; }
-    }
-    const OrbfeKeyPoint* curKps = cam ? unKps.data() : h->defKps.data();
-    for (int f = 0; f < nframes; f++) {
-      const OrbfeKeyPoint* pk;
-      const uint8_t* pd;
-      int pn;
-      if (f == 0) {
-        if (!chain->hostPrevValid || chain->isolated || chain->restart) continue;   // very first frame of the stream (or isolated batches): no predecessor
-        pk = cam ? unPrev.data() : chain->hostPrevKps.data(); pd = chain->hostPrevDesc.data(); pn = (int)chain->hostPrevKps.size();
-      } else {
-        pk = curKps + (size_t)(f - 1) * cap; pd = h->defDesc.data() + (size_t)(f - 1) * cap * 32; pn = h->defN[f - 1];
-      }
-      pxy.emplace_back((size_t)std::max(pn, 1) * 2);
-      for (int j = 0; j < pn; j++) { pxy.back()[2 * j] = pk[j].x; pxy.back()[2 * j + 1] = pk[j].y; }   // vbPrevMatched := F1's keypoints (Tracking.cc:355-357)
-      k1.push_back(pk); d1.push_back(pd); n1.push_back(pn);
-      k2.push_back(curKps + (size_t)f * cap); d2.push_back(h->defDesc.data() + (size_t)f * cap * 32); n2.push_back(h->defN[f]);
-      m12.push_back(h->defM12.data() + (size_t)f * cap);
-      frameOf.push_back(f);
-    }
-    for (auto& v : pxy) prev.push_back(v.data());
-    nm.assign(k1.size(), 0);
-    if (!k1.empty()) {
-      rc = orbfe_search_for_initialization_batch(chain->hostMatcher, (int)k1.size(), k1.data(), d1.data(), n1.data(), k2.data(), d2.data(),
-                                                 n2.data(), bounds, prev.data(), m12.data(), window_size, nnratio, check_orientation,
-                                                 nm.data());
-      if (rc) { h->deferredFrames = 0; return rc; }
-      for (size_t p = 0; p < frameOf.size(); p++) h->defNm[frameOf[p]] = nm[p];
-    }
-    const int last = nframes - 1, ln = h->defN[last];
-    chain->hostPrevKps.assign(h->defKps.begin() + (size_t)last * cap, h->defKps.begin() + (size_t)last * cap + ln);
-    chain->hostPrevDesc.assign(h->defDesc.begin() + (size_t)last * cap * 32, h->defDesc.begin() + ((size_t)last * cap + ln) * 32);
-    if (cam) chain->hostPrevXyUn.assign(h->defXyUn.begin() + (size_t)last * cap * 2, h->defXyUn.begin() + ((size_t)last * cap + ln) * 2);
-    chain->hostPrevValid = !chain->isolated;
-    chain->restart = false;
-    h->deferredMatched = true;
-    return ORBFE_OK;
-  }
-  if (h->deferredFrames) { set_err("a submitted batch has not been collected yet"); return ORBFE_ERR_INVALID; }
   orbfe_extractor::MatchSpec ms;
   ms.chain = chain;
   memcpy(ms.bounds, bounds, sizeof ms.bounds);
   ms.window = window_size;
   ms.nnratio = nnratio;
   ms.checkOri = check_orientation;
-  return h->submitGpuQt(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, &ms);
+  return h->submit(nframes, gray, in_device_memory != 0, rows, cols, stride_bytes, &ms);
 }
 
 int orbfe_extract_batch_collect_matched(orbfe_extractor* h, OrbfeKeyPoint* kps, uint8_t* desc, int cap, int* n_out,
                                         int32_t* matches12, int* nmatches) {
   if (!h || !kps || !desc || !n_out || !matches12 || !nmatches || cap <= 0) { set_err("invalid arguments"); return ORBFE_ERR_INVALID; }
-  if (h->deferredFrames) return deferred_collect(h, kps, desc, cap, n_out, matches12, nmatches);
-  return h->waitGpuQt(kps, desc, cap, n_out, matches12, nmatches);
+  return h->collect(kps, desc, cap, n_out, matches12, nmatches);
 }
 
 int orbfe_extract(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, size_t stride_bytes, OrbfeKeyPoint* kps,

@@ -70,7 +70,7 @@ struct PyramidParams {
   const FastCell* cells;            // [ncells] level-major, cell-row-major
   const uint8_t* zeros;             // 256 zero bytes in device memory: source of the LDS-DMA that clears a FAST wave's score tile
   int iniTh, minTh;
-  int frameBase;                    // first frame of this launch (sub-batch pipelining)
+  int frameBase;                    // first frame of this launch (0: a batch is one launch sequence)
   int gaussVariant;                 // ORBFE_GAUSS_ED / ORBFE_GAUSS_ROUNDED: which GaussianBlur k_describe reproduces
   int fastLean;                     // every cell carries FastCell::geo: k_fast_tasks may take its LEAN prologue (launch_fast decides per launch)
 };

@@ -920,9 +920,9 @@ __device__ __forceinline__ void wave_sum3_i32(int& a, int& b, int& c) {
   c = __builtin_amdgcn_readlane(c, 0) + __builtin_amdgcn_readlane(c, 16) + __builtin_amdgcn_readlane(c, 32) + __builtin_amdgcn_readlane(c, 48);
 }
 
-// Slot mode (GPU quadtree): `sel` is laid out [frame][selPerFrame] with per-level sub-regions; slot k is
-// live iff its index inside its level region is below selCount[frame][level].  Dense mode (host
-// quadtree): selCount == nullptr and every k < nsel is live.
+// Slot mode (both quadtrees write slots): `sel` is laid out [frame][selPerFrame] with per-level sub-regions; slot k is
+// live iff its index inside its level region is below selCount[frame][level].  Dense mode (selCount == nullptr, every
+// k < nsel live) has had no host caller since the host quadtree writes slots too.
 struct SlotInfo {
   const uint32_t* selCount;  // [nframes][kMaxLevels] or nullptr
   int selPerFrame;
@@ -1450,14 +1450,6 @@ static DescribeArgs describe_args(const PyramidParams& P, const SelKp* sel, int 
   A.nsel = nsel; A.selPerFrame = 1; A.nlevels = P.nlevels; A.frameBase = P.frameBase; A.dma = lds_dma_enabled();
   A.gauss = P.gaussVariant;
   return A;
-}
-
-void launch_describe(const PyramidParams& P, const SelKp* sel, int nsel, float* angle, uint8_t* desc,
-                     hipStream_t st) {
-  if (nsel <= 0) return;
-  const DescribeArgs A = describe_args(P, sel, nsel, angle, desc);
-  if (A.gauss == 1) hipLaunchKernelGGL((k_describe<1, 1>), dim3(8 * ((nsel + 7) / 8)), dim3(64), 0, st, A);
-  else hipLaunchKernelGGL((k_describe<1, 0>), dim3(8 * ((nsel + 7) / 8)), dim3(64), 0, st, A);
 }
 
 // sel/angle/desc point at the first slot of frame P.frameBase; nslots = nframes * selPerFrame

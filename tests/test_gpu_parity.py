@@ -148,8 +148,9 @@ def test_legacy_gaussian_variant_parity(api, oracle):
     st.close()
     with pytest.raises(Exception):
         ex.set_blur_variant(2)
-    # the HOST-quadtree route (strips with more than 4 roots per level, more than 2 044 features on a level) describes through
-    # launch_describe: the variant must reach it too (tools/sweep_debug.py found that it did not, round 5)
+    # HOST-selected batches (strips with more than 4 roots per level, more than 2 044 features on a level) once described through a
+    # launch of their own, which the variant did not reach (tools/sweep_debug.py, round 5).  They now take the one describe step of
+    # every batch; what this still covers: the variant on slots the host quadtree wrote, one-frame call and batch
     for (W, H, N, nl) in [(1266, 290, 56, 2), (604, 514, 2759, 1)]:
         img = synth(64, W, H)
         for variant in (1, 0):
