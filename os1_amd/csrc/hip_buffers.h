@@ -1,12 +1,13 @@
 // hip_buffers.h -- the host-side helpers every matcher-side file needs: the HIP error check, grow-only device and page-locked
-// buffers, the arena alignment and the wait for a kernel's completion word.  (orbfe_extractor.hip keeps buffers of its own:
-// its page-locked ones are hipHostMallocDefault, a different thing.)
+// buffers, the scratch a file keeps on a handle, the arena alignment and the wait for a kernel's completion word.
+// (orbfe_extractor.hip keeps buffers of its own: its page-locked ones are hipHostMallocDefault, a different thing.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <chrono>
 #include <cstddef>
+#include <memory>
 
 #include "../../include/orbfe.h"
 
@@ -64,6 +65,14 @@ struct PinBuf {
   void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
 };
 
+// A file's scratch (buffers, events, counters of its own) kept in a slot of the handle that outlives its calls: made on
+// first use, destroyed with the handle -- whose destructor makes the device current first.  One slot holds one type.
+template <class T>
+T* scratch_in(std::shared_ptr<void>& slot) {
+  if (!slot) slot = std::make_shared<T>();
+  return static_cast<T*>(slot.get());
+}
+
 // parts of an upload arena start on 256-byte boundaries
 inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -87,4 +96,5 @@ inline int wait_for_word(const volatile int* word, int seq, hipStream_t st, bool
 using orbfe::al;
 using orbfe::DevBuf;
 using orbfe::PinBuf;
+using orbfe::scratch_in;
 using orbfe::wait_for_word;

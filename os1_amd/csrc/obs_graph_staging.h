@@ -29,10 +29,6 @@ struct ObsGraphScratch {
     d_in.release(); d_out.release(); h_in.release(); h_out.release();
     (void)hipGetLastError();
   }
-  static ObsGraphScratch* of(std::shared_ptr<void>& slot) {      // made on first use
-    if (!slot) slot = std::make_shared<ObsGraphScratch>();
-    return static_cast<ObsGraphScratch*>(slot.get());
-  }
   static int lastMs(const std::shared_ptr<void>* slot, double out[3]) {      // zeros before the first call; slot is null where the matcher was
     if (!slot || !out) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
     const ObsGraphScratch* S = static_cast<const ObsGraphScratch*>(slot->get());

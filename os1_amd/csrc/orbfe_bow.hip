@@ -12,36 +12,13 @@
 // bookkeeping in the order the reference does it, on a few thousand scalars: summing word weights in feature order
 // (double, so the order is part of the result), the L1/L2 normalisation in ascending word order, grouping feature
 // indices by node, and the rotation-histogram pruning.
-#include <hip/hip_runtime.h>
+#include "orbfe_matcher_internal.h"
 
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <initializer_list>
-#include <memory>
 #include <mutex>
-#include <vector>
 
-#include "../../include/orbfe.h"
 #include "bow_batch_plan.h"
-#include "hip_buffers.h"
 #include "tri_batch_plan.h"
-
-namespace orbfe {
-int gpu_readable(const void* p, int device);   // orbfe_frame.hip: 0 ordinary host memory, 1 page-locked, 2 this device's, -1 another's
-// orbfe_frame.hip: a resident frame's device arrays in keypoint order (none of these waits) and the stream order behind its build
-void frame_source_arrays(const orbfe_frame* f, const int** oct, const float** angle, int* maxOctave);
-void frame_xy(const orbfe_frame* f, const float** x, const float** y);
-const uint8_t* frame_descriptor_rows(const orbfe_frame* f);
-void frame_wait_ready(orbfe_frame* f, hipStream_t st);
-int matcher_device(const orbfe_matcher* m);
-hipStream_t matcher_stream(const orbfe_matcher* m);
-std::shared_ptr<void>& matcher_bow_slot(orbfe_matcher* m);
-}
-using orbfe::set_err;
 
 namespace {
 
@@ -1032,11 +1009,9 @@ struct BowCall {
   // parts: bytes of each array of the arena, in order; the caller fills them at host(i) and then submits.  pairs: the nodes,
   // whose sizes decide the route; nullptr: the upload route (a caller whose kernel has no completion word)
   int open(orbfe_matcher* m, std::initializer_list<size_t> parts, size_t nRows, const std::vector<BowPair>* pairs) {
-    HIP_TRY(hipSetDevice(orbfe::matcher_device(m)));
-    std::shared_ptr<void>& slot = orbfe::matcher_bow_slot(m);
-    if (!slot) slot = std::make_shared<BowScratch>();
-    S = static_cast<BowScratch*>(slot.get());
-    st = orbfe::matcher_stream(m);
+    HIP_TRY(hipSetDevice(m->device));
+    S = scratch_in<BowScratch>(m->bow);
+    st = m->stream;
     rows = nRows;
     off.assign(1, 0);
     for (const size_t bytes : parts) off.push_back(off.back() + al(bytes));
@@ -1251,7 +1226,7 @@ static int bow_batch_core(orbfe_matcher* m, int n_kf, const uint8_t* const* desc
     static size_t attr[64] = {};
     {
       std::lock_guard<std::mutex> lk(mu);
-      const int dv = orbfe::matcher_device(m);
+      const int dv = m->device;
       if (dv >= 0 && dv < 64 && ldsBytes > attr[dv]) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
         attr[dv] = ldsBytes;
@@ -1309,7 +1284,7 @@ extern "C" int orbfe_search_by_bow(orbfe_matcher* m, const uint8_t* desc1, const
   }
   *nmatches = 0;
   // a side whose rows are a resident frame's (orbfe_frame_descriptors_device) stays where it is
-  const int dev = orbfe::matcher_device(m);
+  const int dev = m->device;
   // (rows in this device's memory, 16-byte aligned: read in place; another device's, or misaligned: refused, never memcpy'd;
   // everything else -- ordinary, page-locked and managed memory -- is copied into the arena)
   const int g1 = orbfe::gpu_readable(desc1, dev), g2 = orbfe::gpu_readable(desc2, dev);
@@ -1406,7 +1381,7 @@ extern "C" int orbfe_search_for_triangulation_frames_batch(orbfe_matcher* m, orb
     s2[k].tables = N.scale_factors2 && N.level_sigma2_2;
   }
   orbfe::TriBatchPlan plan;
-  const int prc = orbfe::tri_batch_plan(orbfe::matcher_device(m), s1, n_nb, neighbours ? s2.data() : nullptr, sizeof(TriNeighbour), plan);
+  const int prc = orbfe::tri_batch_plan(m->device, s1, n_nb, neighbours ? s2.data() : nullptr, sizeof(TriNeighbour), plan);
   if (prc) { set_err("%s", plan.why); return prc; }
   if (plan.entries == 0) return ORBFE_OK;
   if (!matches12_raw) { set_err("matches12_raw is NULL"); return ORBFE_ERR_INVALID; }

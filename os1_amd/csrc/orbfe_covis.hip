@@ -154,7 +154,7 @@ int orbfe_covisibility_counts(orbfe_matcher* m, int n_kf, int n_mp, const int32_
   if (!m) { set_err("covisibility: null pointer (matcher)"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(m->device));
   (void)hipGetLastError();
-  orbfe::ObsGraphScratch* S = orbfe::ObsGraphScratch::of(m->covis);
+  orbfe::ObsGraphScratch* S = scratch_in<orbfe::ObsGraphScratch>(m->covis);
 
   // one page-locked arena, one copy up: the graph (obs_graph_stage), then the limit per subject
   const size_t ns = (size_t)n_subj, pieces = ns * (size_t)plan.nPass;

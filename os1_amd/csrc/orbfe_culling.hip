@@ -120,7 +120,7 @@ int orbfe_redundant_observations(orbfe_matcher* m, int n_kf, int n_mp, const int
   if (!m) { set_err("redundant observations: null pointer (matcher)"); return ORBFE_ERR_INVALID; }
   HIP_TRY(hipSetDevice(m->device));
   (void)hipGetLastError();
-  orbfe::ObsGraphScratch* S = orbfe::ObsGraphScratch::of(m->culling);
+  orbfe::ObsGraphScratch* S = scratch_in<orbfe::ObsGraphScratch>(m->culling);
 
   // one page-locked arena, one copy up: the graph with its level bytes (obs_graph_stage), then Observations() per MapPoint
   const size_t ns = (size_t)n_subj;

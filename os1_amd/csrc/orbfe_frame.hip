@@ -20,8 +20,8 @@
 // table -> claims" until nothing changes, and finishes a chunk with a serial pass if a bound on the rounds is hit -- the
 // same idea as k_sfi_resolve (orbfe_sfi.hip).
 #include "orbfe_matcher_internal.h"
-#include <atomic>
-#include "orbfe_internal.h"
+
+using namespace orbfe_match;
 
 namespace {
 
@@ -894,17 +894,7 @@ int run_search(orbfe_matcher* m, orbfe_frame* f, const SearchPlan& P, const uint
     M.chi2 = chi2;
     M.packOctave = 1;
     M.codeMode = P.mode; M.nnratio = nnratio; M.maxDist = maxDist;
-    {
-      const float cols = 2.f * rmax * f->invW + 3.f;   // widest window in grid columns (+3: floor / ceil slack of the cell range)
-      const int maxCols = cols >= 64.f ? 64 : std::max(1, (int)std::ceil(cols));
-      int lpq = 8;
-      while (lpq < 64 && lpq < maxCols) lpq <<= 1;
-      const unsigned nblk = (unsigned)((nq + (kWinThreads / lpq) - 1) / (kWinThreads / lpq));
-      if (lpq == 8) hipLaunchKernelGGL(k_window_match<8>, dim3(nblk), dim3(kWinThreads), 0, st, M);
-      else if (lpq == 16) hipLaunchKernelGGL(k_window_match<16>, dim3(nblk), dim3(kWinThreads), 0, st, M);
-      else if (lpq == 32) hipLaunchKernelGGL(k_window_match<32>, dim3(nblk), dim3(kWinThreads), 0, st, M);
-      else hipLaunchKernelGGL(k_window_match<64>, dim3(nblk), dim3(kWinThreads), 0, st, M);
-    }
+    if ((rc = orbfe::launch_window_match(M, 2.f * rmax * f->invW + 3.f, st))) return rc;   // the widest window in grid columns (window_plan.h)
     ResolveParams R;
     R.qword = M.qword; R.rec = M.rec; R.qoff = M.qoff; R.pool = M.pool; R.total = M.total; R.poolCap = M.poolCap;
     R.wpool = M.wpool; R.wtotal = M.wtotal;

@@ -212,11 +212,6 @@ struct Outs {
   uint8_t *inliers_h, *inliers_f;
 };
 
-InitScratch* scratch_of(orbfe_matcher* m) {
-  if (!m->initscore) m->initscore = std::make_shared<InitScratch>();
-  return static_cast<InitScratch*>(m->initscore.get());
-}
-
 int check_common(const orbfe_matcher* m, int n_hyp, const float* H21, const float* H12, const float* F21) {
   if (!m) { set_err("invalid argument: matcher is NULL"); return ORBFE_ERR_INVALID; }
   if (n_hyp < 1) { set_err("invalid argument: n_hyp = %d (at least one hypothesis)", n_hyp); return ORBFE_ERR_INVALID; }
@@ -307,7 +302,7 @@ int orbfe_score_init_hypotheses(orbfe_matcher* m, const float* pts, int n, float
   const Outs O{scores_h, scores_f, best_h, best_f, best_score_h, best_score_f, inliers_h, inliers_f};
   if (n == 0) { fill_empty(n_hyp, H21 != nullptr, F21 != nullptr, O); return ORBFE_OK; }
   HIP_TRY(hipSetDevice(m->device));
-  InitScratch* S = scratch_of(m);
+  InitScratch* S = scratch_in<InitScratch>(m->initscore);
   const size_t pb = sizeof(float) * 4 * (size_t)n;
   if ((rc = stage_hyps(S, n_hyp, pb, H21, H12, F21))) return rc;
   memcpy(S->h_in.p + hyp_bytes(n_hyp), pts, pb);
@@ -331,7 +326,7 @@ int orbfe_score_init_hypotheses_kps(orbfe_matcher* m, const OrbfeKeyPoint* kps1_
   const Outs O{scores_h, scores_f, best_h, best_f, best_score_h, best_score_f, inliers_h, inliers_f};
   if (N == 0) { fill_empty(n_hyp, H21 != nullptr, F21 != nullptr, O); if (n_matches) *n_matches = 0; return ORBFE_OK; }
   HIP_TRY(hipSetDevice(m->device));
-  InitScratch* S = scratch_of(m);
+  InitScratch* S = scratch_in<InitScratch>(m->initscore);
   const size_t pb = sizeof(float) * 4 * (size_t)N;
   if ((rc = stage_hyps(S, n_hyp, pb, H21, H12, F21))) return rc;
   float* p = reinterpret_cast<float*>(S->h_in.p + hyp_bytes(n_hyp));
@@ -367,7 +362,7 @@ int orbfe_score_init_hypotheses_frames(orbfe_matcher* m, orbfe_frame* f1, orbfe_
   const Outs O{scores_h, scores_f, best_h, best_f, best_score_h, best_score_f, inliers_h, inliers_f};
   if (N == 0) { fill_empty(n_hyp, H21 != nullptr, F21 != nullptr, O); if (n_matches) *n_matches = 0; return ORBFE_OK; }
   HIP_TRY(hipSetDevice(m->device));
-  InitScratch* S = scratch_of(m);
+  InitScratch* S = scratch_in<InitScratch>(m->initscore);
   const size_t mb = sizeof(int32_t) * (size_t)n1;
   if ((rc = stage_hyps(S, n_hyp, mb, H21, H12, F21)) || (rc = S->d_pts.ensure((size_t)N))) return rc;
   memcpy(S->h_in.p + hyp_bytes(n_hyp), matches12, mb);

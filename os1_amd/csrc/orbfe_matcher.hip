@@ -9,32 +9,225 @@
 //   SearchByProjection (Frame/KF)  ORBmatcher.cc:1292-1552 (from the projection onwards)
 //   ComputeThreeMaxima             ORBmatcher.cc:1554-1595
 //
-// Split of work: every search is "for each query, scan the grid window, compare
-// descriptors, keep best/second-best" wrapped in bookkeeping that later iterations read
-// (vMatchedDistance / vnMatches21, F.mvpMapPoints occupancy).  The data-parallel part -- window
-// test, level filter and Hamming distance for every (query, candidate) pair, emitted in exactly
-// the order Frame::GetFeaturesInArea would return them -- is one kernel (one wave per query,
-// ballot-ordered compaction).  SearchForInitialization's order-dependent bookkeeping is replayed on
-// the host over those short candidate lists, statement for statement; the SearchByProjection family
-// runs on a transient resident frame with its bookkeeping on the GPU (orbfe_frame.hip).
+// Split of work: every search is "for each query, scan the grid window, compare descriptors, keep
+// best/second-best" wrapped in bookkeeping that later iterations read (vMatchedDistance / vnMatches21, F.mvpMapPoints
+// occupancy).  The data-parallel part -- window test, level filter and Hamming distance for every (query, candidate) pair,
+// emitted in the order Frame::GetFeaturesInArea would return them -- is k_window_match (orbfe_window.hip).
+// SearchForInitialization's order-dependent bookkeeping is replayed on the host over those short candidate lists, statement
+// for statement; the SearchByProjection family runs on a transient resident frame with its bookkeeping on the GPU (orbfe_frame.hip).
 #include "orbfe_matcher_internal.h"
 
-namespace orbfe {
-// orbfe_frame.hip: the host-array searches run on a transient device-resident frame + GPU-side bookkeeping
-int sbp_via_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n, const float bounds[4],
-                  const float* scale_factors, int nlevels, const uint8_t* kp_occupied, const float* mp_proj_xy,
-                  const int32_t* mp_level, const float* mp_viewcos, const uint8_t* mp_flags, const uint8_t* mp_desc, int n_mp,
-                  float th, float nnratio, int32_t* kp_assigned, int* nmatches);
-int sbp_uv_via_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n, const float bounds[4],
-                     const float* scale_factors, int nlevels, const uint8_t* kp_occupied, const float* src_uv,
-                     const int32_t* src_level, const float* src_angle, const uint8_t* src_flags, const uint8_t* src_valid,
-                     const uint8_t* src_desc, int n_src, float th, int max_dist, int skip_any_occupied, int check_orientation,
-                     int32_t* kp_assigned, int* nmatches);
-int projected_via_frame(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const uint8_t* desc, int n, const float bounds[4], int n_src,
-                        const float* src_uv, const float* src_radius, const int32_t* src_level, const uint8_t* src_valid,
-                        const uint8_t* src_desc, const uint8_t* kp_skip, int claim, const float* inv_level_sigma2, int nlevels,
-                        double chi2, int max_dist, int32_t* best_idx, int32_t* best_dist, int* nmatches);
-}  // namespace orbfe
+#include "host_pool.h"
+
+using namespace orbfe_match;
+
+// The host-array search: any number of (train frame, queries) jobs on host arrays, gridded on the host and searched in one
+// upload, one launch of the window kernel and one download; the candidate lists stay here for the caller's bookkeeping.
+// The handle owns one (orbfe_matcher::host).  The staging buffers are also what orbfe_distinctive_descriptors stages in.
+struct orbfe::HostSearch {
+  DevBuf<uint8_t> d_in;    // packed upload arena
+  PinBuf<uint8_t> h_in;
+  DevBuf<uint32_t> d_out;  // [total(1) pad][qcount nq][qoff nq]
+  PinBuf<uint32_t> h_out;
+  PinBuf<uint32_t> h_pool;   // the candidate entries of the last candidates() call (device side: the handle's d_pool)
+  std::unique_ptr<HostPool> pool;
+  size_t lastTotal = 0;
+
+  // One search job: a train frame and a run of queries against it (host pointers).
+  struct Job {
+    const OrbfeKeyPoint* kps; const uint8_t* desc; int n; const float* bounds;
+    const float* qx; const float* qy; const float* qr; const int* qminL; const int* qmaxL; const uint8_t* qdesc; int nq;
+  };
+  // Results of the last candidates() call: per job the first query index; per query, by ORIGINAL query number (all jobs
+  // concatenated), count and offset into h_pool
+  std::vector<int> jobQ0;
+  std::vector<uint32_t> qcount, qoff;
+  std::vector<int> qmap;        // compact (launched) query -> original query
+  struct JobPlan { int lo, hi; size_t trainOff, q0c; int nTrain, nqc; };
+  std::vector<JobPlan> plan;
+
+  int candidates(orbfe_matcher* m, const Job* jobs, int njobs);
+};
+using orbfe::HostSearch;
+
+// Runs the window kernel for all jobs in ONE upload + ONE launch.  Only what can influence a result is
+// uploaded: active queries (r >= 0) and the train keypoints whose octave some active query of the job
+// accepts (e.g. SearchForInitialization touches level-0 keypoints only, ORBmatcher.cc:416-420).
+// Dropping the others cannot change any candidate list: Frame::GetFeaturesInArea would skip them.
+int HostSearch::candidates(orbfe_matcher* m, const Job* jobs, int njobs) {
+  const double tA = orbfe_matcher::nowMs();
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t stream = m->stream;
+  DevBuf<uint32_t>& d_pool = m->d_pool;
+  int rc;
+  const int ncell = kGridCols * kGridRows;
+  jobQ0.assign(njobs + 1, 0);
+  plan.assign(njobs, JobPlan{});
+  size_t nTrain = 0, nqOrig = 0, nq = 0;
+  float widestCols = 0.f;   // widest window in grid columns over all jobs (window_plan.h)
+  for (int j = 0; j < njobs; j++) {
+    const Job& J = jobs[j];
+    // empty bounds make the inverse cell size infinite: the kernel's first column, (int)floorf(+inf), saturates and `cx0 + sub` wraps
+    if (!(J.bounds[1] > J.bounds[0] && J.bounds[3] > J.bounds[2])) { set_err("empty image bounds"); return ORBFE_ERR_INVALID; }
+    jobQ0[j] = (int)nqOrig;
+    nqOrig += J.nq;
+    JobPlan& pl = plan[j];
+    pl.lo = INT_MAX; pl.hi = INT_MIN; pl.nqc = 0;
+    float rmax = 0.f;
+    for (int q = 0; q < J.nq; q++) {
+      rmax = std::max(rmax, J.qr[q]);
+      if (!(J.qr[q] >= 0.f)) continue;
+      pl.nqc++;
+      const bool check = (J.qminL[q] > 0) || (J.qmaxL[q] >= 0);
+      const int lo = check ? J.qminL[q] : INT_MIN, hi = (check && J.qmaxL[q] >= 0) ? J.qmaxL[q] : INT_MAX;
+      pl.lo = std::min(pl.lo, lo);
+      pl.hi = std::max(pl.hi, hi);
+    }
+    const float invW = static_cast<float>(kGridCols) / static_cast<float>(J.bounds[1] - J.bounds[0]);
+    widestCols = std::max(widestCols, 2.f * rmax * invW + 3.f);
+    pl.trainOff = nTrain;
+    pl.q0c = nq;
+    nq += pl.nqc;
+    int cnt = 0;
+    if (pl.nqc)
+      for (int i = 0; i < J.n; i++) cnt += (J.kps[i].octave >= pl.lo && J.kps[i].octave <= pl.hi) ? 1 : 0;
+    pl.nTrain = cnt;   // upper bound (keypoints outside the grid are dropped below)
+    nTrain += cnt;
+  }
+  jobQ0[njobs] = (int)nqOrig;
+  qcount.assign(nqOrig, 0);
+  qoff.assign(nqOrig, 0);
+  qmap.resize(nq);
+  if (nq == 0) {
+    m->stageMs[0] = orbfe_matcher::nowMs() - tA;
+    m->stageMs[1] = 0;
+    return ORBFE_OK;
+  }
+  // arena layout (one H2D copy); train descriptors are stored in grid-sorted order
+  const size_t oSx = 0, oSy = oSx + al(4 * nTrain), oOct = oSy + al(4 * nTrain), oIdx = oOct + al(4 * nTrain),
+               oCell = oIdx + al(4 * nTrain), oTd = oCell + al(4 * (size_t)(ncell + 1) * njobs),
+               oPair = oTd + al(32 * nTrain), oQp = oPair + al(sizeof(PairInfo) * (size_t)njobs),
+               oQx = oQp + al(4 * nq), oQy = oQx + al(4 * nq), oQr = oQy + al(4 * nq), oQa = oQr + al(4 * nq),
+               oQb = oQa + al(4 * nq), oQd = oQb + al(4 * nq), total = oQd + al(32 * nq);
+  if ((rc = h_in.ensure(total))) return rc;
+  if ((rc = d_in.ensure(total))) return rc;
+  uint8_t* H = h_in.p;
+  pool->parallelFor(njobs, [&](int j, int) {
+    const Job& J = jobs[j];
+    const JobPlan& pl = plan[j];
+    const float minX = J.bounds[0], maxX = J.bounds[1], minY = J.bounds[2], maxY = J.bounds[3];
+    const float invW = static_cast<float>(kGridCols) / static_cast<float>(maxX - minX);   // Frame.cc:98
+    const float invH = static_cast<float>(kGridRows) / static_cast<float>(maxY - minY);   // Frame.cc:99
+    int* cellCnt = (int*)(H + oCell) + (size_t)(ncell + 1) * j;
+    for (int c = 0; c <= ncell; c++) cellCnt[c] = 0;
+    PairInfo pi;
+    pi.trainOff = (int)pl.trainOff; pi.cellOff = (ncell + 1) * j; pi.tdescOff = (int)pl.trainOff;
+    pi.minX = minX; pi.minY = minY; pi.invW = invW; pi.invH = invH;
+    ((PairInfo*)(H + oPair))[j] = pi;
+    if (pl.nqc == 0) return;
+    // AssignFeaturesToGrid / PosInGrid (Frame.cc:114-129, 264-274) as a stable counting sort by cell
+    std::vector<int> cellOf(J.n);
+    for (int i = 0; i < J.n; i++) {
+      cellOf[i] = -1;
+      if (J.kps[i].octave < pl.lo || J.kps[i].octave > pl.hi) continue;
+      const int px = (int)roundf((J.kps[i].x - minX) * invW);
+      const int py = (int)roundf((J.kps[i].y - minY) * invH);
+      if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) continue;
+      cellOf[i] = px * kGridRows + py;
+      cellCnt[cellOf[i] + 1]++;
+    }
+    for (int c = 0; c < ncell; c++) cellCnt[c + 1] += cellCnt[c];
+    std::vector<int> order(cellCnt, cellCnt + ncell);
+    float* sx = (float*)(H + oSx) + pl.trainOff;
+    float* sy = (float*)(H + oSy) + pl.trainOff;
+    int* so = (int*)(H + oOct) + pl.trainOff;
+    int* si = (int*)(H + oIdx) + pl.trainOff;
+    uint8_t* td = H + oTd + 32 * pl.trainOff;
+    for (int i = 0; i < J.n; i++) {
+      if (cellOf[i] < 0) continue;
+      const int p = order[cellOf[i]]++;
+      sx[p] = J.kps[i].x; sy[p] = J.kps[i].y; so[p] = J.kps[i].octave; si[p] = i;
+      memcpy(td + 32 * (size_t)p, J.desc + 32 * (size_t)i, 32);
+    }
+    // active queries, compacted
+    int* qp = (int*)(H + oQp) + pl.q0c;
+    float* qxo = (float*)(H + oQx) + pl.q0c;
+    float* qyo = (float*)(H + oQy) + pl.q0c;
+    float* qro = (float*)(H + oQr) + pl.q0c;
+    int* qao = (int*)(H + oQa) + pl.q0c;
+    int* qbo = (int*)(H + oQb) + pl.q0c;
+    uint8_t* qdo = H + oQd + 32 * pl.q0c;
+    int c = 0;
+    for (int q = 0; q < J.nq; q++) {
+      if (!(J.qr[q] >= 0.f)) continue;
+      qp[c] = j; qxo[c] = J.qx[q]; qyo[c] = J.qy[q]; qro[c] = J.qr[q]; qao[c] = J.qminL[q]; qbo[c] = J.qmaxL[q];
+      memcpy(qdo + 32 * (size_t)c, J.qdesc + 32 * (size_t)q, 32);
+      qmap[pl.q0c + c] = jobQ0[j] + q;
+      c++;
+    }
+  });
+  const double tB = orbfe_matcher::nowMs();
+  m->stageMs[0] = tB - tA;
+  // (experiments build, ORBFE_MATCH_ZEROCOPY=1: the kernel reads the pinned host arena directly over PCIe instead of a DMA upload)
+  static const bool zeroCopy = ORBFE_EXP_ENV("ORBFE_MATCH_ZEROCOPY") && atoi(ORBFE_EXP_ENV("ORBFE_MATCH_ZEROCOPY")) != 0;
+  if (!zeroCopy) HIP_TRY(hipMemcpyAsync(d_in.p, H, total, hipMemcpyHostToDevice, stream));
+
+  const size_t outWords = 64 + 2 * nq;
+  if ((rc = d_out.ensure(outWords))) return rc;
+  if ((rc = h_out.ensure(outWords))) return rc;
+  size_t poolCap = d_pool.n ? d_pool.n : std::max<size_t>(1 << 16, nq * 32);
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if ((rc = d_pool.ensure(poolCap))) return rc;
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 64 * sizeof(uint32_t), stream));
+    MatchParams M;
+    uint8_t* D = zeroCopy ? H : d_in.p;
+    M.sx = (const float*)(D + oSx); M.sy = (const float*)(D + oSy); M.soct = (const int*)(D + oOct);
+    M.sidx = (const int*)(D + oIdx); M.cellStart = (const int*)(D + oCell); M.tdesc = D + oTd;
+    M.pairs = (const PairInfo*)(D + oPair); M.qpair = (const int*)(D + oQp);
+    M.qx = (const float*)(D + oQx); M.qy = (const float*)(D + oQy); M.qr = (const float*)(D + oQr);
+    M.qminL = (const int*)(D + oQa); M.qmaxL = (const int*)(D + oQb); M.qdesc = D + oQd;
+    M.nq = (int)nq;
+    M.total = d_out.p; M.qcount = d_out.p + 64; M.qoff = d_out.p + 64 + nq;
+    M.pool = d_pool.p; M.poolCap = (uint32_t)d_pool.n;
+    if ((rc = orbfe::launch_window_match(M, widestCols, stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out.p, d_out.p, outWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    // optimistic: fetch a generous prefix of the pool in the same round trip
+    const size_t guess = std::min<size_t>(d_pool.n, std::max<size_t>(lastTotal + lastTotal / 4 + 1024, 4096));
+    if ((rc = h_pool.ensure(guess + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_pool.p, d_pool.p, guess * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const size_t tot = h_out.p[0];
+    if (tot <= d_pool.n) {
+      if (tot > guess) {
+        if ((rc = h_pool.ensure(tot + 1))) return rc;
+        HIP_TRY(hipMemcpyAsync(h_pool.p, d_pool.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+      }
+      lastTotal = tot;
+      m->stageMs[1] = orbfe_matcher::nowMs() - tB;
+      const uint32_t* qc = h_out.p + 64;
+      const uint32_t* qo = h_out.p + 64 + nq;
+      for (size_t c = 0; c < nq; c++) {
+        qcount[qmap[c]] = qc[c];
+        qoff[qmap[c]] = qo[c];
+      }
+      return ORBFE_OK;
+    }
+    poolCap = tot;  // pool too small: grow to the exact demand and rerun once
+  }
+  set_err("candidate pool sizing failed");
+  return ORBFE_ERR_HIP;
+}
+
+orbfe_matcher::~orbfe_matcher() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  orbfe_frame_destroy(scratch);
+  d_q.release(); h_q.release(); d_r.release(); h_r.release(); d_sf.release(); d_wpool.release();
+  delete host;
+  d_pool.release();
+  if (stream) (void)hipStreamDestroy(stream);
+}
 
 namespace {
 
@@ -108,18 +301,18 @@ inline int rotBin(float a1, float a2) {  // ORBmatcher.cc:470-475 (factor = 1/HI
 
 
 // sequential bookkeeping of SearchForInitialization, ORBmatcher.cc:402-512, over one job's candidate lists
-static int resolveSearchForInitialization(const orbfe_matcher* m, int q0, const OrbfeKeyPoint* kps1, int n1,
+static int resolveSearchForInitialization(const HostSearch* S, int q0, const OrbfeKeyPoint* kps1, int n1,
                                           const OrbfeKeyPoint* kps2, int n2, float* prev_xy, int32_t* matches12,
                                           float nnratio, int check_orientation) {
-  const uint32_t* pool = m->h_pool.p;
+  const uint32_t* pool = S->h_pool.p;
   int nm = 0;
   std::vector<int> rotHist[HISTO_LENGTH];
   std::vector<int> vMatchedDistance(n2, INT_MAX), vnMatches21(n2, -1);
   for (int i1 = 0; i1 < n1; i1++) {
     if (kps1[i1].octave > 0) continue;
-    const uint32_t cnt = m->qcount[q0 + i1];
+    const uint32_t cnt = S->qcount[q0 + i1];
     if (cnt == 0) continue;
-    const uint32_t* cl = pool + m->qoff[q0 + i1];
+    const uint32_t* cl = pool + S->qoff[q0 + i1];
     int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
     for (uint32_t c = 0; c < cnt; c++) {
       const int i2 = (int)(cl[c] & 0xffff), dist = (int)(cl[c] >> 16);
@@ -179,14 +372,16 @@ int orbfe_window_candidates(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const
   }
   *pool_used = 0;
   if (nq == 0) return ORBFE_OK;
-  int rc = m->candidates(kps_un, desc, n, bounds, qx, qy, qr, qmin_level, qmax_level, qdesc, nq);
+  HostSearch* S = m->host;
+  const HostSearch::Job job{kps_un, desc, n, bounds, qx, qy, qr, qmin_level, qmax_level, qdesc, nq};
+  int rc = S->candidates(m, &job, 1);
   if (rc) return rc;
   // repack per query so the caller's pool is dense and in query order
   size_t used = 0;
   for (int q = 0; q < nq; q++) {
-    counts[q] = m->qcount[q];
+    counts[q] = S->qcount[q];
     offsets[q] = (uint32_t)used;
-    used += m->qcount[q];
+    used += S->qcount[q];
   }
   *pool_used = used;
   if (used > pool_cap || (used && !pool)) {
@@ -194,7 +389,7 @@ int orbfe_window_candidates(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, const
     return ORBFE_ERR_OVERFLOW;
   }
   for (int q = 0; q < nq; q++)
-    if (counts[q]) memcpy(pool + offsets[q], m->h_pool.p + m->qoff[q], sizeof(uint32_t) * counts[q]);
+    if (counts[q]) memcpy(pool + offsets[q], S->h_pool.p + S->qoff[q], sizeof(uint32_t) * counts[q]);
   return ORBFE_OK;
 }
 
@@ -214,23 +409,24 @@ int orbfe_distinctive_descriptors(orbfe_matcher* m, int n_mp, const int32_t* off
   HIP_TRY(hipSetDevice(m->device));
   int rc;
   const size_t oOff = 0, oDesc = al(4 * (size_t)(n_mp + 1)), bytes = oDesc + al(32 * total + 32);
-  if ((rc = m->h_in.ensure(bytes))) return rc;
-  if ((rc = m->d_in.ensure(bytes))) return rc;
-  if ((rc = m->d_out.ensure((size_t)n_mp + 64))) return rc;
-  if ((rc = m->h_out.ensure((size_t)n_mp + 64))) return rc;
-  int* ho = (int*)(m->h_in.p + oOff);
+  HostSearch* S = m->host;   // (its staging buffers)
+  if ((rc = S->h_in.ensure(bytes))) return rc;
+  if ((rc = S->d_in.ensure(bytes))) return rc;
+  if ((rc = S->d_out.ensure((size_t)n_mp + 64))) return rc;
+  if ((rc = S->h_out.ensure((size_t)n_mp + 64))) return rc;
+  int* ho = (int*)(S->h_in.p + oOff);
   for (int p = 0; p <= n_mp; p++) ho[p] = offsets[p] - offsets[0];
-  if (total) memcpy(m->h_in.p + oDesc, descs + (size_t)offsets[0] * 32, 32 * total);
-  HIP_TRY(hipMemcpyAsync(m->d_in.p, m->h_in.p, bytes, hipMemcpyHostToDevice, m->stream));
+  if (total) memcpy(S->h_in.p + oDesc, descs + (size_t)offsets[0] * 32, 32 * total);
+  HIP_TRY(hipMemcpyAsync(S->d_in.p, S->h_in.p, bytes, hipMemcpyHostToDevice, m->stream));
   const size_t lds = std::max<size_t>((size_t)maxN * 32, 32);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_distinctive), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_distinctive, dim3(n_mp), dim3(64), lds, m->stream, (const int*)(m->d_in.p + oOff),
-                     (const uint8_t*)(m->d_in.p + oDesc), (int*)m->d_out.p, maxN);
+  hipLaunchKernelGGL(k_distinctive, dim3(n_mp), dim3(64), lds, m->stream, (const int*)(S->d_in.p + oOff),
+                     (const uint8_t*)(S->d_in.p + oDesc), (int*)S->d_out.p, maxN);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(m->h_out.p, m->d_out.p, sizeof(int) * n_mp, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(S->h_out.p, S->d_out.p, sizeof(int) * n_mp, hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  memcpy(best_idx, m->h_out.p, sizeof(int) * n_mp);
+  memcpy(best_idx, S->h_out.p, sizeof(int) * n_mp);
   return ORBFE_OK;
 }
 
@@ -316,6 +512,7 @@ int orbfe_matcher_create(int device_id, orbfe_matcher** out) {
   HIP_TRY(hipSetDevice(device_id));
   orbfe_matcher* m = new orbfe_matcher();
   m->device = device_id;
+  m->host = new HostSearch();
   hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     set_err("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -326,7 +523,7 @@ int orbfe_matcher_create(int device_id, orbfe_matcher** out) {
   if (nthreads > 8) nthreads = 8;
   if (const char* ev = getenv("ORBFE_HOST_THREADS")) nthreads = atoi(ev);
   if (nthreads < 1) nthreads = 1;
-  m->pool.reset(new orbfe::HostPool(nthreads));
+  m->host->pool.reset(new orbfe::HostPool(nthreads));
   *out = m;
   return ORBFE_OK;
 }
@@ -347,15 +544,6 @@ int orbfe_matcher_synchronize(orbfe_matcher* m) {
   return ORBFE_OK;
 }
 
-extern "C++" {
-namespace orbfe {
-// for orbfe_bow.hip, which keeps its device scratch on the matcher handle
-int matcher_device(const orbfe_matcher* m) { return m->device; }
-hipStream_t matcher_stream(const orbfe_matcher* m) { return m->stream; }
-std::shared_ptr<void>& matcher_bow_slot(orbfe_matcher* m) { return m->bow; }
-}  // namespace orbfe
-}  // extern "C++"
-
 int orbfe_debug_matcher_ms(const orbfe_matcher* m, double out[3]) {
   if (!m || !out) { set_err("NULL argument"); return ORBFE_ERR_INVALID; }
   for (int i = 0; i < 3; i++) out[i] = m->stageMs[i];
@@ -366,11 +554,13 @@ int orbfe_debug_features_in_area(orbfe_matcher* m, const OrbfeKeyPoint* kps_un, 
                                  float y, float r, int min_level, int max_level, int32_t* out, int cap, int* n_out) {
   if (!m || !kps_un || !bounds || !n_out || n < 0) { set_err("bad argument"); return ORBFE_ERR_INVALID; }
   std::vector<uint8_t> zdesc((size_t)std::max(n, 1) * 32, 0), qd(32, 0);
-  int rc = m->candidates(kps_un, zdesc.data(), n, bounds, &x, &y, &r, &min_level, &max_level, qd.data(), 1);
+  HostSearch* S = m->host;
+  const HostSearch::Job job{kps_un, zdesc.data(), n, bounds, &x, &y, &r, &min_level, &max_level, qd.data(), 1};
+  int rc = S->candidates(m, &job, 1);
   if (rc) return rc;
-  const int c = (int)m->qcount[0];
+  const int c = (int)S->qcount[0];
   *n_out = c;
-  for (int i = 0; i < c && i < cap; i++) out[i] = (int)(m->h_pool.p[m->qoff[0] + i] & 0xffff);
+  for (int i = 0; i < c && i < cap; i++) out[i] = (int)(S->h_pool.p[S->qoff[0] + i] & 0xffff);
   return ORBFE_OK;
 }
 
@@ -400,7 +590,7 @@ int orbfe_search_for_initialization_batch(orbfe_matcher* m, int npairs, const Or
   // queries: level-0 keypoints of F1, window centred on vbPrevMatched (ORBmatcher.cc:413-420)
   std::vector<float> qx(nqTot), qy(nqTot), qr(nqTot);
   std::vector<int> qa(nqTot), qb(nqTot);
-  std::vector<orbfe_matcher::Job> jobs(npairs);
+  std::vector<HostSearch::Job> jobs(npairs);
   size_t q0 = 0;
   for (int p = 0; p < npairs; p++) {
     for (int i = 0; i < n1[p]; i++) {
@@ -411,15 +601,16 @@ int orbfe_search_for_initialization_batch(orbfe_matcher* m, int npairs, const Or
       qa[q0 + i] = level1;
       qb[q0 + i] = level1;
     }
-    jobs[p] = orbfe_matcher::Job{kps2[p], desc2[p], n2[p], bounds, qx.data() + q0, qy.data() + q0, qr.data() + q0,
+    jobs[p] = HostSearch::Job{kps2[p], desc2[p], n2[p], bounds, qx.data() + q0, qy.data() + q0, qr.data() + q0,
                                  qa.data() + q0, qb.data() + q0, desc1[p], n1[p]};
     q0 += n1[p];
   }
-  int rc = m->candidates(jobs.data(), npairs);
+  HostSearch* S = m->host;
+  int rc = S->candidates(m, jobs.data(), npairs);
   if (rc) return rc;
   const double tR = orbfe_matcher::nowMs();
-  m->pool->parallelFor(npairs, [&](int p, int) {
-    nmatches[p] = resolveSearchForInitialization(m, m->jobQ0[p], kps1[p], n1[p], kps2[p], n2[p], prev_xy[p],
+  S->pool->parallelFor(npairs, [&](int p, int) {
+    nmatches[p] = resolveSearchForInitialization(S, S->jobQ0[p], kps1[p], n1[p], kps2[p], n2[p], prev_xy[p],
                                                  matches12[p], nnratio, check_orientation);
   });
   m->stageMs[2] = orbfe_matcher::nowMs() - tR;

@@ -193,7 +193,6 @@ __global__ __launch_bounds__(64) void k_refresh_map_points(RefreshParams P) {
 }
 
 struct RefreshScratch {
-  int device = 0;
   DevBuf<uint8_t> d_in, d_out;
   PinBuf<uint8_t> h_in, h_out;
   hipEvent_t sent = nullptr;       // recorded after the last upload: the staging is free again once it has completed
@@ -205,15 +204,6 @@ struct RefreshScratch {
     (void)hipGetLastError();
   }
 };
-
-RefreshScratch* scratch_of(const orbfe::LocalMapView& V) {
-  if (!*V.scratch) {
-    auto s = std::make_shared<RefreshScratch>();
-    s->device = V.m->device;
-    *V.scratch = s;
-  }
-  return static_cast<RefreshScratch*>(V.scratch->get());
-}
 
 }  // namespace
 
@@ -244,7 +234,7 @@ int orbfe_local_map_refresh_rows(orbfe_matcher* m, orbfe_local_map* map, int wha
       set_err("keyframe slot %d and matcher live on different devices", s);
       return ORBFE_ERR_INVALID;
     }
-  RefreshScratch* S = scratch_of(V);
+  RefreshScratch* S = scratch_in<RefreshScratch>(*V.scratch);
   S->seen.assign((size_t)V.capacity, 0);
   const int base = obs_offsets[0];
   int maxKept = 0;

@@ -118,11 +118,6 @@ struct RansacScratch {
   ~RansacScratch() { d_in.release(); h_in.release(); h_out.release(); }
 };
 
-RansacScratch* scratch_of(orbfe_matcher* m) {
-  if (!m->ransac) m->ransac = std::make_shared<RansacScratch>();
-  return static_cast<RansacScratch*>(m->ransac.get());
-}
-
 // hypA / hypB: T12 and T21 (12 floats each) for SIM3; Rt (12 doubles) twice for PNP.
 template <int MODEL>
 int score(orbfe_matcher* m, int n_seg, const int32_t* seg_off, const float* corr, const void* cams, int n_hyp, const int32_t* hyp_seg,
@@ -135,7 +130,7 @@ int score(orbfe_matcher* m, int n_seg, const int32_t* seg_off, const float* corr
   }
   if (!counts && !masks) return ORBFE_OK;
   HIP_TRY(hipSetDevice(m->device));
-  RansacScratch* S = scratch_of(m);
+  RansacScratch* S = scratch_in<RansacScratch>(m->ransac);
   const size_t ns = (size_t)n_seg, nh = (size_t)n_hyp, nc = (size_t)plan.nCorr, nw = (size_t)plan.words;
   constexpr size_t kRowBytes = MODEL == SIM3 ? 48 : 32;
   // the upload image, each part on a 256-byte boundary
