@@ -164,7 +164,13 @@ int orbfe_extract(orbfe_extractor* h, const uint8_t* gray, int rows, int cols, s
 /* Batched form of the same call for independent frames of one size (throughput path: one
  * kernel launch sequence for all frames).  gray[i] points to frame i; in_device_memory != 0
  * means the frame pointers are DEVICE pointers on the handle's GPU (frames already resident in
- * HBM).  kps: nframes*cap entries, desc: nframes*cap*32 bytes, n_out: nframes ints. */
+ * HBM).  kps: nframes*cap entries, desc: nframes*cap*32 bytes, n_out: nframes ints.
+ * A device frame is read in place, at any byte alignment of pointer and stride (a ROI of a
+ * larger device image is fine) and needs no padding: the kernels read whole aligned dwords, so
+ * besides the pixels they touch at most the 3 bytes that share a dword with a frame's first
+ * pixel and the 3 that share one with the last pixel of its last row, and up to 15 bytes behind
+ * the last pixel of every other row (the stride's padding or the next row).  None of those
+ * bytes reaches a result. */
 int orbfe_extract_batch(orbfe_extractor* h, int nframes, const uint8_t* const* gray, int in_device_memory,
                         int rows, int cols, size_t stride_bytes, OrbfeKeyPoint* kps, uint8_t* desc, int cap,
                         int* n_out);
